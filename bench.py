@@ -19,7 +19,12 @@ under torchrun / the driver's own launcher (WORLD_SIZE set) it joins that group.
 `--config cfg3|cfg4` (or TFK_BENCH_CONFIG) runs BASELINE configs[2] / [3] as one GPU of their 8-GPU runs sees them
 (bf16 MFMA, 4000 / 8000 pdfs, 1024 / 2048 frames per GPU); `--gpus 8 --config cfg3` is configs[2] itself.
 
-Besides the contract's fields the line carries: `api_fed_value` (frames/s of Nnet.train itself over ark
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  Its line holds the contract's
+fields, what ran (exchange, collectives, build id) and the losses of the first 20 steps.  `--dump-outputs DIR` writes what
+the timed steps computed (the last step's loss and the parameters it left: dump_outputs) as .npy files.
+
+`--full` adds the diagnostics behind the timed region.  Besides the contract's fields its line carries:
+`api_fed_value` (frames/s of Nnet.train itself over ark
 files: dispenser, host, PCIe, engine -- tools/nnet_train_bench.py), `decode` (log-likelihood passes host to host + the
 forward contractions' roofline), `roofline` (dominant kernel, live HIP-event timing),
 `host_fed_value` (the same step fed from HOST numpy through tfk_accumulate: PCIe inclusive, never `value`),
@@ -48,6 +53,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0           # v_mfma_f32_32x32x16_bf16, dense
 TRACE_STEPS = 20                         # per-step average_loss of the first 20 steps
 CPU_WARMUP = 10                          # warm-up steps kept out of the cpu_baseline rate
 MAX_RING = 16                            # distinct micro-batches resident per rank
+DUMP_SAMPLE = 1 << 18                    # --dump-outputs: entries kept of each weight matrix (a fixed, seeded sample)
+DUMP_SEED = 11
 
 
 class Workload(object):
@@ -486,6 +493,55 @@ def kernel_label(w, family):
     return family.replace("gemm_f32", {"float32": "gemm_bf16x3", "float32_mfma": "gemm_f32", "bfloat16": "gemm_bf16"}[w.dtype])
 
 
+def dump_outputs(directory, w, eng, losses):
+    """--dump-outputs: what the timed steps hand their caller, as .npy files -- the last step's loss (`loss`), every step's loss
+    (`losses`, warm-up first) and the parameters the last step left.  Biases and batch-norm tensors are written whole; of each
+    weight matrix the same DUMP_SAMPLE entries in every run (flat indices drawn with DUMP_SEED, ascending): cfg2's whole model
+    is over 100 MB.  float64 losses, float32 parameters; about 8 MB at cfg2, 10 MB at cfg4."""
+    from tfkaldi_amd import _lib
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+    save("loss", np.array([losses[-1]], dtype=np.float64))
+    save("losses", np.array(losses, dtype=np.float64))
+    rng = np.random.default_rng(DUMP_SEED)
+    for l in range(w.L + 1):
+        weights = eng.get(_lib.WEIGHTS, l).ravel()
+        index = np.sort(rng.choice(weights.size, min(weights.size, DUMP_SAMPLE), replace=False))
+        save("weights_%d" % l, weights[index])
+        save("biases_%d" % l, eng.get(_lib.BIASES, l))
+    for l in range(w.L):
+        for kind, name in ((_lib.BN_BETA, "bn_beta"), (_lib.BN_MOVING_MEAN, "bn_moving_mean"), (_lib.BN_MOVING_VAR, "bn_moving_var")):
+            save("%s_%d" % (name, l), eng.get(kind, l))
+
+
+def contract_line(w, args, world, ring, elapsed, per_rank_ms, backend, ran):
+    """the contract's fields (`elapsed` = the slowest rank's seconds over the timed steps) and `ran`, what ran: all a plain run
+    prints, the start of a --full line"""
+    line = {"metric": "acoustic frames/sec (train step)", "value": world * w.T * args.steps / elapsed, "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": Workload.DTYPE_TEXT[args.dtype],
+            "data": "synthetic ark/scp/alignment files (SURVEY 8d) read through the feature reader + dispenser, %d "
+                    "distinct micro-batches per rank cycled (a different one every step); random-init weights "
+                    "N(0,1/sqrt(d_in)), zero output layer" % ring,
+            "config": {"workload": "%s, %d frames/GPU/step, %s, Adam" % (w.text, w.T, Workload.ARITH_TEXT[args.dtype]),
+                       "name": w.name, "frames_per_gpu": w.T, "global_frames": world * w.T,
+                       "parallelism": "dp%d" % world, "flop_per_frame": w.flop_per_frame},
+            "per_rank_ms_per_step": per_rank_ms, "dist_backend": backend, "rccl_ranks": world if backend == "nccl" else 0}
+    line.update(ran)
+    return line
+
+
+def emit(json_fd, line):
+    """the one JSON line, on the stdout main() set aside"""
+    import ctypes
+    sys.stdout.flush()
+    ctypes.CDLL(None).fflush(None)  # C stdio buffers still point at the diverted fd
+    os.write(json_fd, (json.dumps(line) + "\n").encode())
+
+
 def api_fed_leg(w, world, steps):
     """`Nnet.train` itself (tools/nnet_train_bench.py): the reference's entry point over ark files, dispenser included.
     COLLECTIVE under data parallelism: every rank calls it."""
@@ -519,6 +575,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps, every diagnostic leg: host-fed steps, per-kernel event timing and roofline, "
+                         "sustained leg, exchange A/B and phases (N > 1), exchange model, CPU baseline, float64 loss trace, "
+                         "posterior error, decode, eval, the other fp32 arithmetic, Nnet.train.  The --no-* options below "
+                         "switch single legs off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (dump_outputs) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-f64-trace", action="store_true",
                     help="skip the float64-oracle loss trace (about a minute of host numpy behind the CPU baseline)")
@@ -636,6 +699,39 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     my_ms = 1e3 * elapsed / args.steps
+    ran = {"clock_prewarm_ms": prewarm_ms, "lib_build_id": eng.lib.tfk_build_id().decode(),
+           # what RAN, not what was asked for: the exchange mode the reducer settled on after probing the backend and
+           # the torch.distributed calls of the last timed step, in launch order
+           "exchange": reducer.mode if reducer else None,
+           "exchange_driver": (("library (csrc/exchange.hip, %s)" % reducer.backend) if getattr(reducer, "native", False)
+                               else "torch.distributed (dataparallel.BucketReducer)%s" % (
+                                   "; in-library exchange FAILED: %s" % reducer.fallback_reason
+                                   if getattr(reducer, "fallback_reason", None) else "")) if reducer else None,
+           "exchange_requested": (args.exchange or os.environ.get("TFK_DP_EXCHANGE", "sharded")) if reducer else None,
+           "collectives_last_step": list(reducer.last_executed) if reducer else None,
+           "collective_spans_last_step": [list(x) for x in reducer.last_launched] if reducer else None,
+           "loss_first_last": [losses[0], losses[-1]], "loss_trace_gpu": losses[:TRACE_STEPS]}
+    if args.dump_outputs:
+        dp.gather_parameters(eng)  # (collective: the mixed-precision sharded exchange leaves the fp32 parameters sharded)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, w, eng, losses)
+    if not args.full:
+        per_rank_ms, backend = [my_ms], None
+        if dp.enabled:
+            v = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+            gathered = [torch.zeros_like(v) for _ in range(world)]
+            dist.all_gather(gathered, v)
+            per_rank_ms = [1e3 * float(g.item()) / args.steps for g in gathered]
+            elapsed = max(float(g.item()) for g in gathered)
+            backend = dist.get_backend()
+        eng.close()
+        if dp.enabled:
+            dist.destroy_process_group()
+        if rank == 0:
+            emit(json_fd, contract_line(w, args, world, ring, elapsed, per_rank_ms, backend, ran))
+        return
+
+    # ---- --full: everything behind this line
     # the same step fed from host memory (SURVEY 8d / the reference's feed_dict), a different micro-batch per step
     for _ in range(min(3, args.steps)):
         step_host()
@@ -673,21 +769,11 @@ def main():
     if dp.enabled:
         import threading
         budget_s = float(os.environ.get("TFK_BENCH_DIAG_BUDGET_S", "300"))
-        core_ms = 1e3 * elapsed / args.steps
+        core_line = contract_line(w, args, world, ring, elapsed, per_rank_ms, backend, ran)
 
         def bail_out():
             if rank == 0:
-                line = {"metric": "acoustic frames/sec (train step)", "value": world * T * args.steps / elapsed, "unit": "frames/s",
-                        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": core_ms,
-                        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": Workload.DTYPE_TEXT[args.dtype],
-                        "data": "synthetic ark/scp/alignment files (SURVEY 8d) read through the feature reader + dispenser",
-                        "config": {"workload": "%s, %d frames/GPU/step, %s, Adam" % (w.text, T, Workload.ARITH_TEXT[args.dtype]),
-                                   "name": w.name, "frames_per_gpu": T, "global_frames": world * T, "parallelism": "dp%d" % world,
-                                   "flop_per_frame": w.flop_per_frame},
-                        "per_rank_ms_per_step": per_rank_ms, "dist_backend": backend,
-                        "exchange": reducer.mode if reducer else None,
-                        }
-                line = dict(final.get("line") or line)  # (everything, when only the teardown is stuck)
+                line = dict(final.get("line") or core_line)  # (everything, when only the teardown is stuck)
                 line["incomplete"] = ("the diagnostic legs behind the timed region did not finish within %.0f s "
                                       "(TFK_BENCH_DIAG_BUDGET_S); the contract's fields were measured before them" % budget_s)
                 os.write(json_fd, (json.dumps(line) + "\n").encode())
@@ -841,34 +927,11 @@ def main():
                    "note": "counter bytes of EVERY kernel of a step (fabric side of the L2s, Infinity-Cache hits included) over this "
                            "run's step time; model = 40 P + twin writes (SURVEY 8d); the ratio above 1 is activations, operand "
                            "re-reads across the eight L2s and the twins' reads"}
-        out = {
-            "metric": "acoustic frames/sec (train step)", "value": value, "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "clock_prewarm_ms": prewarm_ms,
-            "ms_per_step": 1e3 * elapsed / args.steps,
+        out = contract_line(w, args, world, ring, elapsed, per_rank_ms, backend, ran)
+        out.update({
             "ms_per_step_with_event_profiling": 1e3 * elapsed_profiled / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": Workload.DTYPE_TEXT[args.dtype],
-            "data": "synthetic ark/scp/alignment files (SURVEY 8d) read through the feature reader + dispenser, %d "
-                    "distinct micro-batches per rank cycled (a different one every step); random-init weights "
-                    "N(0,1/sqrt(d_in)), zero output layer" % ring,
-            "lib_build_id": eng.lib.tfk_build_id().decode(),
-            "config": {"workload": "%s, %d frames/GPU/step, %s, Adam" % (w.text, T, Workload.ARITH_TEXT[args.dtype]),
-                       "name": w.name, "frames_per_gpu": T, "global_frames": world * T,
-                       "parallelism": "dp%d" % world, "flop_per_frame": w.flop_per_frame},
-            "rccl_ranks": world if backend == "nccl" else 0, "dist_backend": backend,
-            # what RAN, not what was asked for: the exchange mode the reducer settled on after probing the backend and
-            # the torch.distributed calls of the last timed step, in launch order
-            "exchange": reducer.mode if reducer else None,
-            "exchange_driver": (("library (csrc/exchange.hip, %s)" % reducer.backend) if getattr(reducer, "native", False)
-                                else "torch.distributed (dataparallel.BucketReducer)%s" % (
-                                    "; in-library exchange FAILED: %s" % reducer.fallback_reason
-                                    if getattr(reducer, "fallback_reason", None) else "")) if reducer else None,
-            "exchange_requested": (args.exchange or os.environ.get("TFK_DP_EXCHANGE", "sharded")) if reducer else None,
-            "collectives_last_step": list(reducer.last_executed) if reducer else None,
-            "collective_spans_last_step": [list(x) for x in reducer.last_launched] if reducer else None,
             "dp_host_ms_per_step": ({k: 1e3 * v / max(1, reducer.host_calls["finish_and_apply"])
                                      for k, v in reducer.host_s.items()} if reducer else None),
-            "per_rank_ms_per_step": per_rank_ms,
             "roofline": {"bound": "mfma", "kernel": kernel_label(w, dom["name"]), "achieved": achieved, "peak": peak,
                          "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
                          "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
@@ -891,10 +954,8 @@ def main():
             "host_fed_value": world * T * args.steps / elapsed_host,
             "host_fed_note": "same step, micro-batch handed over as HOST numpy [%d, 440] + targets through "
                              "tfk_accumulate (PCIe inclusive; never `value`)" % T,
-            "loss_first_last": [losses[0], losses[-1]],
-            "loss_trace_gpu": losses[:TRACE_STEPS],
             "kernel_ms_per_step": {kernel_label(w, s["name"]): s["total_ms"] / args.steps for s in stats},
-        }
+        })
         if sustained:
             sus, sus_stats = sustained
             sus["value"] = world * T / (1e-3 * sus["ms_per_step_last_window"])
@@ -1021,10 +1082,7 @@ def main():
     if watchdog is not None:
         watchdog.cancel()
     if rank == 0:
-        import ctypes
-        sys.stdout.flush()
-        ctypes.CDLL(None).fflush(None)  # C stdio buffers still point at the diverted fd
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        emit(json_fd, out)
 
 
 if __name__ == "__main__":

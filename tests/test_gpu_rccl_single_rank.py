@@ -99,7 +99,7 @@ def test_bench_dp_branch_over_rccl(gpu):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", TFK_FORCE_DP="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup",
-                          "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=500)
+                          "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["value"] > 0
@@ -140,7 +140,7 @@ def test_bench_line_survives_stuck_diagnostics(gpu):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", TFK_FORCE_DP="1", HSA_ENABLE_IPC_MODE_LEGACY="0", TFK_BENCH_DIAG_BUDGET_S="1.0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup",
-                          "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=500)
+                          "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -192,7 +192,7 @@ def test_bench_over_real_rccl_ranks(gpu, world, config):
     if world == 8:  # (Nnet.train under real ranks: the 2- and 4-rank cases)
         env.update(TFK_BENCH_AB_STEPS="3", TFK_BENCH_SUSTAIN_MIN_STEPS="10", TFK_BENCH_API_FED="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
-                          "--config", config], env=env, capture_output=True, text=True, timeout=1100)
+                          "--full", "--config", config], env=env, capture_output=True, text=True, timeout=1100)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -239,7 +239,7 @@ def test_bench_eight_ranks_dry_run(gpu):
     env.update(TFK_SHARE_DEVICE="1", TFK_DIST_BACKEND="gloo", TFK_DP_EMULATE_RS="1", TFK_BENCH_PREWARM_MS="0",
                OMP_NUM_THREADS="2", TFK_BENCH_SUSTAIN_S="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup",
-                          "2"], env=env, capture_output=True, text=True, timeout=1100)
+                          "2", "--full"], env=env, capture_output=True, text=True, timeout=1100)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 8 and line["value"] > 0 and len(line["per_rank_ms_per_step"]) == 8

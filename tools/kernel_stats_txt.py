@@ -10,7 +10,7 @@ note = sys.argv[3] if len(sys.argv) > 3 else ""
 f = glob.glob("%s/trace/**/*kernel_stats.csv" % src, recursive=True)[0]
 shutil.copy(f, dst + "_bench_kernel_stats.csv")
 with open(dst + "_bench_kernel_stats.txt", "w") as out:
-    out.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 50 --warmup 5 "
+    out.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 50 --warmup 5 "
               "--no-cpu-baseline   (MI355X%s)\n" % (", " + note if note else ""))
     out.write("# 5 warm-up + 50 timed (HBM-resident input) + 3 + 50 host-fed + 50 event-profiled steps of BASELINE cfg2; avg/min/max in "
               "microseconds (tfk::(anonymous namespace):: stripped)\n")

@@ -3,10 +3,11 @@
 # mapped memory the host polls (default): un-profiled bench steps interleaved three times, and the gap in front of adam_kernel from a
 # kernel trace of each.  usage: bash tools/loss_seq_ablate.sh [tag]; summary -> gpurun_out/<tag>/summary.txt
 tag=${1:-loss_seq}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository root
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 export TFK_BENCH_PREWARM_MS=0 TFK_BENCH_SUSTAIN_S=0
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-decode --no-other-arithmetic --no-eval --no-f64-trace"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-decode --no-other-arithmetic --no-eval --no-f64-trace"
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
   TFK_LOSS_EVENT=$v timeout 300 rocprofv3 --kernel-trace --output-format csv -d $out/ev$v -- $B --no-api-fed --steps 60 --warmup 5 > $out/ev$v.log 2>&1

@@ -29,7 +29,7 @@ for f in glob.glob("%s/pmc*/**/*counter_collection.csv" % src, recursive=True):
             acc[fam][r["Counter_Name"]].append(float(r["Counter_Value"]))
             dur[fam].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 with open(dst + "_bench_pmc.txt", "w") as out:
-    out.write("# rocprofv3 --pmc (counter-only passes, tools/profile_round.sh) over `python bench.py --steps 10 --warmup 3 "
+    out.write("# rocprofv3 --pmc (counter-only passes, tools/profile_round.sh) over `python bench.py --full --steps 10 --warmup 3 "
               "--no-cpu-baseline` (BASELINE cfg2 in the bench's default arithmetic), 1x MI355X: mean per launch.\n"
               "# SQ_* cycle counters are quad-cycles summed over all waves; SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over the 1024 "
               "SIMDs (64 per v_mfma_f32_32x32x2_f32, 32 per v_mfma_f32_32x32x16_bf16).\n"

@@ -3,10 +3,11 @@
 # default (none behind the LAST micro-batch of a step: the slot is free once the host has seen the step's loss) -- the bench command with
 # its host-fed and Nnet.train legs, three interleaved repetitions.  usage: bash tools/slot_event_ablate.sh [tag]
 tag=${1:-slot_event}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository root
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 export TFK_BENCH_SUSTAIN_S=0
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-decode --no-other-arithmetic --no-eval --no-f64-trace"
+B="python $ROOT/bench.py --full --no-cpu-baseline --no-decode --no-other-arithmetic --no-eval --no-f64-trace"
 cd $GRAFT_REPO_ROOT
 for rep in 1 2 3; do
   for v in 1 0; do
