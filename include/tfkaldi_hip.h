@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 8
+#define TFK_ABI_VERSION 9
 
 typedef struct tfk_engine tfk_engine;
 
@@ -248,6 +248,28 @@ int tfk_set_prior(tfk_engine* e, const float* prior, size_t count); /* prior.npy
  * several utterances per call = the batched decode of SURVEY 8f-2). */
 int tfk_posteriors_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t N, const int32_t* utt_len, int32_t U,
                        int32_t context_width, const float* cmvn, float* out, int64_t ldo, int flags);
+
+/* (ABI 9) Best-path CTC decoding -- tf.nn.ctc_greedy_decoder(merge_repeated=True), the standard evaluation of a model
+ * trained with tfk_accumulate_ctc -- and its label errors, tf.edit_distance(normalize=False).  Eval-mode forward of the
+ * flat utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T), per-frame argmax of the LOGITS (ties: the
+ * lowest class; a NaN loses to every number), repeats merged (a blank between two equal classes keeps both), blanks (the
+ * LAST class) removed.  hyp[T]: utterance u's labels start at row sum_{v<u} utt_len[v], the rest of its rows are -1;
+ * hyp_len[U]: their counts.  With ref_labels / ref_len (back to back, as tfk_accumulate_ctc takes labels: values in
+ * [0, output_dim - 1), at most 511 per utterance) and edits[U] non-NULL: edits[u] = Levenshtein distance (unit costs) of
+ * hypothesis and reference.  Host pointers.  Evaluation mode; parameters, accumulators and statistics are not touched
+ * (same rules as tfk_posteriors).  flags: 0. */
+int tfk_ctc_greedy(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                   const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len,
+                   int32_t* edits, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                       int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
+                       int32_t* hyp, int32_t* hyp_len, int32_t* edits, int flags);
+/* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
+ * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
+ * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */
+int tfk_label_edit_distance(void* stream, const int32_t* hyp, const int32_t* hyp_off, const int32_t* ref,
+                            const int32_t* ref_off, int32_t U, int32_t* dist);
 
 /* ---- data parallelism (one engine per rank; the host owns the collective) --------------------- */
 

@@ -43,4 +43,16 @@ void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_gr
 // lengths), scalars[2] (+)= 1
 void ctc_loss_reduce(hipStream_t s, const float* utt_loss, const int32_t* lab_off, int U, float* scalars, bool overwrite);
 
+// Best-path decoding (tf.nn.ctc_greedy_decoder, merge_repeated=True) of the utterances seg[U + 1] over logits [T, ld]:
+// cls[t] = the frame's largest logit (ties: lowest class; a NaN loses to every number); hyp[seg[u] + n] = utterance u's
+// n-th label (repeats merged, then the blank O - 1 removed), -1 on its remaining rows; hyp_len[u] = its label count.
+void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int32_t* cls,
+                   int32_t* hyp, int32_t* hyp_len);
+// tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
+// ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
+// length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,
+// kCtcMaxLabels) gets -1.
+void label_edit_distance(hipStream_t s, const int32_t* hyp, const int32_t* hyp_off, const int32_t* hyp_cnt,
+                         const int32_t* ref, const int32_t* ref_off, int U, int max_ref, int32_t* dist);
+
 }  // namespace tfk

@@ -338,6 +338,137 @@ int regs_for(int max_labels) {
   return r;
 }
 
+// ---- best-path decoding and label edit distance (tf.nn.ctc_greedy_decoder + tf.edit_distance) ----
+
+__device__ __forceinline__ int lane_prev_i(int v, int fill, int lane) {
+  const int r = __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+  return lane == 0 ? fill : r;
+}
+// does (v, i) win against (bv, bi)?  Larger value; on ties the lower class (TF's row max); a NaN loses to every number
+// (and, between NaNs, the lower class wins: a row of NaNs decodes as class 0)
+__device__ __forceinline__ bool beats(float v, int i, float bv, int bi) {
+  if (v > bv) return true;
+  if (v < bv) return false;
+  const bool vn = __builtin_isnan(v), bn = __builtin_isnan(bv);
+  if (vn != bn) return bn;
+  return i < bi;
+}
+
+// one wave per row: cls[t] = the winning class of logits row t.  One read of T x O floats.
+__global__ void __launch_bounds__(256)
+ctc_row_argmax_kernel(const float* __restrict__ logits, int ld, int O, int T, int32_t* __restrict__ cls) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= T) return;
+  const float* z = logits + (size_t)row * ld;
+  float bv = __builtin_nanf("");
+  int bi = 0x7fffffff;  // (NaN, beyond every class): loses to any element
+  for (int c = lane; c < O; c += 64) {
+    const float v = z[c];
+    if (beats(v, c, bv, bi)) { bv = v; bi = c; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) cls[row] = bi;
+}
+
+// ONE WAVE PER UTTERANCE: the frame's class and its predecessor's (a DPP shift; the last class of the previous 64-frame
+// chunk is carried in) give the emit mask k != blank && k != k_prev by ballot; a label's output row is the count so far
+// plus the emitting lanes below it (mbcnt).  hyp[seg[u] + n] = n-th label, -1 on the utterance's remaining rows.
+__global__ void __launch_bounds__(64)
+ctc_merge_kernel(const int32_t* __restrict__ cls, const int32_t* __restrict__ seg, int blank, int32_t* __restrict__ hyp,
+                 int32_t* __restrict__ hyp_len) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  int carry = -1;  // class of the frame before the chunk: none before the first
+  int n = 0;       // labels emitted so far (wave-uniform)
+  for (int f0 = 0; f0 < Tn; f0 += 64) {
+    const int f = f0 + lane;
+    const int k = f < Tn ? cls[r0 + f] : blank;
+    const int prev = lane_prev_i(k, carry, lane);
+    const bool emit = k != blank && k != prev;
+    const uint64_t m = __ballot(emit);
+    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (emit) hyp[r0 + n + below] = k;  // n + below <= f < Tn
+    n += __popcll(m);
+    carry = __builtin_amdgcn_readlane(k, 63);
+  }
+  for (int f = n + lane; f < Tn; f += 64) hyp[r0 + f] = -1;
+  if (lane == 0) hyp_len[u] = n;
+}
+
+// Levenshtein distance D[H][S] (unit costs) of hyp[0, H) and ref[0, S): ONE WAVE PER PAIR, systolic over the
+// anti-diagonals.  Lane k owns the R reference columns j = kR+1 .. kR+R in registers (prev[r] = D[i-1][j], the row above)
+// and computes row i = s - k at step s.  The left boundary D[i][kR] and the hypothesis token h[i-1] are what lane k-1
+// produced / used at step s-1, moved one lane up by DPP; the diagonal D[i-1][kR] is the boundary that arrived at step s-1.
+// Lane 0 takes D[i][0] = i and its token from a 64-token register window (prefetched one window ahead).
+// Bound: H + ceil(S / R) - 1 dependent steps of 2 DPP moves + ~3R + 8 VALU ops each -- no LDS, no barrier, one read of
+// both sequences.  A pair with a negative length or a reference longer than min(64 R, kCtcMaxLabels) gets -1.
+template <int R>
+__global__ void __launch_bounds__(64)
+edit_distance_kernel(const int32_t* __restrict__ hyp, const int32_t* __restrict__ hyp_off,
+                     const int32_t* __restrict__ hyp_cnt, const int32_t* __restrict__ ref,
+                     const int32_t* __restrict__ ref_off, int32_t* __restrict__ dist) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int h0 = hyp_off[u], H = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - h0;
+  const int g0 = ref_off[u], S = ref_off[u + 1] - g0;
+  if (H < 0 || S < 0 || S > 64 * R || S > kCtcMaxLabels) {
+    if (lane == 0) dist[u] = -1;
+    return;
+  }
+  if (H == 0 || S == 0) {
+    if (lane == 0) dist[u] = H + S;
+    return;
+  }
+  const int c0 = lane * R;           // the lane's first column is j = c0 + 1
+  const int steps = H + (S + R - 1) / R - 1;
+  int rf[R], prev[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    rf[r] = c0 + r < S ? ref[g0 + c0 + r] : -1;  // (columns beyond S never reach D[H][S])
+    prev[r] = c0 + r + 1;                        // D[0][j] = j
+  }
+  int out = c0 + R;      // the lane's last column in the row it holds: lane k+1's left boundary
+  int tok = 0;           // the token of that row
+  int left_prev = c0;    // the boundary received at the previous step: this step's diagonal
+  int win = lane < H ? hyp[h0 + lane] : -1;
+  int nxt = 64 + lane < H ? hyp[h0 + 64 + lane] : -1;
+  for (int b = 0; 64 * b < steps; ++b) {
+    for (int j = 0; j < 64; ++j) {
+      const int s = 64 * b + j + 1;  // lane 0's row; its token is h[s - 1] = window lane j
+      if (s > steps) break;
+      const int i = s - lane;
+      const int left = lane_prev_i(out, s, lane);  // lane 0: D[s][0] = s
+      const int t = lane_prev_i(tok, __builtin_amdgcn_readlane(win, j), lane);
+      if (i >= 1 && i <= H) {
+        int l = left, d = left_prev;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int up = prev[r];
+          const int v = min(min(up, l) + 1, d + (t != rf[r] ? 1 : 0));
+          d = up;
+          l = v;
+          prev[r] = v;
+        }
+      }
+      out = prev[R - 1];
+      tok = t;
+      left_prev = left;
+    }
+    win = nxt;
+    const int q = 64 * (b + 2) + lane;
+    nxt = q < H ? hyp[h0 + q] : -1;
+  }
+  int res = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (c0 + r == S - 1) res = prev[r];
+  if (lane == (S - 1) / R) dist[u] = res;
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -361,6 +492,24 @@ void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_gr
 void ctc_loss_reduce(hipStream_t s, const float* utt_loss, const int32_t* lab_off, int U, float* scalars,
                      bool overwrite) {
   hipLaunchKernelGGL(ctc_loss_reduce_kernel, dim3(1), dim3(256), 0, s, utt_loss, lab_off, U, scalars, overwrite ? 1 : 0);
+}
+
+void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int32_t* cls,
+                   int32_t* hyp, int32_t* hyp_len) {
+  if (T > 0) hipLaunchKernelGGL(ctc_row_argmax_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, cls);
+  if (U > 0) hipLaunchKernelGGL(ctc_merge_kernel, dim3(U), dim3(64), 0, s, cls, seg, O - 1, hyp, hyp_len);
+}
+
+void label_edit_distance(hipStream_t s, const int32_t* hyp, const int32_t* hyp_off, const int32_t* hyp_cnt,
+                         const int32_t* ref, const int32_t* ref_off, int U, int max_ref, int32_t* dist) {
+  if (U <= 0) return;
+  const int r = max_ref <= 64 ? 1 : max_ref <= 128 ? 2 : max_ref <= 256 ? 4 : 8;
+  switch (r) {
+    case 1: hipLaunchKernelGGL(edit_distance_kernel<1>, dim3(U), dim3(64), 0, s, hyp, hyp_off, hyp_cnt, ref, ref_off, dist); break;
+    case 2: hipLaunchKernelGGL(edit_distance_kernel<2>, dim3(U), dim3(64), 0, s, hyp, hyp_off, hyp_cnt, ref, ref_off, dist); break;
+    case 4: hipLaunchKernelGGL(edit_distance_kernel<4>, dim3(U), dim3(64), 0, s, hyp, hyp_off, hyp_cnt, ref, ref_off, dist); break;
+    default: hipLaunchKernelGGL(edit_distance_kernel<8>, dim3(U), dim3(64), 0, s, hyp, hyp_off, hyp_cnt, ref, ref_off, dist); break;
+  }
 }
 
 }  // namespace tfk

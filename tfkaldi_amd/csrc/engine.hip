@@ -66,13 +66,13 @@ struct LayerLayout {
 
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
-  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_COUNT
+  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
                                      "act_forward",             "hidden_backward",  "colsum",          "softmax_xent",
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
-                                     "misc"};
+                                     "misc",                    "ctc_best_path",    "edit_distance"};
 
 struct ProfRec {
   int family;
@@ -178,6 +178,12 @@ struct tfk_engine {
   size_t ctc_cap_offrows = 0;
   size_t ctc_cap_seg = 0, ctc_cap_off = 0, ctc_cap_loss = 0, ctc_cap_lab = 0, ctc_cap_lp = 0, ctc_cap_ab = 0,
          ctc_cap_rows = 0;
+  // best-path decoding (tfk_ctc_greedy): [class ids T | hypotheses T | their lengths U | edit distances U] on the
+  // device, the last T + 2U of it pinned on the host
+  int32_t* ctc_dec = nullptr;
+  size_t ctc_cap_dec = 0;
+  int32_t* h_dec = nullptr;
+  size_t h_dec_cap = 0;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1355,17 +1361,20 @@ int grow(tfk_engine* e, Tp** p, size_t* cap, size_t need) {
   *cap = n;
   return 0;
 }
-// Loss + dLogits of one CTC micro-batch (logits already in e->logits).  Replaces compute_loss of the reference's
-// CTCTrainer (trainer.py:533-570); batch_loss += sum of -log p, num_frames += number of labels (trainer.py:126-133).
-int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
-  if (c.U <= 0 || !c.utt_len || !c.label_len) return fail(-1, "CTC: no utterances");
+// Validate the utterance / label tables of a CTC batch and stage (seg, lab_off, labels) in e->ctc_seg / ctc_lab_off /
+// ctc_lab on the engine's stream.  Labels follow tf.nn.ctc_loss: values in [0, O - 1) (the blank is the LAST class), at most
+// kCtcMaxLabels per utterance.  label_len may be NULL only when !need_labels (no references: every label count is 0).
+// Returns the longest label sequence in *max_labels_out.
+int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max_labels_out) {
+  if (c.U <= 0 || !c.utt_len || (need_labels && !c.label_len)) return fail(-1, "CTC: no utterances");
   std::vector<int32_t> seg(c.U + 1, 0), off(c.U + 1, 0);
   int max_labels = 0;
   for (int u = 0; u < c.U; ++u) {
-    if (c.utt_len[u] < 0 || c.label_len[u] < 0) return fail(-1, "CTC: negative length");
+    const int32_t n = c.label_len ? c.label_len[u] : 0;
+    if (c.utt_len[u] < 0 || n < 0) return fail(-1, "CTC: negative length");
     seg[u + 1] = seg[u] + c.utt_len[u];
-    off[u + 1] = off[u] + c.label_len[u];
-    max_labels = c.label_len[u] > max_labels ? c.label_len[u] : max_labels;
+    off[u + 1] = off[u] + n;
+    max_labels = n > max_labels ? n : max_labels;
   }
   if (seg[c.U] != T) return fail(-1, "CTC: utterance lengths sum to %d, expected T = %d", seg[c.U], T);
   if (max_labels > kCtcMaxLabels) return fail(-1, "CTC: %d labels in one utterance (limit %d)", max_labels, kCtcMaxLabels);
@@ -1373,20 +1382,9 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   if (total > 0 && !c.labels) return fail(-1, "CTC: labels is NULL");
   for (int i = 0; i < total; ++i)  // the blank is the LAST class (tf.nn.ctc_loss): labels live in [0, O - 1)
     if (c.labels[i] < 0 || c.labels[i] >= e->O - 1) return fail(-1, "CTC: label %d outside [0, %d)", c.labels[i], e->O - 1);
-  const int sext = ctc_state_stride(max_labels);
   CHK(grow(e, &e->ctc_seg, &e->ctc_cap_seg, (size_t)c.U + 1));
   CHK(grow(e, &e->ctc_lab_off, &e->ctc_cap_off, (size_t)c.U + 1));
-  CHK(grow(e, &e->ctc_utt_loss, &e->ctc_cap_loss, (size_t)c.U));
   CHK(grow(e, &e->ctc_lab, &e->ctc_cap_lab, (size_t)(total > 0 ? total : 1)));
-  CHK(grow(e, &e->ctc_lp, &e->ctc_cap_lp, (size_t)T * sext));
-  CHK(grow(e, &e->ctc_ab, &e->ctc_cap_ab, (size_t)T * sext));
-  CHK(grow(e, &e->ctc_lse, &e->ctc_cap_rows, (size_t)T));
-  CHK(grow(e, &e->ctc_off, &e->ctc_cap_offrows, (size_t)T));
-  CHK(grow(e, &e->ctc_logz, &e->ctc_cap_logz, (size_t)c.U));
-  if (train) {
-    CHK(grow(e, &e->ctc_bb, &e->ctc_cap_bb, (size_t)T * sext));
-    CHK(grow(e, &e->ctc_offb, &e->ctc_cap_offb, (size_t)T));
-  }
   {
     // The three small tables go through pinned staging, two buffers used in turn: the host never waits for the
     // stream here (the event guards the buffer's use two micro-batches ago).
@@ -1411,6 +1409,26 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
       HIPCHK(hipMemcpyAsync(e->ctc_lab, h + 2 * (c.U + 1), (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice,
                             e->stream));
     HIPCHK(hipEventRecord(e->ctc_staged[k], e->stream));
+  }
+  *max_labels_out = max_labels;
+  return 0;
+}
+
+// Loss + dLogits of one CTC micro-batch (logits already in e->logits).  Replaces compute_loss of the reference's
+// CTCTrainer (trainer.py:533-570); batch_loss += sum of -log p, num_frames += number of labels (trainer.py:126-133).
+int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
+  int max_labels = 0;
+  CHK(ctc_stage(e, c, T, true, &max_labels));
+  const int sext = ctc_state_stride(max_labels);
+  CHK(grow(e, &e->ctc_utt_loss, &e->ctc_cap_loss, (size_t)c.U));
+  CHK(grow(e, &e->ctc_lp, &e->ctc_cap_lp, (size_t)T * sext));
+  CHK(grow(e, &e->ctc_ab, &e->ctc_cap_ab, (size_t)T * sext));
+  CHK(grow(e, &e->ctc_lse, &e->ctc_cap_rows, (size_t)T));
+  CHK(grow(e, &e->ctc_off, &e->ctc_cap_offrows, (size_t)T));
+  CHK(grow(e, &e->ctc_logz, &e->ctc_cap_logz, (size_t)c.U));
+  if (train) {
+    CHK(grow(e, &e->ctc_bb, &e->ctc_cap_bb, (size_t)T * sext));
+    CHK(grow(e, &e->ctc_offb, &e->ctc_cap_offb, (size_t)T));
   }
   CtcBatch b;
   b.logits = e->logits; b.ld = e->ldO; b.post = e->post; b.lse = e->ctc_lse;
@@ -1874,8 +1892,9 @@ int tfk_destroy(tfk_engine* e) {
   if (e->ws_splitk) hipFree(e->ws_splitk);
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
-                  (void*)e->ctc_logz})
+                  (void*)e->ctc_logz, (void*)e->ctc_dec})
     if (p) hipFree(p);
+  if (e->h_dec) hipHostFree(e->h_dec);
   for (hipEvent_t ev : e->post_ev) hipEventDestroy(ev);
   for (int k = 0; k < 2; ++k) {
     if (e->h_ctc[k]) hipHostFree(e->h_ctc[k]);
@@ -2501,6 +2520,90 @@ int tfk_posteriors_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t N
   const RawSpec r = {utt_len, U, context_width, cmvn};
   if (!utt_len) return fail(-1, "utt_len is NULL");
   return posteriors_impl(e, raw, ldraw, N, out, ldo, flags, &r);
+}
+
+// Best-path CTC decoding (tf.nn.ctc_greedy_decoder, merge_repeated=True) + tf.edit_distance(normalize=False) against the
+// references: evaluation-mode forward as tfk_posteriors, then ctc_best_path (and label_edit_distance) on the logits in
+// HBM; T + 2U int32 go back to the host instead of T x O floats.
+static int ctc_greedy_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                           const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len,
+                           int32_t* edits, int flags, const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
+    return fail(-1, "flags %d: tfk_ctc_greedy takes 0, tfk_ctc_greedy_raw 0 or TFK_RAW_DEVICE", flags);
+  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
+  if (!X) return fail(-1, "X is NULL");
+  if (!hyp || !hyp_len) return fail(-1, "hyp / hyp_len is NULL");
+  if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  CHK(reserve(e, T));
+  const CtcSpec c = {utt_len, U, ref_labels, ref_len};
+  int max_ref = 0;
+  CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
+  const size_t words = 2 * (size_t)T + 2 * (size_t)U;  // [class ids | hypotheses | lengths | distances]
+  CHK(grow(e, &e->ctc_dec, &e->ctc_cap_dec, words));
+  const float* Xd; const int32_t* yd; int ld;
+  const int slot_before = e->slot;
+  if (raw) CHK(stage_raw(e, X, ldx, nullptr, T, raw->utt_len, raw->U, raw->context, raw->cmvn, &Xd, &ld, &yd, (flags & TFK_RAW_DEVICE) != 0));
+  else CHK(stage_input(e, X, ldx, nullptr, T, 0, &Xd, &ld, &yd));
+  if (e->bf16) CHK(twin_input(e, &Xd, &ld, T));
+  const int nact = e->nact();
+  const uint32_t call = e->call_counter++;
+  CHK(forward(e, Xd, ld, T, 0, nact, nact, call));
+  int32_t* d_cls = e->ctc_dec;
+  int32_t* d_hyp = d_cls + T;
+  int32_t* d_len = d_hyp + T;
+  int32_t* d_dist = d_len + U;
+  {
+    ProfScope ps(e, KF_CTC_BEST_PATH, 0, 4.0 * T * e->O + 12.0 * T);
+    ctc_best_path(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, d_cls, d_hyp, d_len);
+  }
+  if (edits) {
+    ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
+    label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_dist);
+  }
+  HIPCHK(hipGetLastError());
+  CHK(finish_slot(e, flags, slot_before));
+  const size_t back = (size_t)T + 2 * (size_t)U;
+  if (back > e->h_dec_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
+    e->h_dec = nullptr;
+    e->h_dec_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
+    e->h_dec_cap = back + back / 2;
+  }
+  HIPCHK(hipMemcpyAsync(e->h_dec, d_hyp, (edits ? back : back - U) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  e->last_T = T; e->last_nfw = nact; e->last_call = call; e->last_in = Xd;
+  CHK(check_kernel_errors(e));
+  memcpy(hyp, e->h_dec, (size_t)T * sizeof(int32_t));
+  memcpy(hyp_len, e->h_dec + T, (size_t)U * sizeof(int32_t));
+  if (edits) memcpy(edits, e->h_dec + T + U, (size_t)U * sizeof(int32_t));
+  return 0;
+}
+
+int tfk_ctc_greedy(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                   const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, int32_t* edits,
+                   int flags) {
+  return ctc_greedy_impl(e, X, ldx, T, utt_len, U, ref_labels, ref_len, hyp, hyp_len, edits, flags, nullptr);
+}
+int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                       int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
+                       int32_t* hyp, int32_t* hyp_len, int32_t* edits, int flags) {
+  const RawSpec r = {utt_len, U, context_width, cmvn};
+  if (!utt_len) return fail(-1, "utt_len is NULL");
+  return ctc_greedy_impl(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp, hyp_len, edits, flags, &r);
+}
+int tfk_label_edit_distance(void* stream, const int32_t* hyp, const int32_t* hyp_off, const int32_t* ref,
+                            const int32_t* ref_off, int32_t U, int32_t* dist) {
+  if (U < 0) return fail(-1, "U = %d < 0", U);
+  if (U == 0) return 0;
+  if (!hyp_off || !ref_off || !dist) return fail(-1, "hyp_off / ref_off / dist is NULL");
+  label_edit_distance((hipStream_t)stream, hyp, hyp_off, nullptr, ref, ref_off, U, kCtcMaxLabels, dist);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int tfk_reduce_region(tfk_engine* e, void** device_ptr, size_t* num_floats) {

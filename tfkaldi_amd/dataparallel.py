@@ -161,6 +161,19 @@ def _eval_accumulate_all(engine, mine):
         _eval_accumulate(engine, mb)
 
 
+def _label_errors(engine, mb):
+    """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding"""
+    if not isinstance(mb, CtcMicroBatch):
+        raise TypeError("label errors need CTC micro-batches (label sequences), not %s" % type(mb).__name__)
+    if mb.context_width is not None:
+        _, edits = engine.ctc_greedy_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, labels=mb.labels,
+                                         label_lens=mb.label_lens)
+    else:
+        _, edits = engine.ctc_greedy(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens)
+    import numpy as np
+    return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
+
+
 def _run_overlap(overlap):
     """the host work a step overlaps with the GPU (the dispenser's prefetch): run it, and hand back what it raised instead of
     letting it unwind in the middle of the step -- the collective part of the step must complete on every rank first (a rank
@@ -1272,6 +1285,30 @@ class DataParallel(object):
             return self.eval_own(engine, microbatches)
         start, end = partition(len(microbatches), self.world)[self.rank]
         return self.eval_own(engine, microbatches[start:end])
+
+    def label_errors(self, engine, microbatches):
+        """(edits, reference labels): best-path label errors summed over the CTC micro-batches of the WHOLE batch (identical
+        on every rank).  COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and
+        the two counts are SUM all-reduced as one int64 tensor over self.group (on the device for an NCCL / RCCL group)."""
+        mine = microbatches
+        if self.enabled:
+            start, end = partition(len(microbatches), self.world)[self.rank]
+            mine = microbatches[start:end]
+        edits = labels = 0
+        for mb in mine:
+            e, n = _label_errors(engine, mb)
+            edits += e
+            labels += n
+        if not self.enabled:
+            return edits, labels
+        import torch
+        import torch.distributed as dist
+        counts = torch.tensor([edits, labels], dtype=torch.int64)
+        if dist.get_backend(self.group) == "nccl":
+            counts = counts.cuda(engine.cfg.device)
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        counts = counts.cpu()
+        return int(counts[0]), int(counts[1])
 
     def eval_own(self, engine, mine):
         """validation loss from THIS rank's micro-batches (all of them in a single-process run)"""

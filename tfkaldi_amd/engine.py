@@ -346,6 +346,77 @@ class Engine(object):
             self._raw_release()
         return out
 
+    # ---- best-path CTC decoding: tf.nn.ctc_greedy_decoder(merge_repeated=True) + tf.edit_distance(normalize=False) ----
+    def _greedy_refs(self, utt_lens, labels, label_lens):
+        utt_lens = np.ascontiguousarray(utt_lens, dtype=np.int32).reshape(-1)
+        if (labels is None) != (label_lens is None):
+            raise ValueError("labels and label_lens go together")
+        if labels is None:
+            return utt_lens, None, None, c_void_p(None), c_void_p(None), None
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
+        if label_lens.size != utt_lens.size or int(label_lens.sum()) != labels.size:
+            raise ValueError("references: %d label counts (sum %d) for %d utterances and %d labels"
+                             % (label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
+        edits = np.empty(utt_lens.size, dtype=np.int32)
+        return (utt_lens, labels, label_lens, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
+                edits)
+
+    @staticmethod
+    def _greedy_result(hyp, hyp_len, utt_lens, edits):
+        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
+        return [hyp[s:s + n].copy() for s, n in zip(starts, hyp_len)], edits
+
+    def ctc_greedy(self, X, utt_lens, labels=None, label_lens=None):
+        """Best-path decoding of the utterances X [sum(utt_lens), F] (tfk_ctc_greedy): per frame the largest logit, repeats
+        merged, blanks (the last class) removed.  With references (labels back to back, label_lens per utterance) also the
+        Levenshtein distance of every hypothesis to its reference.  Returns (list of int32 label arrays, int32 [U] edit
+        distances or None)."""
+        X = _f32(X)
+        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
+        if int(utt_lens.sum()) != X.shape[0]:
+            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
+        if X.shape[0] == 0:  # only zero-frame utterances: empty hypotheses, the reference lengths as distances
+            return [np.zeros(0, dtype=np.int32) for _ in utt_lens], None if edits is None else label_lens.copy()
+        hyp = np.empty(X.shape[0], dtype=np.int32)
+        hyp_len = np.empty(utt_lens.size, dtype=np.int32)
+        check(self.lib.tfk_ctc_greedy(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
+                                      utt_lens.ctypes.data_as(c_void_p), utt_lens.size, lab_ptr, len_ptr,
+                                      hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
+                                      c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), 0))
+        return self._greedy_result(hyp, hyp_len, utt_lens, edits)
+
+    def ctc_greedy_raw(self, raw, utt_lens, context_width, cmvn=None, labels=None, label_lens=None):
+        """ctc_greedy on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        flags = 0
+        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
+        if self._on_device(raw):
+            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
+            flags |= _lib.RAW_DEVICE
+            cols = raw.shape[1]
+        else:
+            raw, utt_lens = self._raw_batch(raw, utt_lens)
+            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
+        if rows == 0:
+            self._raw_release()
+            return [np.zeros(0, dtype=np.int32) for _ in utt_lens], None if edits is None else label_lens.copy()
+        if cmvn is not None:
+            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
+            if cmvn.shape != (utt_lens.size, 2, cols):
+                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
+        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
+        hyp = np.empty(rows, dtype=np.int32)
+        hyp_len = np.empty(utt_lens.size, dtype=np.int32)
+        try:
+            check(self.lib.tfk_ctc_greedy_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
+                                              int(context_width), cmvn_ptr, lab_ptr, len_ptr, hyp.ctypes.data_as(c_void_p),
+                                              hyp_len.ctypes.data_as(c_void_p),
+                                              c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), flags))
+        finally:
+            self._raw_release()
+        return self._greedy_result(hyp, hyp_len, utt_lens, edits)
+
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):
         X = _f32(X)

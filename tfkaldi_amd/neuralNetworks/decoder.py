@@ -69,6 +69,25 @@ class Decoder(object):
             flat = self.engine.posteriors(stack, log_div_prior=log_div_prior)
         return np.split(flat, np.cumsum(lens)[:-1])
 
+    def ctc_best_path(self, utterances):
+        """Best-path decoding of a CTC model (tf.nn.ctc_greedy_decoder with merge_repeated=True, the reference framework's
+        standard CTC evaluation): every utterance in ONE forward pass, per frame the largest logit, repeats merged, blanks
+        (the last class) removed, on the device (tfk_ctc_greedy).  Returns one int32 label array per utterance; text comes
+        from the trainer's TargetCoder.decode.  All `Unspliced` -> device-side splice, as decode_batch."""
+        if len(utterances) == 0:
+            return []
+        lens = [u.shape[0] for u in utterances]
+        for u in utterances:
+            self._check(u)
+        if all(isinstance(u, Unspliced) for u in utterances):
+            hyps, _ = self.engine.ctc_greedy_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
+                                                 utterances[0].context_width, cmvn=cmvn_table(utterances))
+        else:
+            stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
+                                    for u in utterances])
+            hyps, _ = self.engine.ctc_greedy(stack, lens)
+        return hyps
+
     def set_prior(self, prior):
         self.engine.set_prior(prior)
 

@@ -1,5 +1,9 @@
 """GPU tool: time the CTC training step on a BASELINE configs[4]-like workload (4x512 DNN, 440 in, 35 characters +
-blank, 16 utterances x 800 frames, 100 labels each) and print the per-kernel-family HIP-event profile."""
+blank, 16 utterances x 800 frames, 100 labels each) and print the per-kernel-family HIP-event profile; then the decode leg:
+best-path decoding + label edit distances on the device (tfk_ctc_greedy) against the eval-mode forward alone and against the
+host alternative (logits to the host, numpy argmax + merge, a Python Levenshtein), once with random output weights (long
+hypotheses: the edit distance's worst case) and once with the blank biased so that hypotheses come out near the reference
+length.  `--decode-only` skips the training step (e.g. under rocprofv3)."""
 import os
 import sys
 import time
@@ -23,6 +27,13 @@ def main():
     raw = rng.standard_normal((T, F // 11)).astype(np.float32)  # 40-dim unspliced frames, context 5
     labels = rng.integers(0, O - 1, size=U * S).astype(np.int32)
     utt, lab = [Tu] * U, [S] * U
+    if "--decode-only" not in sys.argv:
+        train_leg(eng, X, raw, utt, labels, lab, T)
+    decode_leg(eng, X, utt, labels, lab, rng)
+    eng.close()
+
+
+def train_leg(eng, X, raw, utt, labels, lab, T):
     K = 10
     for name, step in (("host-spliced frames, 22 MB over PCIe", lambda: eng.accumulate_ctc(X, utt, labels, lab, last=True)),
                        ("unspliced frames, splice on the device",
@@ -42,7 +53,79 @@ def main():
         eng.apply()
     for s in eng.profile_end():
         print("  %-28s n=%4d %9.3f ms/step" % (s["name"], s["launches"] // K, s["total_ms"] / K))
-    eng.close()
+
+
+def _levenshtein_py(a, b):
+    """the workaround a user would write: plain Python dynamic programming, one row at a time"""
+    row = list(range(len(b) + 1))
+    for i, x in enumerate(a, 1):
+        new = [i]
+        for j, y in enumerate(b, 1):
+            new.append(min(row[j] + 1, new[j - 1] + 1, row[j - 1] + (x != y)))
+        row = new
+    return row[-1]
+
+
+def _host_alternative(eng, X, utt, labels, lab):
+    logits = eng.posteriors(X, raw_logits=True)
+    blank = logits.shape[1] - 1
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    edits, t0 = [], 0
+    for n, r in zip(utt, refs):
+        ks = np.argmax(logits[t0:t0 + n], axis=1)
+        t0 += n
+        h = ks[(ks != blank) & (ks != np.concatenate([[-1], ks[:-1]]))]
+        edits.append(_levenshtein_py(h.tolist(), r.tolist()))
+    return edits
+
+
+FORWARD = ("gemm_f32_nn(fwd affine)", "act_forward", "bn_stats", "gemm_f32_dual(dA+dW)")
+
+
+def decode_leg(eng, X, utt, labels, lab, rng):
+    from tfkaldi_amd import _lib
+    O, K = eng.O, 20
+    lab = np.asarray(lab)
+    W = rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H)
+    eng.set(_lib.WEIGHTS, eng.L, W)  # random output layer: every class wins somewhere
+    for case in ("random output weights", "blank biased to ~reference length"):
+        bias = np.zeros(O, np.float32)
+        if case.startswith("blank"):
+            lo, hi = 0.0, 20.0  # bisect the blank's bias until the mean hypothesis length is the reference length's
+            for _ in range(16):
+                bias[O - 1] = 0.5 * (lo + hi)
+                eng.set(_lib.BIASES, eng.L, bias)
+                hyps, _ = eng.ctc_greedy(X, utt)
+                lo, hi = (bias[O - 1], hi) if np.mean([h.size for h in hyps]) > np.mean(lab) else (lo, bias[O - 1])
+        eng.set(_lib.BIASES, eng.L, bias)
+        hyps, edits = eng.ctc_greedy(X, utt, labels, lab)
+        assert edits.tolist() == _host_alternative(eng, X, utt, labels, lab)  # the two paths agree
+        H = [h.size for h in hyps]
+        print("decode (%s): hypothesis length mean %.1f max %d, references %d, label error rate %.3f"
+              % (case, np.mean(H), max(H), int(np.mean(lab)), edits.sum() / lab.sum()))
+        for name, fn in (("eval forward alone (tfk_posteriors, raw logits to the host)", lambda: eng.posteriors(X, raw_logits=True)),
+                         ("tfk_ctc_greedy without references", lambda: eng.ctc_greedy(X, utt)),
+                         ("tfk_ctc_greedy with references", lambda: eng.ctc_greedy(X, utt, labels, lab))):
+            for _ in range(3):
+                fn()
+            t0 = time.perf_counter()
+            for _ in range(K):
+                fn()
+            print("  %-62s %8.3f ms/call" % (name, (time.perf_counter() - t0) / K * 1e3))
+        t0 = time.perf_counter()
+        _host_alternative(eng, X, utt, labels, lab)
+        print("  %-62s %8.3f ms/call" % ("host alternative (logits, numpy argmax + merge, Python Levenshtein)",
+                                        (time.perf_counter() - t0) * 1e3))
+        eng.profile_begin()
+        for _ in range(K):
+            eng.ctc_greedy(X, utt, labels, lab)
+        stats = {s["name"]: s for s in eng.profile_end()}
+        fwd = sum(stats[n]["total_ms"] for n in FORWARD if n in stats) / K
+        dec = sum(stats[n]["total_ms"] for n in ("ctc_best_path", "edit_distance") if n in stats) / K
+        for s in stats.values():
+            print("    %-28s n=%4d %9.1f us/call" % (s["name"], s["launches"] // K, s["total_ms"] / K * 1e3))
+        print("    eval forward device time %.1f us, decode kernels %.1f us (%.1f %% of the forward)" % (fwd * 1e3, dec * 1e3,
+                                                                                                     100.0 * dec / fwd))
 
 
 if __name__ == "__main__":
