@@ -338,15 +338,17 @@ struct ProfScope {
   tfk_engine* e;
   ProfRec r;
   hipStream_t st;
+  bool live;
   ProfScope(tfk_engine* e_, int family, double flops, double bytes, hipStream_t st_ = nullptr)
-      : e(e_), st(st_ ? st_ : e_->stream) {
-    if (!e->profiling) return;
+      : e(e_), st(st_ ? st_ : e_->stream), live(e_->profiling) {
+    if (!live) return;
     r.family = family; r.flops = flops; r.bytes = bytes;
     r.a = get_event(e); r.b = get_event(e);
     hipEventRecord(r.a, st);
   }
+  void drop() { live = false; }  // nothing was launched: no record (the unused event pair stays in the pool)
   ~ProfScope() {
-    if (!e->profiling) return;
+    if (!live) return;
     hipEventRecord(r.b, st);
     e->prof.push_back(r);
   }
@@ -447,45 +449,54 @@ struct ActEpi {  // EPI_DACT operands: the hidden layer whose output gradient th
   int ld_twin = 0;
   float scale = 1.f;       // EPI_DACT: 1 / keep_prob of a ReLU + dropout chain
 };
+// the epilogue operands GemmArgs and GemmArgsB share (same field names on purpose)
+template <class Args>
+void fill_epilogue(Args& g, const ActEpi* act, float* stats, const int* row_vend) {
+  g.stats = stats;
+  g.stats_stride = kMaxRowSplits;
+  g.act_a = act ? act->a : nullptr; g.act_z = act ? act->z : nullptr;
+  g.act_mean = act ? act->mean : nullptr; g.act_rstd = act ? act->rstd : nullptr;
+  g.act_nonlin = act ? act->nonlin : 0;
+  g.act_beta = act ? act->beta : nullptr; g.bn_eps = act ? act->eps : 0.f;
+  g.act_scale = act ? act->scale : 1.f;
+  g.act_keep = act ? 1.f / act->scale : 1.f;
+  g.row_vend = row_vend;
+}
+// split-K workspace of at least `need` floats, grown in stream order: behind the GEMMs that still use the old one
+int grow_splitk(tfk_engine* e, size_t need, bool zero, hipStream_t st) {
+  if (need <= e->ws_splitk_floats) return 0;
+  dev_free(e, e->ws_splitk, true);
+  e->ws_splitk = nullptr;
+  e->ws_splitk_floats = 0;
+  CHK(dev_alloc(e, (void**)&e->ws_splitk, need * sizeof(float), false));
+  e->ws_splitk_floats = need;
+  if (zero) HIPCHK(hipMemsetAsync(e->ws_splitk, 0, need * sizeof(float), st));
+  return 0;
+}
 int run_gemm(tfk_engine* e, GemmLayout layout, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
              int M, int N, int K, const float* bias, int epi, hipStream_t st = nullptr, float* stats = nullptr,
              int cfg = -1, const ActEpi* act = nullptr, const int* row_vend = nullptr) {
   if (!st) st = e->stream;
+  const int fam = layout == GEMM_NN ? KF_GEMM_NN : layout == GEMM_NT ? KF_GEMM_NT : KF_GEMM_TN;
   if (e->bf16) {
     GemmArgsB b = {};
     int lda8 = 0, ldb8 = 0;
     b.A = twin_of(e, A, &lda8);
     b.B = twin_of(e, B, &ldb8);
     if (!b.A || !b.B) return fail(-1, "internal: GEMM operand without a bf16 twin");
-    b.C = C; b.bias = bias; b.stats = stats;
-    b.act_a = act ? act->a : nullptr; b.act_z = act ? act->z : nullptr;
-    b.act_mean = act ? act->mean : nullptr; b.act_rstd = act ? act->rstd : nullptr;
-    b.act_nonlin = act ? act->nonlin : 0;
-    b.stats_stride = kMaxRowSplits;
-    b.act_beta = act ? act->beta : nullptr; b.bn_eps = act ? act->eps : 0.f;
+    b.C = C; b.bias = bias;
+    fill_epilogue(b, act, stats, row_vend);
     b.C_twin = act ? act->twin : nullptr; b.ldct = act ? act->ld_twin : 0;
     b.ct_x3 = e->x3;
-    b.act_scale = act ? act->scale : 1.f;
-    b.act_keep = act ? 1.f / act->scale : 1.f;
-    b.row_vend = row_vend;
     b.M = M; b.N = N; b.K = K; b.lda = lda8; b.ldb = ldb8; b.ldc = ldc; b.epi = epi;
     if (e->x3) {
       // the split-K form of the 1024-frame contractions (gemm_bf16.h); its flag words start out as zeros and every launch
       // leaves them so.  (The workspace is shared with the fp32 split-K form, which an x3 engine never runs.)
-      const size_t need = gemm_bf16x3_splitk_floats(layout, M, N, K);
-      if (need > e->ws_splitk_floats) {  // stream-ordered: behind the GEMMs that still use the old workspace
-        dev_free(e, e->ws_splitk, true);
-        e->ws_splitk = nullptr;
-        e->ws_splitk_floats = 0;
-        CHK(dev_alloc(e, (void**)&e->ws_splitk, need * sizeof(float), false));
-        e->ws_splitk_floats = need;
-        HIPCHK(hipMemsetAsync(e->ws_splitk, 0, need * sizeof(float), st));
-      }
+      CHK(grow_splitk(e, gemm_bf16x3_splitk_floats(layout, M, N, K), true, st));
       b.splitk_ws = e->ws_splitk;
       b.splitk_ws_floats = e->ws_splitk_floats;
       b.err = reinterpret_cast<unsigned*>(e->h_scalars_dev + kErrWord);
     }
-    const int fam = layout == GEMM_NN ? KF_GEMM_NN : layout == GEMM_NT ? KF_GEMM_NT : KF_GEMM_TN;
     ProfScope ps(e, fam, 2.0 * M * N * K,
                  (e->x3 ? 6.0 : 2.0) * ((double)M * K + (double)K * N) + 4.0 * (double)M * N * ((epi & EPI_ACCUM) ? 2 : 1), st);
     const int rc = e->x3 ? gemm_bf16x3(layout, b, st) : gemm_bf16(layout, b, st);
@@ -493,30 +504,15 @@ int run_gemm(tfk_engine* e, GemmLayout layout, const float* A, int lda, const fl
     return 0;
   }
   GemmArgs g;
-  g.A = A; g.B = B; g.C = C; g.bias = bias; g.stats = stats;
-  g.act_a = act ? act->a : nullptr; g.act_z = act ? act->z : nullptr;
-  g.act_mean = act ? act->mean : nullptr; g.act_rstd = act ? act->rstd : nullptr;
-  g.act_nonlin = act ? act->nonlin : 0;
-  g.stats_stride = kMaxRowSplits;
-  g.act_beta = act ? act->beta : nullptr; g.bn_eps = act ? act->eps : 0.f;
-  g.act_scale = act ? act->scale : 1.f;
-  g.act_keep = act ? 1.f / act->scale : 1.f;
-  g.row_vend = row_vend;
+  g.A = A; g.B = B; g.C = C; g.bias = bias;
+  fill_epilogue(g, act, stats, row_vend);
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.epi = epi;
   if (layout == GEMM_TN && K >= gemm_f32_splitk_min_k() && (size_t)M * N < ((size_t)1 << 20)) {
     // narrow layer, many frames: the weight gradient may run split-K (gemm_f32.h) -- partials of up to 32 chunks
-    const size_t need = (size_t)32 * M * ldc;
-    if (need > e->ws_splitk_floats) {  // stream-ordered: behind the GEMMs that still read the old workspace
-      dev_free(e, e->ws_splitk, true);
-      e->ws_splitk = nullptr;
-      e->ws_splitk_floats = 0;
-      CHK(dev_alloc(e, (void**)&e->ws_splitk, need * sizeof(float), false));
-      e->ws_splitk_floats = need;
-    }
+    CHK(grow_splitk(e, (size_t)32 * M * ldc, false, st));
     g.splitk_ws = e->ws_splitk;
     g.splitk_ws_floats = e->ws_splitk_floats;
   }
-  const int fam = layout == GEMM_NN ? KF_GEMM_NN : layout == GEMM_NT ? KF_GEMM_NT : KF_GEMM_TN;
   ProfScope ps(e, fam, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N * ((epi & EPI_ACCUM) ? 2 : 1)), st);
   const int rc = gemm_f32(layout, g, cfg, st);
   if (rc != 0) return fail(rc, "gemm_f32 launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -530,6 +526,7 @@ int run_gemm_dual(tfk_engine* e, const float* dz, int ld_dz, const float* W, int
                   int d_in, int d_out, int epi_w, int* chunk_rows) {
   if (!e->dual_gemm) return 1;
   const double flops = 2.0 * T * N_da * K_da + 2.0 * d_in * d_out * T;
+  const double out_w = (double)d_in * d_out * ((epi_w & EPI_ACCUM) ? 2 : 1);
   if (e->bf16) {
     const int dcfg = e->x3 ? -1 : gemm_bf16_dual_config(T, N_da, d_in, d_out);
     const int bm = e->x3 ? kGemmBf16x3TileRows : gemm_bf16_dual_tile_rows(dcfg);
@@ -541,66 +538,33 @@ int run_gemm_dual(tfk_engine* e, const float* dz, int ld_dz, const float* W, int
     w.A = twin_of(e, in, &ld_c);
     w.B = twin_of(e, dz, &ld_d);
     if (!a.A || !a.B || !w.A || !w.B) return fail(-1, "internal: GEMM operand without a bf16 twin");
-    a.C = da_out; a.stats = stats;
-    a.act_a = act ? act->a : nullptr; a.act_z = act ? act->z : nullptr;
-    a.act_mean = act ? act->mean : nullptr; a.act_rstd = act ? act->rstd : nullptr;
-    a.act_nonlin = act ? act->nonlin : 0;
-    a.act_scale = act ? act->scale : 1.f;
-    a.act_keep = act ? 1.f / act->scale : 1.f;
-    a.act_beta = act ? act->beta : nullptr;
-    a.stats_stride = kMaxRowSplits;
+    a.C = da_out;
+    fill_epilogue(a, act, stats, nullptr);
     a.M = T; a.N = N_da; a.K = K_da; a.lda = ld_a; a.ldb = ld_b; a.ldc = ld_da; a.epi = act ? EPI_DACT : 0;
     w.C = Gw;
     w.M = d_in; w.N = d_out; w.K = T; w.lda = ld_c; w.ldb = ld_d; w.ldc = ld_g; w.epi = epi_w;
     const double ob = e->x3 ? 6.0 : 2.0;  // operand bytes per element: one bf16 value, or three planes
-    const double bytes = ob * ((double)T * K_da + (double)K_da * N_da) + 4.0 * (double)T * N_da +
-                         ob * ((double)T * d_in + (double)T * d_out) + 4.0 * (double)d_in * d_out * ((epi_w & EPI_ACCUM) ? 2 : 1);
-    hipEvent_t pa = nullptr, pb = nullptr;
-    if (e->profiling) {
-      pa = get_event(e); pb = get_event(e);
-      hipEventRecord(pa, e->stream);
-    }
+    ProfScope ps(e, KF_GEMM_DUAL, flops, ob * ((double)T * K_da + (double)K_da * N_da) + 4.0 * (double)T * N_da +
+                                             ob * ((double)T * d_in + (double)T * d_out) + 4.0 * out_w);
     const int rc = e->x3 ? gemm_bf16x3_dual(a, w, e->stream) : gemm_bf16_dual(a, w, e->stream);
+    if (rc != 0) ps.drop();
     if (rc == -1) return 1;
     if (rc != 0) return fail(rc, "gemm_bf16%s_dual launch failed: %s", e->x3 ? "x3" : "", hipGetErrorString((hipError_t)rc));
-    if (e->profiling) {
-      hipEventRecord(pb, e->stream);
-      ProfRec r;
-      r.family = KF_GEMM_DUAL; r.flops = flops; r.bytes = bytes; r.a = pa; r.b = pb;
-      e->prof.push_back(r);
-    }
     if (chunk_rows) *chunk_rows = bm;
     return 0;
   }
-  GemmArgs a, w;
-  a.A = dz; a.B = W; a.C = da_out; a.bias = nullptr; a.stats = stats;
-  a.act_a = act ? act->a : nullptr; a.act_z = act ? act->z : nullptr;
-  a.act_mean = act ? act->mean : nullptr; a.act_rstd = act ? act->rstd : nullptr;
-  a.act_nonlin = act ? act->nonlin : 0;
-  a.act_scale = act ? act->scale : 1.f;
-  a.act_keep = act ? 1.f / act->scale : 1.f;
-  a.act_beta = act ? act->beta : nullptr;
-  a.stats_stride = kMaxRowSplits;
+  GemmArgs a, w = {};  // (w: no epilogue operands, stats_stride 0)
+  a.A = dz; a.B = W; a.C = da_out; a.bias = nullptr;
+  fill_epilogue(a, act, stats, nullptr);
   a.M = T; a.N = N_da; a.K = K_da; a.lda = ld_dz; a.ldb = ldw; a.ldc = ld_da; a.epi = act ? EPI_DACT : 0;
-  w.A = in; w.B = dz; w.C = Gw; w.bias = nullptr; w.stats = nullptr;
-  w.act_a = w.act_z = w.act_mean = w.act_rstd = nullptr; w.act_nonlin = 0; w.stats_stride = 0;
+  w.A = in; w.B = dz; w.C = Gw;
   w.M = d_in; w.N = d_out; w.K = T; w.lda = ld_in; w.ldb = ld_dz; w.ldc = ld_g; w.epi = epi_w;
-  const double bytes = 4.0 * ((double)T * K_da + (double)K_da * N_da + (double)T * N_da) +
-                       4.0 * ((double)T * d_in + (double)T * d_out + (double)d_in * d_out * ((epi_w & EPI_ACCUM) ? 2 : 1));
-  hipEvent_t pa = nullptr, pb = nullptr;
-  if (e->profiling) {
-    pa = get_event(e); pb = get_event(e);
-    hipEventRecord(pa, e->stream);
-  }
+  ProfScope ps(e, KF_GEMM_DUAL, flops, 4.0 * ((double)T * K_da + (double)K_da * N_da + (double)T * N_da) +
+                                           4.0 * ((double)T * d_in + (double)T * d_out + out_w));
   const int rc = gemm_f32_dual(a, w, e->stream);
-  if (rc == -1) return 1;  // (an unused event pair stays in the pool)
+  if (rc != 0) ps.drop();
+  if (rc == -1) return 1;
   if (rc != 0) return fail(rc, "gemm_f32_dual launch failed: %s", hipGetErrorString((hipError_t)rc));
-  if (e->profiling) {
-    hipEventRecord(pb, e->stream);
-    ProfRec r;
-    r.family = KF_GEMM_DUAL; r.flops = flops; r.bytes = bytes; r.a = pa; r.b = pb;
-    e->prof.push_back(r);
-  }
   return 0;
 }
 
@@ -728,6 +692,8 @@ struct Stack {
   int T_pad = 0, T_valid = 0;
   const int* d_vend = nullptr;  // device: row_vend table of the pass
 };
+// segments start at multiples of the tallest GEMM tile of the arithmetic (fp32: 128, bf16: 256 rows)
+int stack_align(const tfk_engine* e) { return (e->bf16 && !e->x3) ? 256 : 128; }
 
 // Bring one micro-batch to HBM (or adopt device pointers).  Returns the GEMM-ready X (ld in *ldx_out).
 int wait_slot_free(tfk_engine* e, int s);  // (below, next to finish_slot)
@@ -917,7 +883,9 @@ ActDesc act_desc(const tfk_engine* e, int layer, int train, uint32_t call) {
 
 // Forward through `nfw` hidden layers; logits from the output of hidden layer `nact - 1`
 // (dnn.py:73-108; the tf.case of dnn.py:97-102 is the choice of nact).
-int forward(tfk_engine* e, const float* Xd, int ldx, int T, int train, int nact, int nfw, uint32_t call) {
+// `st` (stacked pass, struct Stack above): T = st->T_pad rows, segment i runs as call `call + i`.
+int forward(tfk_engine* e, const float* Xd, int ldx, int T, int train, int nact, int nfw, uint32_t call,
+            const Stack* st = nullptr) {
   const float* in = Xd;
   int ld_in = ldx;
   const int H = e->H, ldH = e->ldH;
@@ -936,12 +904,24 @@ int forward(tfk_engine* e, const float* Xd, int ldx, int T, int train, int nact,
       // and applies BN + nonlinearity + dropout (4 kernels per layer -> 2)
       int cfg;
       const int chunk = gemm_chunk_rows(e, GEMM_NN, T, H, y.d_in, &cfg);
+      if (st && stack_align(e) % chunk) return fail(-1, "internal: GEMM tile of %d rows does not divide the stack alignment", chunk);
       CHK(run_gemm(e, GEMM_NN, in, ld_in, e->p_param() + y.w_off, y.ld_out, e->z[l], ldH, T, H, y.d_in,
-                   e->p_param() + y.b_off, EPI_BIAS | EPI_COLSTATS, nullptr, e->ws_stats, cfg));
-      {
+                   e->p_param() + y.b_off, EPI_BIAS | EPI_COLSTATS, nullptr, e->ws_stats, cfg, nullptr, st ? st->d_vend : nullptr));
+      const int nchunk = (T + chunk - 1) / chunk;
+      if (st) {
+        for (int i = 0; i < st->k; ++i) {  // statistics, moving averages (in segment order) and the activation chain per segment
+          ProfScope ps(e, KF_ACT_FWD, 0, 8.0 * st->rows[i] * H);
+          const ActDesc d = act_desc(e, l, train, call + (uint32_t)i);
+          Twin tw = twin_a(l);
+          if (e->bf16) tw.p += e->tw_row((size_t)st->r0[i], e->ldHb);
+          bn_act_forward(e->stream, d, e->z[l] + (size_t)st->r0[i] * ldH, e->a[l] + (size_t)st->r0[i] * ldH,
+                         e->ws_stats + (size_t)(st->r0[i] / chunk) * ldH, chunk, st->rows[i], H, ldH, e->bn_eps, e->bn_decay,
+                         e->seg_mean[l] + (size_t)i * ldH, e->seg_rstd[l] + (size_t)i * ldH, e->ema_mean(l), e->ema_var(l),
+                         e->p_param() + y.beta_off, tw, st->span[i], nchunk);
+        }
+      } else {
         ProfScope ps(e, KF_ACT_FWD, 0, 8.0 * T * H);
         const ActDesc d = act_desc(e, l, train, call);
-        const int nchunk = (T + chunk - 1) / chunk;
         if (nchunk > kMergeOnceChunks && nchunk <= kMaxRowSplits) {
           // tall micro-batch: the statistics are merged once, the row-wise kernel applies them
           bn_stats_from_chunks(e->stream, e->ws_stats, chunk, T, H, ldH, e->bn_eps, e->bn_decay, e->mean[l], e->rstd[l],
@@ -1001,7 +981,8 @@ int forward(tfk_engine* e, const float* Xd, int ldx, int T, int train, int nact,
   return 0;
 }
 
-int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t call, bool fire) {
+// `st` (stacked pass): T = st->T_pad rows, batch-norm backward runs per segment (segment i as call `call + i`).
+int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t call, bool fire, const Stack* st = nullptr) {
   const int L = e->L, H = e->H, ldH = e->ldH;
   const LayerLayout& o = e->lay[L];
   float* G = e->p_grad();
@@ -1016,7 +997,6 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
     }
   // output layer: dZ = softmax - onehot sits in `logits`
   // (when eligible the output layer's dW runs in one launch with the dA that follows: see below)
-  bool out_dw_done = false;
   FinalBatch fin;
   fin.n = 0;
   fin.accumulate = acc;
@@ -1025,7 +1005,7 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
   {
     if (!e->colsum_done) {  // (CTC: the loss has a reduction of its own)
       ProfScope ps(e, KF_COLSUM, 0, 4.0 * T * e->O);
-      colsum_partial(e->stream, e->logits, T, e->ldO, ws_of(L));
+      colsum_partial(e->stream, e->logits, T, e->ldO, ws_of(L));  // (stacked: padding rows of dLogits are zero)
     }
     e->colsum_done = false;
     fin.it[fin.n++] = {ws_of(L), G + o.b_off, 0, rs, e->O, e->ldO};
@@ -1036,39 +1016,40 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
   // over [T, H] per layer.  The per-tile partial sums must fit the kMaxRowSplits chunk slots of the workspace.
   int cfg_h, cfg_o;
   const int rows_h = gemm_chunk_rows(e, GEMM_NT, T, H, H, &cfg_h), rows_o = gemm_chunk_rows(e, GEMM_NT, T, H, e->O, &cfg_o);
-  const int chunks_h = (T + rows_h - 1) / rows_h, chunks_o = (T + rows_o - 1) / rows_o;
   // Dropout behind a ReLU fuses as well: a = relu(u) * mask / keep, so d a / d u = (a > 0) / keep exactly -- the
   // epilogue reads it off the stored layer output without regenerating the mask.  (Behind sigmoid / tanh the kept
   // value would have to be un-scaled first; those chains keep the separate pass.)
   const bool drop = e->cfg.keep_prob < 1.f;
-  const float dscale = drop ? 1.f / e->cfg.keep_prob : 1.f;
   const bool fuse_hb = e->cfg.batch_norm && !e->cfg.l2_norm && (!drop || e->cfg.nonlin == TFK_NONLIN_RELU) &&
-                       e->fuse_hb_enabled && chunks_h <= kMaxRowSplits && chunks_o <= kMaxRowSplits;
-  int chunks_first = chunks_o;  // row chunks of the EPI_DACT partial sums of the GEMM that produced the current `da`
+                       e->fuse_hb_enabled && (T + rows_h - 1) / rows_h <= kMaxRowSplits &&
+                       (T + rows_o - 1) / rows_o <= kMaxRowSplits;
+  // the EPI_DACT operands of hidden layer l, whose output gradient a GEMM produces.  (Stacked pass: ReLU chains take the
+  // normalised pre-activation from the layer output (a * keep - beta): the epilogue needs no per-segment mean / rstd.)
+  const std::vector<float*>& mean = st ? e->seg_mean : e->mean;
+  const std::vector<float*>& rstd = st ? e->seg_rstd : e->rstd;
+  auto act_of = [&](int l) {
+    ActEpi act = {e->a[l], e->z[l], mean[l], rstd[l], e->cfg.nonlin};
+    act.scale = drop ? 1.f / e->cfg.keep_prob : 1.f;
+    act.beta = e->cfg.batch_norm ? e->p_param() + e->lay[l].beta_off : nullptr;
+    return act;
+  };
+  // the output gradient of hidden layer `target` as a launch of its own (the dual launch declined)
   auto dact_gemm = [&](const float* dz, int ld_dz, const float* W, int ldw, float* out, int K, int target, int cfg) {
     if (!fuse_hb) return run_gemm(e, GEMM_NT, dz, ld_dz, W, ldw, out, ldH, T, H, K, nullptr, 0);
-    ActEpi act = {e->a[target], e->z[target], e->mean[target], e->rstd[target], e->cfg.nonlin};
-    act.scale = dscale;
-    act.beta = e->p_param() + e->lay[target].beta_off;
-    return run_gemm(e, GEMM_NT, dz, ld_dz, W, ldw, out, ldH, T, H, K, nullptr, EPI_DACT, nullptr, ws_of(target), cfg,
-                    &act);
+    const ActEpi act = act_of(target);
+    return run_gemm(e, GEMM_NT, dz, ld_dz, W, ldw, out, ldH, T, H, K, nullptr, EPI_DACT, nullptr, ws_of(target), cfg, &act);
   };
+  int bm_in = rows_o;  // rows per chunk of the EPI_DACT partial sums of the GEMM that produced the current `da`
   {
-    ActEpi act = {e->a[nact - 1], e->z[nact - 1], e->mean[nact - 1], e->rstd[nact - 1], e->cfg.nonlin};
-    act.scale = dscale;
-    act.beta = e->cfg.batch_norm ? e->p_param() + e->lay[nact - 1].beta_off : nullptr;
-    int bm = rows_o;
+    const ActEpi act = act_of(nact - 1);
     const int rc = run_gemm_dual(e, e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], ldH, T, H, e->O,
                                  fuse_hb ? &act : nullptr, fuse_hb ? ws_of(nact - 1) : nullptr, e->a[nact - 1], ldH,
-                                 G + o.w_off, o.ld_out, H, e->O, epi_w, &bm);
+                                 G + o.w_off, o.ld_out, H, e->O, epi_w, &bm_in);
     if (rc < 0) return rc;
-    out_dw_done = rc == 0;
-    if (out_dw_done) chunks_first = (T + bm - 1) / bm;
-  }
-  if (!out_dw_done) {
-    CHK(run_gemm(e, GEMM_TN, e->a[nact - 1], ldH, e->logits, e->ldO, G + o.w_off, o.ld_out, H, e->O, T, nullptr,
-                 epi_w));
-    CHK(dact_gemm(e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], e->O, nact - 1, cfg_o));
+    if (rc > 0) {
+      CHK(run_gemm(e, GEMM_TN, e->a[nact - 1], ldH, e->logits, e->ldO, G + o.w_off, o.ld_out, H, e->O, T, nullptr, epi_w));
+      CHK(dact_gemm(e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], e->O, nact - 1, cfg_o));
+    }
   }
   if (fire && e->cb) {
     e->cb(e->cb_user, 0);  // the output layer's weight gradient is enqueued
@@ -1077,56 +1058,72 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
     // whatever the active depth is: a rank without micro-batches replays exactly that order (dataparallel.py).
     for (int l = L - 1; l >= nact; --l) e->cb(e->cb_user, L - l);
   }
-  int chunks_in = chunks_first;
   for (int l = nact - 1; l >= 0; --l) {
     const LayerLayout& y = e->lay[l];
     float* da = e->dA[pp];
-    const ActDesc d = act_desc(e, l, 1, call);
-    int pre_du = fuse_hb ? 1 : 0;
-    if (e->cfg.l2_norm) {
-      ProfScope ps(e, KF_HIDDEN_BWD, 0, 12.0 * T * H);
-      act_backward_rows(e->stream, d, da, e->v[l], e->rowscale[l], T, H, ldH);
-      pre_du = 1;
-    }
-    {
+    const int chunks_in = (T + bm_in - 1) / bm_in;
+    // the layer's d beta / d bias items: `n_beta` chunks in slab 0, `n_bias` in slab 2
+    auto fin_layer = [&](int n_beta, int n_bias) {
+      if (e->cfg.batch_norm) fin.it[fin.n++] = {ws_of(l), G + y.beta_off, 0, n_beta, H, ldH};
+      fin.it[fin.n++] = {ws_of(l), G + y.b_off, 2, n_bias, H, ldH};
+      if (fin.n + 2 > kMaxFinalItems) {  // very deep nets: flush
+        grad_final(e->stream, fin);
+        fin.n = 0;
+      }
+    };
+    Twin tw;
+    if (e->bf16) { tw.p = e->dAb[pp]; tw.ld = e->ldHb; tw.x3 = e->x3; }
+    if (st) {
+      if (!fuse_hb || stack_align(e) % bm_in || chunks_in > kMaxRowSplits)
+        return fail(-1, "internal: EPI_DACT chunks of %d rows do not fit a stacked pass of %d rows", bm_in, T);
+      int slot = 0;
+      for (int i = 0; i < st->k; ++i) {  // BN backward per segment: its own column means, its own row count
+        ProfScope ps(e, KF_HIDDEN_BWD, 0, 28.0 * st->rows[i] * H);
+        const ActDesc d = act_desc(e, l, 1, call + (uint32_t)i);
+        Twin tws = tw;
+        if (e->bf16) tws.p += e->tw_row((size_t)st->r0[i], e->ldHb);
+        const size_t r = (size_t)st->r0[i] * ldH;
+        hidden_backward(e->stream, d, 1, da + r, e->a[l] + r, e->z[l] + r, mean[l] + (size_t)i * ldH, rstd[l] + (size_t)i * ldH,
+                        st->rows[i], H, ldH, ws_of(l) + (size_t)(st->r0[i] / bm_in) * ldH, (st->rows[i] + bm_in - 1) / bm_in, tws,
+                        st->span[i], ws_of(l) + ((size_t)2 * kMaxRowSplits + slot) * ldH);
+        slot += row_splits(st->span[i]);
+      }
+      if (slot > kMaxRowSplits) return fail(-1, "internal: %d partial-sum slots in a stacked pass", slot);
+      // d beta = sum of du over ALL rows (the chunks of every segment; padding chunks hold zeros), d bias = sum of dz
+      fin_layer(chunks_in, slot);
+    } else {
+      const ActDesc d = act_desc(e, l, 1, call);
+      int pre_du = fuse_hb ? 1 : 0;
+      if (e->cfg.l2_norm) {
+        ProfScope ps(e, KF_HIDDEN_BWD, 0, 12.0 * T * H);
+        act_backward_rows(e->stream, d, da, e->v[l], e->rowscale[l], T, H, ldH);
+        pre_du = 1;
+      }
       ProfScope ps(e, KF_HIDDEN_BWD, 0, (e->cfg.batch_norm ? 28.0 : 12.0) * T * H);
-      Twin tw;
-      if (e->bf16) { tw.p = e->dAb[pp]; tw.ld = e->ldHb; tw.x3 = e->x3; }
       int chunks_eff = fuse_hb ? chunks_in : 0;
       if (chunks_eff > kMergeOnceChunks) {  // tall micro-batch: reduce the EPI_DACT partial sums once
         chunk_totals(e->stream, ws_of(l), chunks_eff, ldH);
         chunks_eff = 1;
       }
-      hidden_backward(e->stream, d, pre_du, da, e->a[l], e->z[l], e->mean[l], e->rstd[l], T, H, ldH, ws_of(l),
-                      chunks_eff, tw);
-      if (e->cfg.batch_norm) fin.it[fin.n++] = {ws_of(l), G + y.beta_off, 0, fuse_hb ? chunks_eff : rs, H, ldH};
-      fin.it[fin.n++] = {ws_of(l), G + y.b_off, 2, rs, H, ldH};
-      if (fin.n + 2 > kMaxFinalItems) {  // very deep nets: flush
-        grad_final(e->stream, fin);
-        fin.n = 0;
-      }
+      hidden_backward(e->stream, d, pre_du, da, e->a[l], e->z[l], mean[l], rstd[l], T, H, ldH, ws_of(l), chunks_eff, tw);
+      fin_layer(fuse_hb ? chunks_eff : rs, rs);
     }
     const float* in = l == 0 ? Xd : e->a[l - 1];
     const int ld_in = l == 0 ? ldx : ldH;
     bool fused = false;
-    int chunks_next = chunks_h;
+    bm_in = rows_h;
     if (l > 0) {  // dW_l and the dA that feeds layer l - 1 both read dz_l: one launch when eligible
-      ActEpi act = {e->a[l - 1], e->z[l - 1], e->mean[l - 1], e->rstd[l - 1], e->cfg.nonlin};
-      act.scale = dscale;
-      act.beta = e->cfg.batch_norm ? e->p_param() + e->lay[l - 1].beta_off : nullptr;
-      int bm = rows_h;
+      const ActEpi act = act_of(l - 1);
       const int rc = run_gemm_dual(e, da, ldH, e->p_param() + y.w_off, y.ld_out, e->dA[pp ^ 1], ldH, T, H, H,
                                    fuse_hb ? &act : nullptr, fuse_hb ? ws_of(l - 1) : nullptr, in, ld_in, G + y.w_off,
-                                   y.ld_out, y.d_in, H, epi_w, &bm);
+                                   y.ld_out, y.d_in, H, epi_w, &bm_in);
       if (rc < 0) return rc;
       fused = rc == 0;
-      chunks_next = (T + bm - 1) / bm;
     }
     if (!fused) {
       CHK(run_gemm(e, GEMM_TN, in, ld_in, da, ldH, G + y.w_off, y.ld_out, y.d_in, H, T, nullptr, epi_w));
       if (l > 0) CHK(dact_gemm(da, ldH, e->p_param() + y.w_off, y.ld_out, e->dA[pp ^ 1], H, l - 1, cfg_h));
     }
-    if (l > 0) chunks_in = fused ? chunks_next : chunks_h;
     if (fire && e->cb) e->cb(e->cb_user, L - l);
     pp ^= 1;
   }
@@ -1456,75 +1453,6 @@ struct RawSpec {  // non-null utt_len selects the device-side splice
   int U, context;
   const float* cmvn;  // nullable [U, 2, raw_dim]
 };
-int train_or_eval(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int32_t T, int flags, int train,
-                  const RawSpec* raw = nullptr, const CtcSpec* ctc = nullptr) {
-  if (!e) return fail(-1, "engine is NULL");
-  if (T <= 0) return fail(-1, "empty micro-batch (T = %d)", T);
-  if (!X || (!y && !ctc)) return fail(-1, "X / y is NULL");
-  if (raw && (flags & TFK_DEVICE_PTRS)) return fail(-1, "the raw entry points take host pointers (TFK_RAW_DEVICE: raw alone on the device)");
-  if (!raw && (flags & TFK_RAW_DEVICE)) return fail(-1, "TFK_RAW_DEVICE belongs to the *_raw entry points");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  // (a call that failed between the fused loss / column-sum launch and its backward pass must not leave the flag behind for a
-  // later micro-batch -- a CTC one has no fused column sums: round-5 advisor finding)
-  e->colsum_done = false;
-  CHK(reserve(e, T));
-  const float* Xd; const int32_t* yd; int ld;
-  const int slot_before = e->slot;
-  if (raw) CHK(stage_raw(e, X, ldx, y, T, raw->utt_len, raw->U, raw->context, raw->cmvn, &Xd, &ld, &yd, (flags & TFK_RAW_DEVICE) != 0));
-  else CHK(stage_input(e, X, ldx, y, T, flags, &Xd, &ld, &yd));
-  if (e->bf16) CHK(twin_input(e, &Xd, &ld, T));
-  const uint32_t call = e->call_counter++;
-  const int nact = e->nact();
-  // train mode evaluates every hidden layer when BN is on: the UPDATE_OPS of all batch-norm layers are
-  // fetched by update_gradients_op (trainer.py:164-169) even for layers the tf.case does not select.
-  const int nfw = (train && e->cfg.layerwise_init && e->cfg.batch_norm) ? e->L : nact;
-  CHK(forward(e, Xd, ld, T, train, nact, nfw, call));
-  if (ctc) {
-    CHK(ctc_loss(e, *ctc, T, train));
-  } else {
-    {
-      ProfScope ps(e, KF_SOFTMAX_XENT, 0, (train ? 8.0 : 4.0) * T * e->O);
-      Twin tw;
-      if (e->bf16 && train) { tw.p = e->logb; tw.ld = e->ldOb; tw.x3 = e->x3; }
-      softmax_xent(e->stream, e->logits, yd, T, e->O, e->ldO, e->row_loss, train, tw);
-    }
-    {
-      // (folding this sum into softmax_xent -- the block that finishes last adds up the frames' losses -- was measured in
-      // round 3 and is SLOWER than the second launch: 21.4 vs 9.3 + 6.3 us at cfg2, profiles/r03_fusion_experiments.txt)
-      // training: ONE launch with the column sums of dLogits the backward pass starts with (kernels.hip: colsum_loss_kernel)
-      ProfScope ps(e, train ? KF_COLSUM : KF_LOSS_REDUCE, 0, train ? 4.0 * T * e->O : 4.0 * T);
-      if (train) {
-        colsum_loss(e->stream, e->logits, T, e->ldO, e->ws_bwd + (size_t)e->L * e->ws_bwd_stride, e->row_loss, T, e->p_scalars(),
-                    e->scalars_fresh);
-        e->colsum_done = true;
-      } else {
-        loss_reduce(e->stream, e->row_loss, T, e->p_scalars(), e->scalars_fresh);
-      }
-      e->scalars_fresh = false;
-    }
-  }
-  if (train) {
-    const bool fire = (flags & TFK_LAST_MICROBATCH) != 0;
-    if (fire) {
-      // loss, frame count and the BN moving-average increments of the step are final once the last micro-batch's
-      // forward + loss have run: their (tiny) bucket is announced FIRST, so that its all-reduce is long done when
-      // the optimiser needs the frame count
-      if (e->cfg.batch_norm && e->later_mb > 0) {
-        ProfScope ps(e, KF_MISC, 0, 8.0 * e->E);
-        scale_inplace(e->stream, e->p_ema(), e->E, (float)pow((double)e->bn_decay, (double)e->later_mb));
-      }
-      if (e->cb) e->cb(e->cb_user, e->L + 2);
-    }
-    CHK(backward(e, Xd, ld, T, nact, call, fire));
-    if (fire && e->cb) e->cb(e->cb_user, e->L + 1);  // bias / beta gradients: finalised by backward's last kernel
-    e->grads_fresh = false;
-  }
-  HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, slot_before));
-  e->last_T = T; e->last_nfw = nfw; e->last_call = call; e->last_in = Xd;
-  return 0;
-}
-
 
 // ================= stacked passes (struct Stack above) =================
 
@@ -1534,8 +1462,6 @@ bool stack_eligible(const tfk_engine* e) {
   return e->cfg.batch_norm && !e->cfg.l2_norm && e->cfg.nonlin == TFK_NONLIN_RELU && !e->cfg.layerwise_init &&
          e->fuse_hb_enabled && e->stack_enabled;
 }
-// segments start at multiples of the tallest GEMM tile of the arithmetic (fp32: 128, bf16: 256 rows)
-int stack_align(const tfk_engine* e) { return (e->bf16 && !e->x3) ? 256 : 128; }
 // rows of a stacked pass are bounded by the chunk slots of the backward workspaces: one slab-2 slot per row split (32 rows)
 // of every segment, kMaxRowSplits in all
 constexpr int kMaxStackRows = 8192;
@@ -1549,150 +1475,6 @@ int seg_stats(tfk_engine* e) {
   for (int l = 0; l < e->L; ++l)
     if (alloc_zero(&e->seg_mean[l], (size_t)kMaxStack * e->ldH) || alloc_zero(&e->seg_rstd[l], (size_t)kMaxStack * e->ldH))
       return -1;
-  return 0;
-}
-
-int forward_stacked(tfk_engine* e, const float* Xd, int ldx, const Stack& st, uint32_t call0) {
-  const int H = e->H, ldH = e->ldH, T = st.T_pad;
-  const float* in = Xd;
-  int ld_in = ldx;
-  if (e->bf16 && e->shadow_dirty) {
-    need_params(e, -1);
-    CHK(join_optimizer(e));
-    CHK(refresh_shadow(e));
-  }
-  for (int l = 0; l < e->L; ++l) {
-    const LayerLayout& y = e->lay[l];
-    need_params(e, l);
-    CHK(wait_layer_update(e, l, l == 0));
-    int cfg;
-    const int chunk = gemm_chunk_rows(e, GEMM_NN, T, H, y.d_in, &cfg);
-    if (stack_align(e) % chunk) return fail(-1, "internal: GEMM tile of %d rows does not divide the stack alignment", chunk);
-    CHK(run_gemm(e, GEMM_NN, in, ld_in, e->p_param() + y.w_off, y.ld_out, e->z[l], ldH, T, H, y.d_in,
-                 e->p_param() + y.b_off, EPI_BIAS | EPI_COLSTATS, nullptr, e->ws_stats, cfg, nullptr, st.d_vend));
-    const int tiles = (T + chunk - 1) / chunk;
-    for (int i = 0; i < st.k; ++i) {  // statistics, moving averages (in segment order) and the activation chain per segment
-      ProfScope ps(e, KF_ACT_FWD, 0, 8.0 * st.rows[i] * H);
-      const ActDesc d = act_desc(e, l, 1, call0 + (uint32_t)i);
-      Twin tw;
-      if (e->bf16) { tw.p = e->ab[l] + e->tw_row((size_t)st.r0[i], e->ldHb); tw.ld = e->ldHb; tw.x3 = e->x3; }
-      bn_act_forward(e->stream, d, e->z[l] + (size_t)st.r0[i] * ldH, e->a[l] + (size_t)st.r0[i] * ldH,
-                     e->ws_stats + (size_t)(st.r0[i] / chunk) * ldH, chunk, st.rows[i], H, ldH, e->bn_eps, e->bn_decay,
-                     e->seg_mean[l] + (size_t)i * ldH, e->seg_rstd[l] + (size_t)i * ldH, e->ema_mean(l), e->ema_var(l),
-                     e->p_param() + y.beta_off, tw, st.span[i], tiles);
-    }
-    in = e->a[l];
-    ld_in = ldH;
-  }
-  const LayerLayout& o = e->lay[e->L];
-  need_params(e, e->L);
-  CHK(wait_layer_update(e, e->L, false));
-  CHK(run_gemm(e, GEMM_NN, e->a[e->L - 1], ldH, e->p_param() + o.w_off, o.ld_out, e->logits, e->ldO, T, e->O, H,
-               e->p_param() + o.b_off, EPI_BIAS));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int backward_stacked(tfk_engine* e, const float* Xd, int ldx, const Stack& st, uint32_t call0, bool fire) {
-  const int L = e->L, H = e->H, ldH = e->ldH, T = st.T_pad;
-  const LayerLayout& o = e->lay[L];
-  float* G = e->p_grad();
-  const int acc = e->grads_fresh ? 0 : 1;
-  const int epi_w = acc ? EPI_ACCUM : 0;
-  FinalBatch fin;
-  fin.n = 0;
-  fin.accumulate = acc;
-  auto ws_of = [&](int l) { return e->ws_bwd + (size_t)l * e->ws_bwd_stride; };
-  {
-    if (!e->colsum_done) {
-      ProfScope ps(e, KF_COLSUM, 0, 4.0 * T * e->O);
-      colsum_partial(e->stream, e->logits, T, e->ldO, ws_of(L));  // (padding rows of dLogits are zero)
-    }
-    e->colsum_done = false;
-    fin.it[fin.n++] = {ws_of(L), G + o.b_off, 0, row_splits(T), e->O, e->ldO};
-  }
-  int cfg_h, cfg_o;
-  const int rows_h = gemm_chunk_rows(e, GEMM_NT, T, H, H, &cfg_h), rows_o = gemm_chunk_rows(e, GEMM_NT, T, H, e->O, &cfg_o);
-  const float dscale = e->cfg.keep_prob < 1.f ? 1.f / e->cfg.keep_prob : 1.f;
-  // the EPI_DACT operands of the layer whose output gradient a GEMM produces.  ReLU chains take the normalised
-  // pre-activation from the layer output (a * keep - beta): the epilogue needs no per-segment mean / rstd.
-  auto act_of = [&](int l) {
-    ActEpi act = {e->a[l], e->z[l], e->seg_mean[l], e->seg_rstd[l], e->cfg.nonlin};
-    act.scale = dscale;
-    act.beta = e->p_param() + e->lay[l].beta_off;
-    return act;
-  };
-  int pp = 0;
-  int bm_in = rows_o;  // rows per chunk of the EPI_DACT partial sums of the GEMM that produced the current `da`
-  {
-    ActEpi act = act_of(L - 1);
-    int bm = rows_o;
-    const int rc = run_gemm_dual(e, e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], ldH, T, H, e->O, &act,
-                                 ws_of(L - 1), e->a[L - 1], ldH, G + o.w_off, o.ld_out, H, e->O, epi_w, &bm);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      bm_in = bm;
-    } else {
-      CHK(run_gemm(e, GEMM_TN, e->a[L - 1], ldH, e->logits, e->ldO, G + o.w_off, o.ld_out, H, e->O, T, nullptr, epi_w));
-      CHK(run_gemm(e, GEMM_NT, e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], ldH, T, H, e->O, nullptr,
-                   EPI_DACT, nullptr, ws_of(L - 1), cfg_o, &act));
-    }
-  }
-  if (fire && e->cb) e->cb(e->cb_user, 0);
-  for (int l = L - 1; l >= 0; --l) {
-    const LayerLayout& y = e->lay[l];
-    float* da = e->dA[pp];
-    if (stack_align(e) % bm_in || (T + bm_in - 1) / bm_in > kMaxRowSplits)
-      return fail(-1, "internal: EPI_DACT chunks of %d rows do not fit a stacked pass of %d rows", bm_in, T);
-    int slot = 0;
-    for (int i = 0; i < st.k; ++i) {  // BN backward per segment: its own column means, its own row count
-      ProfScope ps(e, KF_HIDDEN_BWD, 0, 28.0 * st.rows[i] * H);
-      const ActDesc d = act_desc(e, l, 1, call0 + (uint32_t)i);
-      Twin tw;
-      if (e->bf16) { tw.p = e->dAb[pp] + e->tw_row((size_t)st.r0[i], e->ldHb); tw.ld = e->ldHb; tw.x3 = e->x3; }
-      const size_t r = (size_t)st.r0[i] * ldH;
-      hidden_backward(e->stream, d, 1, da + r, e->a[l] + r, e->z[l] + r, e->seg_mean[l] + (size_t)i * ldH,
-                      e->seg_rstd[l] + (size_t)i * ldH, st.rows[i], H, ldH, ws_of(l) + (size_t)(st.r0[i] / bm_in) * ldH,
-                      (st.rows[i] + bm_in - 1) / bm_in, tw, st.span[i], ws_of(l) + ((size_t)2 * kMaxRowSplits + slot) * ldH);
-      slot += row_splits(st.span[i]);
-    }
-    if (slot > kMaxRowSplits) return fail(-1, "internal: %d partial-sum slots in a stacked pass", slot);
-    // d beta = sum of du over ALL rows (the chunks of every segment; padding chunks hold zeros), d bias = sum of dz
-    fin.it[fin.n++] = {ws_of(l), G + y.beta_off, 0, (T + bm_in - 1) / bm_in, H, ldH};
-    fin.it[fin.n++] = {ws_of(l), G + y.b_off, 2, slot, H, ldH};
-    if (fin.n + 2 > kMaxFinalItems) {
-      grad_final(e->stream, fin);
-      fin.n = 0;
-    }
-    const float* in = l == 0 ? Xd : e->a[l - 1];
-    const int ld_in = l == 0 ? ldx : ldH;
-    bool fused = false;
-    if (l > 0) {
-      ActEpi act = act_of(l - 1);
-      int bm = rows_h;
-      const int rc = run_gemm_dual(e, da, ldH, e->p_param() + y.w_off, y.ld_out, e->dA[pp ^ 1], ldH, T, H, H, &act,
-                                   ws_of(l - 1), in, ld_in, G + y.w_off, y.ld_out, y.d_in, H, epi_w, &bm);
-      if (rc < 0) return rc;
-      fused = rc == 0;
-      if (fused) bm_in = bm;
-    }
-    if (!fused) {
-      CHK(run_gemm(e, GEMM_TN, in, ld_in, da, ldH, G + y.w_off, y.ld_out, y.d_in, H, T, nullptr, epi_w));
-      if (l > 0) {
-        ActEpi act = act_of(l - 1);
-        CHK(run_gemm(e, GEMM_NT, da, ldH, e->p_param() + y.w_off, y.ld_out, e->dA[pp ^ 1], ldH, T, H, H, nullptr, EPI_DACT,
-                     nullptr, ws_of(l - 1), cfg_h, &act));
-        bm_in = rows_h;
-      }
-    }
-    if (fire && e->cb) e->cb(e->cb_user, L - l);
-    pp ^= 1;
-  }
-  {
-    ProfScope ps(e, KF_COLSUM, 0, 0);
-    grad_final(e->stream, fin);
-  }
-  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -1711,48 +1493,6 @@ void stack_layout(const tfk_engine* e, const int32_t* seg_rows, int k, Stack* st
   st->T_pad = row;
   st->T_valid = valid;
   st->d_vend = nullptr;
-}
-
-// forward + loss + backward of one stacked pass whose input is staged (Xd: [T_pad, ld], yd: labels with -1 on padding)
-int run_stacked(tfk_engine* e, const float* Xd, int ld, const int32_t* yd, const Stack& st, int flags, int slot_before) {
-  e->colsum_done = false;  // (as train_or_eval: never inherited from a call that failed half way)
-  if (e->bf16) {
-    const float* x = Xd;
-    CHK(twin_input(e, &x, &ld, st.T_pad));
-    Xd = x;
-  }
-  CHK(seg_stats(e));
-  const uint32_t call0 = e->call_counter;
-  e->call_counter += (uint32_t)st.k;
-  CHK(forward_stacked(e, Xd, ld, st, call0));
-  {
-    ProfScope ps(e, KF_SOFTMAX_XENT, 0, 8.0 * st.T_pad * e->O);
-    Twin tw;
-    if (e->bf16) { tw.p = e->logb; tw.ld = e->ldOb; tw.x3 = e->x3; }
-    softmax_xent(e->stream, e->logits, yd, st.T_pad, e->O, e->ldO, e->row_loss, 1, tw);
-  }
-  {
-    ProfScope ps(e, KF_COLSUM, 0, 4.0 * st.T_pad * e->O);
-    colsum_loss(e->stream, e->logits, st.T_pad, e->ldO, e->ws_bwd + (size_t)e->L * e->ws_bwd_stride, e->row_loss, st.T_pad,
-                e->p_scalars(), e->scalars_fresh, st.T_valid, st.k);
-    e->colsum_done = true;
-    e->scalars_fresh = false;
-  }
-  const bool fire = (flags & TFK_LAST_MICROBATCH) != 0;
-  if (fire) {
-    if (e->later_mb > 0) {
-      ProfScope ps(e, KF_MISC, 0, 8.0 * e->E);
-      scale_inplace(e->stream, e->p_ema(), e->E, (float)pow((double)e->bn_decay, (double)e->later_mb));
-    }
-    if (e->cb) e->cb(e->cb_user, e->L + 2);
-  }
-  CHK(backward_stacked(e, Xd, ld, st, call0, fire));
-  if (fire && e->cb) e->cb(e->cb_user, e->L + 1);
-  e->grads_fresh = false;
-  HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, slot_before));
-  e->last_T = st.T_pad; e->last_nfw = e->L; e->last_call = call0; e->last_in = Xd;
-  return 0;
 }
 
 // stage a stacked pass from a [T, F] matrix (host, or device with TFK_DEVICE_PTRS) whose segments lie back to back
@@ -1807,6 +1547,114 @@ int stage_stacked(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, 
   return 0;
 }
 
+// One staged pass: where its input lies on the device, the input slot it took, its depth and dropout stream.
+struct Pass {
+  const float* Xd;
+  const int32_t* yd;
+  int ld, T;        // T: rows of the pass (stacked: with the padding)
+  int slot_before, nact;
+  uint32_t call;    // (stacked: of the first segment)
+};
+struct NoTables { int operator()() const { return 0; } };
+int check_raw_flags(const RawSpec* raw, int flags) {
+  if (raw && (flags & TFK_DEVICE_PTRS)) return fail(-1, "the raw entry points take host pointers (TFK_RAW_DEVICE: raw alone on the device)");
+  if (!raw && (flags & TFK_RAW_DEVICE)) return fail(-1, "TFK_RAW_DEVICE belongs to the *_raw entry points");
+  return 0;
+}
+// Stage a pass of T rows (st: a stacked pass of T valid rows, seg_utts with raw): grow the buffers, bring the input to HBM, make
+// its bf16 twin, take the call index(es).  `tables` runs between the growth and the staging (CTC decoding stages its tables there).
+template <class Tables = NoTables>
+int stage_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T, int flags, const RawSpec* raw, Pass* p,
+               Stack* st = nullptr, const int32_t* seg_utts = nullptr, Tables tables = Tables()) {
+  HIPCHK(hipSetDevice(e->cfg.device));
+  p->T = st ? st->T_pad : T;
+  CHK(reserve(e, p->T));
+  CHK(tables());
+  p->slot_before = e->slot;
+  if (raw) CHK(stage_raw(e, X, ldx, y, T, raw->utt_len, raw->U, raw->context, raw->cmvn, &p->Xd, &p->ld, &p->yd,
+                         (flags & TFK_RAW_DEVICE) != 0, st, seg_utts));
+  else if (st) CHK(stage_stacked(e, X, ldx, y, flags, st, &p->Xd, &p->ld, &p->yd));
+  else CHK(stage_input(e, X, ldx, y, T, flags, &p->Xd, &p->ld, &p->yd));
+  if (e->bf16) CHK(twin_input(e, &p->Xd, &p->ld, p->T));
+  if (st) CHK(seg_stats(e));
+  p->call = e->call_counter;
+  e->call_counter += st ? (uint32_t)st->k : 1u;
+  p->nact = e->nact();
+  return 0;
+}
+// what tfk_debug_fetch reads back
+void remember_pass(tfk_engine* e, int T, int nfw, uint32_t call, const float* in) {
+  e->last_T = T; e->last_nfw = nfw; e->last_call = call; e->last_in = in;
+}
+
+// One micro-batch -- or, with `st`, one stacked pass of st->k micro-batches (train only) -- through staging, forward, loss and
+// backward.  The arguments have been checked.
+int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T, int flags, int train, const RawSpec* raw,
+             const CtcSpec* ctc, Stack* st = nullptr, const int32_t* seg_utts = nullptr) {
+  Pass p;
+  CHK(stage_pass(e, X, ldx, y, T, flags, raw, &p, st, seg_utts));
+  // (a call that failed between the fused loss / column-sum launch and its backward pass must not leave the flag behind for a
+  // later micro-batch -- a CTC one has no fused column sums: round-5 advisor finding)
+  e->colsum_done = false;
+  T = p.T;
+  // train mode evaluates every hidden layer when BN is on: the UPDATE_OPS of all batch-norm layers are
+  // fetched by update_gradients_op (trainer.py:164-169) even for layers the tf.case does not select.
+  const int nfw = (train && e->cfg.layerwise_init && e->cfg.batch_norm) ? e->L : p.nact;
+  CHK(forward(e, p.Xd, p.ld, T, train, p.nact, nfw, p.call, st));
+  if (ctc) {
+    CHK(ctc_loss(e, *ctc, T, train));
+  } else {
+    {
+      ProfScope ps(e, KF_SOFTMAX_XENT, 0, (train ? 8.0 : 4.0) * T * e->O);
+      Twin tw;
+      if (e->bf16 && train) { tw.p = e->logb; tw.ld = e->ldOb; tw.x3 = e->x3; }
+      softmax_xent(e->stream, e->logits, p.yd, T, e->O, e->ldO, e->row_loss, train, tw);
+    }
+    {
+      // (folding this sum into softmax_xent -- the block that finishes last adds up the frames' losses -- was measured in
+      // round 3 and is SLOWER than the second launch: 21.4 vs 9.3 + 6.3 us at cfg2, profiles/r03_fusion_experiments.txt)
+      // training: ONE launch with the column sums of dLogits the backward pass starts with (kernels.hip: colsum_loss_kernel)
+      ProfScope ps(e, train ? KF_COLSUM : KF_LOSS_REDUCE, 0, train ? 4.0 * T * e->O : 4.0 * T);
+      if (train) {
+        colsum_loss(e->stream, e->logits, T, e->ldO, e->ws_bwd + (size_t)e->L * e->ws_bwd_stride, e->row_loss, T, e->p_scalars(),
+                    e->scalars_fresh, st ? st->T_valid : -1, st ? st->k : 1);
+        e->colsum_done = true;
+      } else {
+        loss_reduce(e->stream, e->row_loss, T, e->p_scalars(), e->scalars_fresh);
+      }
+      e->scalars_fresh = false;
+    }
+  }
+  if (train) {
+    const bool fire = (flags & TFK_LAST_MICROBATCH) != 0;
+    if (fire) {
+      // loss, frame count and the BN moving-average increments of the step are final once the last micro-batch's
+      // forward + loss have run: their (tiny) bucket is announced FIRST, so that its all-reduce is long done when
+      // the optimiser needs the frame count
+      if (e->cfg.batch_norm && e->later_mb > 0) {
+        ProfScope ps(e, KF_MISC, 0, 8.0 * e->E);
+        scale_inplace(e->stream, e->p_ema(), e->E, (float)pow((double)e->bn_decay, (double)e->later_mb));
+      }
+      if (e->cb) e->cb(e->cb_user, e->L + 2);
+    }
+    CHK(backward(e, p.Xd, p.ld, T, p.nact, p.call, fire, st));
+    if (fire && e->cb) e->cb(e->cb_user, e->L + 1);  // bias / beta gradients: finalised by backward's last kernel
+    e->grads_fresh = false;
+  }
+  HIPCHK(hipGetLastError());
+  CHK(finish_slot(e, flags, p.slot_before));
+  remember_pass(e, T, nfw, p.call, p.Xd);
+  return 0;
+}
+int train_or_eval(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int32_t T, int flags, int train,
+                  const RawSpec* raw = nullptr, const CtcSpec* ctc = nullptr) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (T <= 0) return fail(-1, "empty micro-batch (T = %d)", T);
+  if (!X || (!y && !ctc)) return fail(-1, "X / y is NULL");
+  CHK(check_raw_flags(raw, flags));
+  return run_pass(e, X, ldx, y, T, flags, train, raw, ctc);
+}
+
 // Cut the k micro-batches of a call into runs: consecutive segments that fit one stacked pass, and single segments that
 // go through the ordinary path.  fn(first, count, stacked) is called for every run in order.
 template <class Fn>
@@ -1830,6 +1678,50 @@ int for_each_run(const tfk_engine* e, const int32_t* seg_rows, int k, Fn fn) {
       i += 1;
     }
   }
+  return 0;
+}
+
+// the k micro-batches of a tfk_*accumulate_stacked call: seg_rows[i] > 0 rows each, T in all
+int check_seg_rows(const int32_t* seg_rows, int k, int T) {
+  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
+  long total = 0;
+  for (int i = 0; i < k; ++i) {
+    if (seg_rows[i] <= 0) return fail(-1, "micro-batch %d of the stack is empty (%d rows)", i, seg_rows[i]);
+    total += seg_rows[i];
+  }
+  if (total != T) return fail(-1, "the micro-batches hold %ld rows, expected T = %d", total, T);
+  return 0;
+}
+// the k micro-batches of a tfk_*accumulate_stacked_raw call (`who`), seg_utts[i] > 0 utterances each: where micro-batch i starts
+// in the utterance table / the frames, and its rows
+struct SegTable {
+  std::vector<int> first_utt, first_row;  // [k + 1]
+  std::vector<int32_t> seg_rows;          // [k]
+  int D;                                  // raw dimension
+};
+int check_seg_utts(const tfk_engine* e, const char* who, const int32_t* utt_len, int U, int T, int context_width,
+                   const int32_t* seg_utts, int k, int flags, SegTable* t) {
+  if (flags & (TFK_DEVICE_PTRS | TFK_RAW_DEVICE)) return fail(-1, "%s takes host pointers", who);
+  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
+  const int win = 2 * context_width + 1;
+  if (context_width < 0 || e->F % win) return fail(-1, "input_dim %d is not a multiple of 2*context_width+1 = %d", e->F, win);
+  t->D = e->F / win;
+  t->first_utt.assign(k + 1, 0);
+  t->first_row.assign(k + 1, 0);
+  t->seg_rows.assign(k, 0);
+  for (int i = 0; i < k; ++i) {
+    if (seg_utts[i] <= 0) return fail(-1, "micro-batch %d of the stack holds no utterance", i);
+    t->first_utt[i + 1] = t->first_utt[i] + seg_utts[i];
+    if (t->first_utt[i + 1] > U) return fail(-1, "the micro-batches hold more than U = %d utterances", U);
+    for (int u = t->first_utt[i]; u < t->first_utt[i + 1]; ++u) {
+      if (utt_len[u] < 0) return fail(-1, "negative utterance length");
+      t->seg_rows[i] += utt_len[u];
+    }
+    if (t->seg_rows[i] <= 0) return fail(-1, "micro-batch %d of the stack is empty", i);
+    t->first_row[i + 1] = t->first_row[i] + t->seg_rows[i];
+  }
+  if (t->first_utt[k] != U || t->first_row[k] != T)
+    return fail(-1, "the micro-batches hold %d utterances / %d frames, expected U = %d / T = %d", t->first_utt[k], t->first_row[k], U, T);
   return 0;
 }
 
@@ -2018,14 +1910,7 @@ int tfk_accumulate_stacked(tfk_engine* e, const float* X, int64_t ldx, const int
                            int32_t k, int flags) {
   if (!e) return fail(-1, "engine is NULL");
   if (!X || !y || !seg_rows) return fail(-1, "X / y / seg_rows is NULL");
-  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
-  long total = 0;
-  for (int i = 0; i < k; ++i) {
-    if (seg_rows[i] <= 0) return fail(-1, "micro-batch %d of the stack is empty (%d rows)", i, seg_rows[i]);
-    total += seg_rows[i];
-  }
-  if (total != T) return fail(-1, "the micro-batches hold %ld rows, expected T = %d", total, T);
-  HIPCHK(hipSetDevice(e->cfg.device));
+  CHK(check_seg_rows(seg_rows, k, T));
   std::vector<int> first(k + 1, 0);
   for (int i = 0; i < k; ++i) first[i + 1] = first[i] + seg_rows[i];
   return for_each_run(e, seg_rows, k, [&](int i0, int n, bool stacked) -> int {
@@ -2036,11 +1921,7 @@ int tfk_accumulate_stacked(tfk_engine* e, const float* X, int64_t ldx, const int
     if (!stacked) return train_or_eval(e, Xr, ldx, yr, seg_rows[i0], fl, 1);
     Stack st;
     stack_layout(e, seg_rows + i0, n, &st);
-    CHK(reserve(e, st.T_pad));
-    const float* Xd; const int32_t* yd; int ld;
-    const int slot_before = e->slot;
-    CHK(stage_stacked(e, Xr, ldx, yr, fl, &st, &Xd, &ld, &yd));
-    return run_stacked(e, Xd, ld, yd, st, fl, slot_before);
+    return run_pass(e, Xr, ldx, yr, st.T_valid, fl, 1, nullptr, nullptr, &st);
   });
 }
 
@@ -2049,45 +1930,19 @@ int tfk_accumulate_stacked_raw(tfk_engine* e, const float* raw, int64_t ldraw, c
                                const int32_t* seg_utts, int32_t k, int flags) {
   if (!e) return fail(-1, "engine is NULL");
   if (!raw || !y || !utt_len || !seg_utts) return fail(-1, "raw / y / utt_len / seg_utts is NULL");
-  if (flags & (TFK_DEVICE_PTRS | TFK_RAW_DEVICE)) return fail(-1, "tfk_accumulate_stacked_raw takes host pointers");
-  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
-  const int win = 2 * context_width + 1;
-  if (context_width < 0 || e->F % win) return fail(-1, "input_dim %d is not a multiple of 2*context_width+1 = %d", e->F, win);
-  const int D = e->F / win;
-  std::vector<int> first_utt(k + 1, 0), first_row(k + 1, 0);
-  std::vector<int32_t> seg_rows(k, 0);
-  for (int i = 0; i < k; ++i) {
-    if (seg_utts[i] <= 0) return fail(-1, "micro-batch %d of the stack holds no utterance", i);
-    first_utt[i + 1] = first_utt[i] + seg_utts[i];
-    if (first_utt[i + 1] > U) return fail(-1, "the micro-batches hold more than U = %d utterances", U);
-    for (int u = first_utt[i]; u < first_utt[i + 1]; ++u) {
-      if (utt_len[u] < 0) return fail(-1, "negative utterance length");
-      seg_rows[i] += utt_len[u];
-    }
-    if (seg_rows[i] <= 0) return fail(-1, "micro-batch %d of the stack is empty", i);
-    first_row[i + 1] = first_row[i] + seg_rows[i];
-  }
-  if (first_utt[k] != U || first_row[k] != T)
-    return fail(-1, "the micro-batches hold %d utterances / %d frames, expected U = %d / T = %d", first_utt[k], first_row[k], U, T);
-  HIPCHK(hipSetDevice(e->cfg.device));
-  return for_each_run(e, seg_rows.data(), k, [&](int i0, int n, bool stacked) -> int {
+  SegTable t;
+  CHK(check_seg_utts(e, "tfk_accumulate_stacked_raw", utt_len, U, T, context_width, seg_utts, k, flags, &t));
+  return for_each_run(e, t.seg_rows.data(), k, [&](int i0, int n, bool stacked) -> int {
     const int last = (i0 + n == k) ? (flags & TFK_LAST_MICROBATCH) : 0;
-    const float* rr = raw + (size_t)first_row[i0] * ldraw;
-    const int32_t* yr = y + first_row[i0];
-    const int32_t* ul = utt_len + first_utt[i0];
-    const float* cm = cmvn ? cmvn + (size_t)first_utt[i0] * 2 * D : nullptr;
-    const int nu = first_utt[i0 + n] - first_utt[i0], nt = first_row[i0 + n] - first_row[i0];
-    if (!stacked) {
-      const RawSpec r = {ul, nu, context_width, cm};
-      return train_or_eval(e, rr, ldraw, yr, nt, last, 1, &r);
-    }
+    const RawSpec r = {utt_len + t.first_utt[i0], t.first_utt[i0 + n] - t.first_utt[i0], context_width,
+                       cmvn ? cmvn + (size_t)t.first_utt[i0] * 2 * t.D : nullptr};
+    const float* rr = raw + (size_t)t.first_row[i0] * ldraw;
+    const int32_t* yr = y + t.first_row[i0];
+    const int nt = t.first_row[i0 + n] - t.first_row[i0];
+    if (!stacked) return train_or_eval(e, rr, ldraw, yr, nt, last, 1, &r);
     Stack st;
-    stack_layout(e, seg_rows.data() + i0, n, &st);
-    CHK(reserve(e, st.T_pad));
-    const float* Xd; const int32_t* yd; int ld;
-    const int slot_before = e->slot;
-    CHK(stage_raw(e, rr, ldraw, yr, nt, ul, nu, context_width, cm, &Xd, &ld, &yd, false, &st, seg_utts + i0));
-    return run_stacked(e, Xd, ld, yd, st, last, slot_before);
+    stack_layout(e, t.seg_rows.data() + i0, n, &st);
+    return run_pass(e, rr, ldraw, yr, nt, last, 1, &r, nullptr, &st, seg_utts + i0);
   });
 }
 
@@ -2109,13 +1964,7 @@ int tfk_eval_accumulate_stacked(tfk_engine* e, const float* X, int64_t ldx, cons
                                 int32_t k, int flags) {
   if (!e) return fail(-1, "engine is NULL");
   if (!X || !y || !seg_rows) return fail(-1, "X / y / seg_rows is NULL");
-  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
-  long total = 0;
-  for (int i = 0; i < k; ++i) {
-    if (seg_rows[i] <= 0) return fail(-1, "micro-batch %d of the stack is empty (%d rows)", i, seg_rows[i]);
-    total += seg_rows[i];
-  }
-  if (total != T) return fail(-1, "the micro-batches hold %ld rows, expected T = %d", total, T);
+  CHK(check_seg_rows(seg_rows, k, T));
   const int cap = eval_pass_rows();
   for (int i0 = 0, r0 = 0; i0 < k;) {
     int n = 0, rows = 0;
@@ -2131,34 +1980,16 @@ int tfk_eval_accumulate_stacked_raw(tfk_engine* e, const float* raw, int64_t ldr
                                     const int32_t* seg_utts, int32_t k, int flags) {
   if (!e) return fail(-1, "engine is NULL");
   if (!raw || !y || !utt_len || !seg_utts) return fail(-1, "raw / y / utt_len / seg_utts is NULL");
-  if (flags & (TFK_DEVICE_PTRS | TFK_RAW_DEVICE)) return fail(-1, "tfk_eval_accumulate_stacked_raw takes host pointers");
-  if (k <= 0) return fail(-1, "no micro-batch (k = %d)", k);
-  const int win = 2 * context_width + 1;
-  if (context_width < 0 || e->F % win) return fail(-1, "input_dim %d is not a multiple of 2*context_width+1 = %d", e->F, win);
-  const int D = e->F / win;
-  std::vector<int> first_utt(k + 1, 0), first_row(k + 1, 0);
-  for (int i = 0; i < k; ++i) {
-    if (seg_utts[i] <= 0) return fail(-1, "micro-batch %d of the stack holds no utterance", i);
-    first_utt[i + 1] = first_utt[i] + seg_utts[i];
-    if (first_utt[i + 1] > U) return fail(-1, "the micro-batches hold more than U = %d utterances", U);
-    int rows = 0;
-    for (int u = first_utt[i]; u < first_utt[i + 1]; ++u) {
-      if (utt_len[u] < 0) return fail(-1, "negative utterance length");
-      rows += utt_len[u];
-    }
-    if (rows <= 0) return fail(-1, "micro-batch %d of the stack is empty", i);
-    first_row[i + 1] = first_row[i] + rows;
-  }
-  if (first_utt[k] != U || first_row[k] != T)
-    return fail(-1, "the micro-batches hold %d utterances / %d frames, expected U = %d / T = %d", first_utt[k], first_row[k], U, T);
+  SegTable t;
+  CHK(check_seg_utts(e, "tfk_eval_accumulate_stacked_raw", utt_len, U, T, context_width, seg_utts, k, flags, &t));
   const int cap = eval_pass_rows();
   for (int i0 = 0; i0 < k;) {
     int n = 1;
-    while (i0 + n < k && first_row[i0 + n + 1] - first_row[i0] <= cap) ++n;
-    const RawSpec r = {utt_len + first_utt[i0], first_utt[i0 + n] - first_utt[i0], context_width,
-                       cmvn ? cmvn + (size_t)first_utt[i0] * 2 * D : nullptr};
-    CHK(train_or_eval(e, raw + (size_t)first_row[i0] * ldraw, ldraw, y + first_row[i0], first_row[i0 + n] - first_row[i0],
-                      flags & ~TFK_LAST_MICROBATCH, 0, &r));
+    while (i0 + n < k && t.first_row[i0 + n + 1] - t.first_row[i0] <= cap) ++n;
+    const RawSpec r = {utt_len + t.first_utt[i0], t.first_utt[i0 + n] - t.first_utt[i0], context_width,
+                       cmvn ? cmvn + (size_t)t.first_utt[i0] * 2 * t.D : nullptr};
+    CHK(train_or_eval(e, raw + (size_t)t.first_row[i0] * ldraw, ldraw, y + t.first_row[i0],
+                      t.first_row[i0 + n] - t.first_row[i0], flags & ~TFK_LAST_MICROBATCH, 0, &r));
     i0 += n;
   }
   return 0;
@@ -2394,21 +2225,16 @@ int tfk_set_prior(tfk_engine* e, const float* prior, size_t count) {
 static int posteriors_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t N, float* out, int64_t ldo, int flags,
                            const RawSpec* raw) {
   if (!e) return fail(-1, "engine is NULL");
-  if (raw && (flags & TFK_DEVICE_PTRS)) return fail(-1, "the raw entry points take host pointers (TFK_RAW_DEVICE: raw alone on the device)");
-  if (!raw && (flags & TFK_RAW_DEVICE)) return fail(-1, "TFK_RAW_DEVICE belongs to the *_raw entry points");
+  CHK(check_raw_flags(raw, flags));
   if (N <= 0) return fail(-1, "empty utterance (N = %d)", N);
   if (!X || !out) return fail(-1, "X / out is NULL");
   if (ldo < e->O) return fail(-1, "ldo %lld < output_dim %d", (long long)ldo, e->O);
   if ((flags & TFK_LOG_DIV_PRIOR) && !e->have_prior) return fail(-1, "TFK_LOG_DIV_PRIOR without tfk_set_prior");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  CHK(reserve(e, N));
-  const float* Xd; const int32_t* yd; int ld;
-  const int slot_before = e->slot;
-  if (raw) CHK(stage_raw(e, X, ldx, nullptr, N, raw->utt_len, raw->U, raw->context, raw->cmvn, &Xd, &ld, &yd, (flags & TFK_RAW_DEVICE) != 0));
-  else CHK(stage_input(e, X, ldx, nullptr, N, flags, &Xd, &ld, &yd));
-  if (e->bf16) CHK(twin_input(e, &Xd, &ld, N));
-  const int nact = e->nact();
-  const uint32_t call = e->call_counter++;
+  Pass p;
+  CHK(stage_pass(e, X, ldx, nullptr, N, flags, raw, &p));
+  const float* Xd = p.Xd;
+  const int ld = p.ld, slot_before = p.slot_before, nact = p.nact;
+  const uint32_t call = p.call;
   const float* prior = (flags & TFK_LOG_DIV_PRIOR) ? e->prior : nullptr;
   const bool want_logits = (flags & TFK_RAW_LOGITS) != 0;
   // a caller that hands over PINNED host memory gets the result by DMA, without a staging copy
@@ -2463,9 +2289,7 @@ static int posteriors_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t N
     HIPCHK(hipStreamSynchronize(e->copy_stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipGetLastError());
-    const int n_last = N - (nchunks - 1) * e->post_chunk;
-    e->last_T = n_last; e->last_nfw = nact; e->last_call = call;
-    e->last_in = Xd + (size_t)(nchunks - 1) * e->post_chunk * ld;
+    remember_pass(e, N - (nchunks - 1) * e->post_chunk, nact, call, Xd + (size_t)(nchunks - 1) * e->post_chunk * ld);
     return 0;
   }
   CHK(forward(e, Xd, ld, N, 0, nact, nact, call));
@@ -2489,7 +2313,7 @@ static int posteriors_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t N
                               e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       HIPCHK(hipGetLastError());
-      e->last_T = N; e->last_nfw = nact; e->last_call = call; e->last_in = Xd;
+      remember_pass(e, N, nact, call, Xd);
       return 0;
     }
     const size_t need = (size_t)N * e->O;
@@ -2506,7 +2330,7 @@ static int posteriors_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t N
     for (int t = 0; t < N; ++t) memcpy(out + (size_t)t * ldo, e->h_post + (size_t)t * e->O, (size_t)e->O * sizeof(float));
   }
   HIPCHK(hipGetLastError());
-  e->last_T = N; e->last_nfw = nact; e->last_call = call; e->last_in = Xd;
+  remember_pass(e, N, nact, call, Xd);
   return 0;
 }
 
@@ -2535,21 +2359,15 @@ static int ctc_greedy_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T
   if (!X) return fail(-1, "X is NULL");
   if (!hyp || !hyp_len) return fail(-1, "hyp / hyp_len is NULL");
   if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  CHK(reserve(e, T));
   const CtcSpec c = {utt_len, U, ref_labels, ref_len};
   int max_ref = 0;
-  CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
-  const size_t words = 2 * (size_t)T + 2 * (size_t)U;  // [class ids | hypotheses | lengths | distances]
-  CHK(grow(e, &e->ctc_dec, &e->ctc_cap_dec, words));
-  const float* Xd; const int32_t* yd; int ld;
-  const int slot_before = e->slot;
-  if (raw) CHK(stage_raw(e, X, ldx, nullptr, T, raw->utt_len, raw->U, raw->context, raw->cmvn, &Xd, &ld, &yd, (flags & TFK_RAW_DEVICE) != 0));
-  else CHK(stage_input(e, X, ldx, nullptr, T, 0, &Xd, &ld, &yd));
-  if (e->bf16) CHK(twin_input(e, &Xd, &ld, T));
-  const int nact = e->nact();
-  const uint32_t call = e->call_counter++;
-  CHK(forward(e, Xd, ld, T, 0, nact, nact, call));
+  Pass p;
+  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
+    CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
+    const size_t words = 2 * (size_t)T + 2 * (size_t)U;  // [class ids | hypotheses | lengths | distances]
+    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, words);
+  }));
+  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
   int32_t* d_cls = e->ctc_dec;
   int32_t* d_hyp = d_cls + T;
   int32_t* d_len = d_hyp + T;
@@ -2563,7 +2381,7 @@ static int ctc_greedy_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T
     label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_dist);
   }
   HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, slot_before));
+  CHK(finish_slot(e, flags, p.slot_before));
   const size_t back = (size_t)T + 2 * (size_t)U;
   if (back > e->h_dec_cap) {
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -2576,7 +2394,7 @@ static int ctc_greedy_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T
   HIPCHK(hipMemcpyAsync(e->h_dec, d_hyp, (edits ? back : back - U) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipGetLastError());
-  e->last_T = T; e->last_nfw = nact; e->last_call = call; e->last_in = Xd;
+  remember_pass(e, T, p.nact, p.call, p.Xd);
   CHK(check_kernel_errors(e));
   memcpy(hyp, e->h_dec, (size_t)T * sizeof(int32_t));
   memcpy(hyp_len, e->h_dec + T, (size_t)U * sizeof(int32_t));
