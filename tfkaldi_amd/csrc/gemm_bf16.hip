@@ -55,11 +55,8 @@ constexpr int NUM_XCD = 8;
 // `group_rows` tile rows, column-major inside a group), i.e. a patch of about group_rows x (run / group_rows) tiles that
 // share A row-panels and B column-panels in that XCD's L2.  The host picks group_rows so that the patch is square in
 // BYTES (group_rows * BM ~ columns * BN), which minimises what the eight private L2s fetch from the fabric.
-__device__ __forceinline__ void tile_of_block(int tiles_m, int tiles_n, int group_rows, int bid, int& tm, int& tn) {
-  const int nwg = tiles_m * tiles_n;
-  const int xcd = bid % NUM_XCD, loc = bid / NUM_XCD;
-  const int q = nwg / NUM_XCD, r = nwg % NUM_XCD;
-  const int seq = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+// (tile_of_seq: the tile at position `seq` of the grouped sequence -- a block of a tile LIST walks consecutive positions)
+__device__ __forceinline__ void tile_of_seq(int tiles_m, int tiles_n, int group_rows, int seq, int& tm, int& tn) {
   const int per_group = group_rows * tiles_n;
   const int grp = seq / per_group;
   const int first_m = grp * group_rows;
@@ -68,6 +65,13 @@ __device__ __forceinline__ void tile_of_block(int tiles_m, int tiles_n, int grou
   tm = first_m + within % gsize;
   tn = within / gsize;
 }
+__device__ __forceinline__ void tile_of_block(int tiles_m, int tiles_n, int group_rows, int bid, int& tm, int& tn) {
+  const int nwg = tiles_m * tiles_n;
+  const int xcd = bid % NUM_XCD, loc = bid / NUM_XCD;
+  const int q = nwg / NUM_XCD, r = nwg % NUM_XCD;
+  const int seq = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+  tile_of_seq(tiles_m, tiles_n, group_rows, seq, tm, tn);
+}
 
 __device__ __forceinline__ uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
 
@@ -75,7 +79,11 @@ __device__ __forceinline__ uint16_t f2bf(float x) { return __builtin_bit_cast(ui
 // Wave (wm, wn) of a WAVES_M x WAVES_N arrangement owns the 32x32 fragments acc[a][b] at rows
 // m0 + (wm * FM + a) * 32, columns n0 + (wn * FN + b) * 32.  D reg r of lane (i, h) is row (r&3) + 8*(r>>2) + 4*h,
 // column i of its fragment.  `red` = LDS scratch (the K loop ended behind a barrier), >= 2 * WAVES_M * BN floats.
-template <int EPI, int WAVES_M, int WAVES_N, int FM, int FN>
+// CBUF: C is written (EPI_ACCUM: read) through a buffer resource that covers exactly [M, N] of it, the whole byte offset in the
+// per-lane operand: a register outside the matrix is dropped by the range check, and a store is one address addition + the
+// store -- the flat form costs twelve instructions per register (two compares, a 64-bit multiply-add, an exec-mask branch),
+// ~2 us of issue time per 128x128 tile on eight waves.  The caller guarantees M * ldc * 4 < 2^31.
+template <int EPI, int WAVES_M, int WAVES_N, int FM, int FN, bool CBUF = false>
 __device__ __forceinline__ void epilogue(const GemmArgsB& p, f32x16 (&acc)[FM][FN], int tiles_m, int tm, int m0, int n0,
                                          int wm, int wn, int i, int h, float* red) {
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
@@ -204,6 +212,30 @@ __device__ __forceinline__ void epilogue(const GemmArgsB& p, f32x16 (&acc)[FM][F
         p.stats[((size_t)1 * p.stats_stride + tm) * p.ldc + col] = t2;
       }
       __syncthreads();
+    }
+    if constexpr (CBUF) {
+      static_assert((EPI & EPI_EVAL_ACT) == 0, "no bf16 twin on this path");
+      const __amdgpu_buffer_rsrc_t crs =
+          __builtin_amdgcn_make_buffer_rsrc((void*)p.C, 0, (int)(((unsigned)(p.M - 1) * p.ldc + p.N) * 4u), 0x00020000);
+#pragma unroll
+      for (int a = 0; a < FM; ++a) {
+        const unsigned base = col_ok ? ((unsigned)(m0 + (wm * FM + a) * 32 + 4 * h) * p.ldc + col) * 4u : (unsigned)kOOB;
+        float old[16];
+        if constexpr ((EPI & EPI_ACCUM) != 0) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            old[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                   crs, base + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc) * 4u, 0, 0));
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float v = acc[a][b][r];
+          if (EPI & EPI_ACCUM) v += old[r];
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), crs,
+                                                base + (unsigned)(((r & 3) + 8 * (r >> 2)) * p.ldc) * 4u, 0, 0);
+        }
+      }
+      continue;
     }
 #pragma unroll
     for (int a = 0; a < FM; ++a) {
@@ -470,6 +502,12 @@ struct Frag3M {
 #define TFKB_ABL 0
 #endif
 
+// TFKB_TL(event, tile of the block's list) (tools/ubench/x3_dual_timeline.hip only): a time stamp per block and tile at entry,
+// in front of the first MFMA, behind the last one and behind the epilogue.  Nothing in the library.
+#ifndef TFKB_TL
+#define TFKB_TL(ev, ti)
+#endif
+
 #define TFKB_WAIT_BARRIER(n) \
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(n) : "memory")
 
@@ -495,9 +533,11 @@ constexpr int kSplitXccWord = 2048;
 // once its own pieces of the NEXT tile have landed); after the K loop the loaders end -- a barrier counts surviving waves only,
 // so the epilogue's barriers are the multipliers' own.
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
-          int NPL = 1, int KSPLIT = 1, int LOADERS = 0>
-__device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int tiles_n, int group_rows, int bid, char* smem) {
+          int NPL = 1, int KSPLIT = 1, int LOADERS = 0, bool LIST = false, bool CBUF = false>
+__device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int tiles_n, int group_rows, int bid, char* smem,
+                                         int seq0 = 0, int ntiles = 1) {
   static_assert(LOADERS == 0 || (NPL == 3 && LOADERS == WAVES_M * WAVES_N), "loader waves: one per multiplying wave, x3 only");
+  static_assert(!LIST || (NPL == 3 && KSPLIT == 1 && LOADERS == 0), "tile lists: the unsplit fp32-emulating contraction, no loader waves");
   constexpr int NTH = WAVES_M * WAVES_N * 64;
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
   // (NPL == 3: one image per operand holds its three planes, x3_layout.h)
@@ -522,8 +562,9 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   // same time and meet in that XCD's L2; the tile sequence is the unsplit one (tiles_m * tiles_n is a multiple of 8 here)
   const int khalf = KSPLIT == 2 ? (bid / NUM_XCD) & 1 : 0;
   const int tile_bid = KSPLIT == 2 ? (bid / NUM_XCD >> 1) * NUM_XCD + bid % NUM_XCD : bid;
-  tile_of_block(tiles_m, tiles_n, group_rows, tile_bid, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
+  if constexpr (LIST) tile_of_seq(tiles_m, tiles_n, group_rows, seq0, tm, tn);
+  else tile_of_block(tiles_m, tiles_n, group_rows, tile_bid, tm, tn);
+  int m0 = tm * BM, n0 = tn * BN;
   unsigned my_xcc = 0;
   if constexpr (KSPLIT == 2) {
     // where this block runs, for its partner to read when the two meet (below): a fact about THIS launch, whatever the placement
@@ -581,10 +622,15 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
       TFKB_WAIT_BARRIER(0);
       return;
     }
-  } else {
-    la.init(p.A, p.lda, A_KC ? p.M : p.K, m0, A_KC ? p.M : ((p.M + 7) & ~7), a_klim, tid);
-    lb.init(p.B, p.ldb, B_KC ? p.N : p.K, n0, B_KC ? p.N : ((p.N + 7) & ~7), b_klim, tid);
   }
+  // the loaders' per-lane offsets for the tile at (m0, n0)
+  auto init_loaders = [&]() {
+    if constexpr (LOADERS == 0) {
+      la.init(p.A, p.lda, A_KC ? p.M : p.K, m0, A_KC ? p.M : ((p.M + 7) & ~7), a_klim, tid);
+      lb.init(p.B, p.ldb, B_KC ? p.N : p.K, n0, B_KC ? p.N : ((p.N + 7) & ~7), b_klim, tid);
+    }
+  };
+  init_loaders();
   typename std::conditional<NPL == 3, Frag3<A_KC, BM, FM>, Frag<A_KC, BM, FM, BKT>>::type qa;
   typename std::conditional<NPL == 3, Frag3<B_KC, BN, FN>, Frag<B_KC, BN, FN, BKT>>::type qb;
   qa.init(lane, wm * FM);
@@ -592,20 +638,22 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
 
   f32x16 acc[FM][FN];
   f32x16 acc2[NPL == 3 ? FM : 1][NPL == 3 ? FN : 1];  // (NPL == 3: the correction products, see mfma_step)
-#pragma unroll
-  for (int a = 0; a < FM; ++a)
-#pragma unroll
-    for (int b = 0; b < FN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-  if constexpr (NPL == 3) {
+  auto zero_acc = [&]() {
 #pragma unroll
     for (int a = 0; a < FM; ++a)
 #pragma unroll
       for (int b = 0; b < FN; ++b)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[a][b][r] = 0.f;
-  }
+        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    if constexpr (NPL == 3) {
+#pragma unroll
+      for (int a = 0; a < FM; ++a)
+#pragma unroll
+        for (int b = 0; b < FN; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc2[a][b][r] = 0.f;
+    }
+  };
 
   // (guard: std::true_type -- a piece beyond the operand's k range lands as zeros; std::false_type, NPL == 3 only: the caller
   //  knows the tile lies inside it, see DmaOperand3::issue)
@@ -627,15 +675,17 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   };
   auto piece = [&](int j, int slot, int kt) { piece_g(std::true_type(), j, slot, kt); };
   // prologue: tiles 0 .. NS-2 (tiles beyond K land as zeros without touching memory)
-#pragma unroll
-  for (int t = 0; t < NS - 1; ++t)
-#pragma unroll
-    for (int j = 0; j < NP; ++j) piece(j, t, t);
   // (NPL == 3 spreads a tile's pieces over TWO half-steps, see its loop: the first half of tile NS-1 goes out here)
   constexpr int NPH = NPL == 3 ? NP / 2 : 0;
+  auto prologue = [&]() {
 #pragma unroll
-  for (int j = 0; j < NPH; ++j) piece(j, NS - 1, NS - 1);
-  TFKB_WAIT_BARRIER((NS - 2) * NP + NPH);
+    for (int t = 0; t < NS - 1; ++t)
+#pragma unroll
+      for (int j = 0; j < NP; ++j) piece(j, t, t);
+#pragma unroll
+    for (int j = 0; j < NPH; ++j) piece(j, NS - 1, NS - 1);
+    TFKB_WAIT_BARRIER((NS - 2) * NP + NPH);
+  };
 
   bf16x8 fa[2][NPL][FM], fb[2][NPL][FN];
   auto read_frags = [&](int buf, const char* st, int ks) {
@@ -712,347 +762,405 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   // every wave of the block then waited for them at the same moment (all waves leave a barrier together): ~300 idle
   // matrix-pipe cycles per 64-k tile on the 8-wave 256x128 block, where MFMAs + fragment reads cost 53 us against 43.5 us
   // of MFMAs alone (profiles/r02_gemm_bf16_ablation.txt).
+  // A tile LIST (x3_layout.h: the short problem of a dual launch): `nlist` consecutive tiles of the grouped sequence, one after
+  // the other on this CU.  Where the block form allows it (CHAIN) the ring KEEPS RUNNING across a tile boundary: the last NS
+  // iterations of a tile, which would issue pieces behind its K range (zeros), issue the first ring tiles of the NEXT tile
+  // instead -- the loaders' offsets switch once, behind the barrier of iteration nk - NS, from where on every piece is the next
+  // tile's -- and the last iteration fetches the next tile's first fragments.  The counted waits stay what they are (the same
+  // number of pieces is issued between any two barriers).  The tile's epilogue then runs with the next tile's pieces landing,
+  // its stores are waited for no earlier than at the next tile's first barrier, and `red` lies behind the ring.  A tile of fewer
+  // than NS ring tiles, or a block form without the chain, drains the ring and starts the next tile from its prologue.
+  constexpr bool CHAIN = LIST && NPL == 3 && TFK_X3_M16 == 0 && SCHED == 0;
+  const int nlist = LIST ? ntiles : 1;
+  float* const red = reinterpret_cast<float*>(smem + (LIST ? NS * STAGE : 0));
+  bool primed = false;  // the ring holds this tile's first ring tiles and fa[0] / fb[0] its first fragments
   int rs = 0, ws = NS - 1;
-  if constexpr (SCHED == 2) {
-    // Half-steps are numbered by the barriers between them.  Waves 0 .. 3 (group 0, one per SIMD): LOAD(0) | MUL(0) | LOAD(1) | ..;
-    // waves 4 .. 7 (group 1, their SIMD partners): idle | LOAD(0) | MUL(0) | ..  LOAD(t) reads every fragment of slot t into
-    // registers, issues the wave's pieces of tile t+NS-1 into the slot tile t-1 occupied (its last reader, the other group,
-    // finished one half-step earlier) and waits for its own pieces of tile t+1; MUL(t) is KSPT * FM * FN MFMAs and nothing else.
-    static_assert(WAVES_M * WAVES_N == 8, "two waves per SIMD");
-    const int group = wave >> 2;
-    bf16x8 wa[KSPT][FM], wb[KSPT][FN];
-    if (group == 1) {
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_barrier" : : : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    }
 #pragma unroll 1
-    for (int kt = 0; kt < nk; ++kt) {
-      const char* st = smem + rs * STAGE;
-#pragma unroll
-      for (int ks = 0; ks < KSPT; ++ks) {
-#pragma unroll
-        for (int a = 0; a < FM; ++a) wa[ks][a] = qa.read(st, a, ks);
-#pragma unroll
-        for (int b = 0; b < FN; ++b) wb[ks][b] = qb.read(st + A_BYTES, b, ks);
+  for (int ti = 0; ti < nlist; ++ti) {
+    TFKB_TL(0, ti);
+    if (!primed) {
+      if (ti > 0) {
+        tile_of_seq(tiles_m, tiles_n, group_rows, seq0 + ti, tm, tn);
+        m0 = tm * BM;
+        n0 = tn * BN;
+        init_loaders();
       }
-#pragma unroll
-      for (int j = 0; j < NP; ++j) piece(j, ws, kt + NS - 1);
-      __builtin_amdgcn_sched_barrier(0);
-      TFKB_WAIT_BARRIER((NS - 2) * NP);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < KSPT; ++ks)
-#pragma unroll
-        for (int a = 0; a < FM; ++a)
-#pragma unroll
-          for (int b = 0; b < FN; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][a], wb[ks][b], acc[a][b], 0, 0, 0);
-      rs = rs + 1 == NS ? 0 : rs + 1;
-      ws = ws + 1 == NS ? 0 : ws + 1;
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_barrier" : : : "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      prologue();
+      rs = 0;
+      ws = NS - 1;
     }
-    if (group == 0) {
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_barrier" : : : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else if constexpr (NPL == 3 && TFK_X3_M16 != 0) {
-    // The 16x16x32 shape: a ring slot is ONE 32-k step of six plane products x FM16 x FN16 MFMAs.  The products run (0,0) (0,1)
-    // (0,2) | barrier | (1,0) (1,1) (2,0): every fragment register is read for the last time as early as possible, so one set of
-    // fragments (+ a second B plane 0) serves -- A1 and A2 of this slot are fetched under the first half, A0, B0, B2, B1 of the
-    // NEXT slot under the second, each into registers whose last use lies behind it.  The barrier sits where it sat (round 3):
-    // every read of this slot has been issued in front of it, the next slot's data is complete behind it.
-    static_assert(KSPT == 2, "fp32-emulating contraction: 32 k per ring slot");
-    constexpr int FM16 = 2 * FM, FN16 = 2 * FN;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    Frag3M<A_KC, BM, FM16> ma;
-    Frag3M<B_KC, BN, FN16> mb;
-    ma.init(lane, wm * FM16);
-    mb.init(lane, wn * FN16);
-    f32x4 c1[FM16][FN16], c2[FM16][FN16];
-#pragma unroll
-    for (int a = 0; a < FM16; ++a)
-#pragma unroll
-      for (int b = 0; b < FN16; ++b) {
-        c1[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        c2[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc();
+    const bool chain_next = CHAIN && nk >= NS && ti + 1 < nlist;
+    const int tm_out = tm, m0_out = m0, n0_out = n0;  // (a chained list moves tm, m0, n0 on to the next tile inside the K loop)
+    if constexpr (SCHED == 2) {
+      // Half-steps are numbered by the barriers between them.  Waves 0 .. 3 (group 0, one per SIMD): LOAD(0) | MUL(0) | LOAD(1) | ..;
+      // waves 4 .. 7 (group 1, their SIMD partners): idle | LOAD(0) | MUL(0) | ..  LOAD(t) reads every fragment of slot t into
+      // registers, issues the wave's pieces of tile t+NS-1 into the slot tile t-1 occupied (its last reader, the other group,
+      // finished one half-step earlier) and waits for its own pieces of tile t+1; MUL(t) is KSPT * FM * FN MFMAs and nothing else.
+      static_assert(WAVES_M * WAVES_N == 8, "two waves per SIMD");
+      const int group = wave >> 2;
+      bf16x8 wa[KSPT][FM], wb[KSPT][FN];
+      if (group == 1) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_barrier" : : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
       }
-    bf16x8 ga[3][FM16], gb[3][FN16], gb0n[FN16];
-    auto rd_a = [&](const decltype(ma)& r, int pl) {
+#pragma unroll 1
+      for (int kt = 0; kt < nk; ++kt) {
+        const char* st = smem + rs * STAGE;
 #pragma unroll
-      for (int a = 0; a < FM16; ++a) ga[pl][a] = r.read(smem, a, pl);
-    };
-    auto rd_b = [&](const decltype(mb)& r, int pl, bf16x8 (&dst)[FN16]) {
+        for (int ks = 0; ks < KSPT; ++ks) {
 #pragma unroll
-      for (int b = 0; b < FN16; ++b) dst[b] = r.read(smem, b, pl);
-    };
-    auto mm = [&](int pa, int pb) {
+          for (int a = 0; a < FM; ++a) wa[ks][a] = qa.read(st, a, ks);
+#pragma unroll
+          for (int b = 0; b < FN; ++b) wb[ks][b] = qb.read(st + A_BYTES, b, ks);
+        }
+#pragma unroll
+        for (int j = 0; j < NP; ++j) piece(j, ws, kt + NS - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        TFKB_WAIT_BARRIER((NS - 2) * NP);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < KSPT; ++ks)
+#pragma unroll
+          for (int a = 0; a < FM; ++a)
+#pragma unroll
+            for (int b = 0; b < FN; ++b)
+              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][a], wb[ks][b], acc[a][b], 0, 0, 0);
+        rs = rs + 1 == NS ? 0 : rs + 1;
+        ws = ws + 1 == NS ? 0 : ws + 1;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_barrier" : : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (group == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_barrier" : : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else if constexpr (NPL == 3 && TFK_X3_M16 != 0) {
+      // The 16x16x32 shape: a ring slot is ONE 32-k step of six plane products x FM16 x FN16 MFMAs.  The products run (0,0) (0,1)
+      // (0,2) | barrier | (1,0) (1,1) (2,0): every fragment register is read for the last time as early as possible, so one set of
+      // fragments (+ a second B plane 0) serves -- A1 and A2 of this slot are fetched under the first half, A0, B0, B2, B1 of the
+      // NEXT slot under the second, each into registers whose last use lies behind it.  The barrier sits where it sat (round 3):
+      // every read of this slot has been issued in front of it, the next slot's data is complete behind it.
+      static_assert(KSPT == 2, "fp32-emulating contraction: 32 k per ring slot");
+      constexpr int FM16 = 2 * FM, FN16 = 2 * FN;
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+      Frag3M<A_KC, BM, FM16> ma;
+      Frag3M<B_KC, BN, FN16> mb;
+      ma.init(lane, wm * FM16);
+      mb.init(lane, wn * FN16);
+      f32x4 c1[FM16][FN16], c2[FM16][FN16];
 #pragma unroll
       for (int a = 0; a < FM16; ++a)
 #pragma unroll
         for (int b = 0; b < FN16; ++b) {
-          if (pa + pb == 0) c1[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[0][a], gb[0][b], c1[a][b], 0, 0, 0);
-          else c2[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[pa][a], gb[pb][b], c2[a][b], 0, 0, 0);
+          c1[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+          c2[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    // third `part` of the pieces [j0, j1) of tile `tile` into slot `slot`
-    auto pieces = [&](auto guard, int part, int j0, int j1, int slot, int tile) {
+      bf16x8 ga[3][FM16], gb[3][FN16], gb0n[FN16];
+      auto rd_a = [&](const decltype(ma)& r, int pl) {
 #pragma unroll
-      for (int j = j0 + part * (j1 - j0) / 3; j < j0 + (part + 1) * (j1 - j0) / 3; ++j) piece_g(guard, j, slot, tile);
-    };
-    {
-      const auto r0a = ma.at(0);
-      const auto r0b = mb.at(NPL * A_BYTES);
-      rd_a(r0a, 0);
-      rd_b(r0b, 0, gb[0]);
-      rd_b(r0b, 1, gb[1]);
-      rd_b(r0b, 2, gb[2]);
-    }
-    const int n_fast = max(0, min(nk, nk_full - NS));
-    auto iteration = [&](auto guard, int kt) {
-      const auto ra = ma.at(rs * STAGE);
-      rd_a(ra, 1);
-      pieces(guard, 0, NPH, NP, ws, kt + NS - 1);
-      mm(0, 0);
-      rd_a(ra, 2);
-      pieces(guard, 1, NPH, NP, ws, kt + NS - 1);
-      mm(0, 1);
-      pieces(guard, 2, NPH, NP, ws, kt + NS - 1);
-      mm(0, 2);
+        for (int a = 0; a < FM16; ++a) ga[pl][a] = r.read(smem, a, pl);
+      };
+      auto rd_b = [&](const decltype(mb)& r, int pl, bf16x8 (&dst)[FN16]) {
+#pragma unroll
+        for (int b = 0; b < FN16; ++b) dst[b] = r.read(smem, b, pl);
+      };
+      auto mm = [&](int pa, int pb) {
+#pragma unroll
+        for (int a = 0; a < FM16; ++a)
+#pragma unroll
+          for (int b = 0; b < FN16; ++b) {
+            if (pa + pb == 0) c1[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[0][a], gb[0][b], c1[a][b], 0, 0, 0);
+            else c2[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[pa][a], gb[pb][b], c2[a][b], 0, 0, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      // third `part` of the pieces [j0, j1) of tile `tile` into slot `slot`
+      auto pieces = [&](auto guard, int part, int j0, int j1, int slot, int tile) {
+#pragma unroll
+        for (int j = j0 + part * (j1 - j0) / 3; j < j0 + (part + 1) * (j1 - j0) / 3; ++j) piece_g(guard, j, slot, tile);
+      };
+      {
+        const auto r0a = ma.at(0);
+        const auto r0b = mb.at(NPL * A_BYTES);
+        rd_a(r0a, 0);
+        rd_b(r0b, 0, gb[0]);
+        rd_b(r0b, 1, gb[1]);
+        rd_b(r0b, 2, gb[2]);
+      }
+      const int n_fast = max(0, min(nk, nk_full - NS));
+      auto iteration = [&](auto guard, int kt) {
+        const auto ra = ma.at(rs * STAGE);
+        rd_a(ra, 1);
+        pieces(guard, 0, NPH, NP, ws, kt + NS - 1);
+        mm(0, 0);
+        rd_a(ra, 2);
+        pieces(guard, 1, NPH, NP, ws, kt + NS - 1);
+        mm(0, 1);
+        pieces(guard, 2, NPH, NP, ws, kt + NS - 1);
+        mm(0, 2);
+        TFKB_WAIT_BARRIER((NS - 2) * NP);
+        rs = rs + 1 == NS ? 0 : rs + 1;
+        ws = ws + 1 == NS ? 0 : ws + 1;
+        const bool fetch = kt + 1 < nk;
+        const auto na = ma.at(rs * STAGE);
+        const auto nb = mb.at(rs * STAGE + NPL * A_BYTES);
+        if (fetch) {
+          rd_a(na, 0);
+          rd_b(nb, 0, gb0n);
+        }
+        pieces(guard, 0, 0, NPH, ws, kt + NS);
+        mm(1, 0);
+        if (fetch) rd_b(nb, 2, gb[2]);
+        pieces(guard, 1, 0, NPH, ws, kt + NS);
+        mm(1, 1);
+        if (fetch) rd_b(nb, 1, gb[1]);
+        pieces(guard, 2, 0, NPH, ws, kt + NS);
+        mm(2, 0);
+        if (fetch) {
+#pragma unroll
+          for (int b = 0; b < FN16; ++b) gb[0][b] = gb0n[b];
+        }
+      };
+#pragma unroll 1
+      for (int kt = 0; kt < n_fast; ++kt) iteration(std::false_type(), kt);
+#pragma unroll 1
+      for (int kt = n_fast; kt < nk; ++kt) iteration(std::true_type(), kt);
+      // the 16x16 result tiles -> the 32x32 register layout the epilogues are written for: reg r of lane (i, h) is row
+      // 4 h + (r & 3) + 8 (r >> 2), column i of a 32x32 fragment; 16x16 tile (p, q) of it holds row 16 p + 4 (l >> 4) + s, column
+      // 16 q + (l & 15) in reg s of lane l.  One ds_bpermute per (register, column half), once per block.
+      {
+        const int src = (16 * h + (i & 15)) * 4;  // + 128 for the registers with (r >> 2) & 1
+#pragma unroll
+        for (int a = 0; a < FM; ++a)
+#pragma unroll
+          for (int b = 0; b < FN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int addr = src + (((r >> 2) & 1) ? 128 : 0);
+              const f32x4& t0 = c1[2 * a + (r >> 3)][2 * b], &u0 = c2[2 * a + (r >> 3)][2 * b];
+              const f32x4& t1 = c1[2 * a + (r >> 3)][2 * b + 1], &u1 = c2[2 * a + (r >> 3)][2 * b + 1];
+              const float v0 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t0[r & 3] + u0[r & 3])));
+              const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t1[r & 3] + u1[r & 3])));
+              acc[a][b][r] = (i & 16) ? v1 : v0;
+            }
+      }
+    } else if constexpr (NPL == 3) {
+      // One wave per SIMD, and per 16-k step 6 * FM * FN MFMAs for 3 * (FM + FN) fragment reads and a handful of LDS-DMA pieces:
+      // issued in bursts (every read, then every piece, then the MFMAs -- the bf16 loop below) the wave sits in the LDS / vector
+      // memory issue queues while the matrix pipe runs dry (tools/gemm_f32x3_ablate.hip: MFMAs alone 31 us, with the pieces 50,
+      // with everything 61 at 1024 x 2048 x 2048).  Here every step is SIX groups, one per plane product: a share of the next
+      // step's fragment reads (in the order of their first use; the last three groups read nothing, so the reads have three
+      // groups of MFMAs to land), a share of the pieces, then the product's FM * FN MFMAs.  A tile's pieces are spread over BOTH
+      // half-steps between two barriers: the half-step after barrier kt sends the first half of tile kt+NS into the slot tile
+      // kt just left, the half-step in front of the next barrier the second half.
+      static_assert(KSPT == 2, "fp32-emulating contraction: 32 k per ring slot");
+      // (ordering the last three products so that consecutive MFMAs share an operand plane -- (0,1) (0,0) (1,0) -- changes
+      // nothing: 94.7 / 98.4 us against 102.9 / 97.7 for the pair of a layer, run to run)
+      constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+      // Addresses: the fragment offsets of the slot being read are advanced ONCE per slot (four additions); every read is then
+      // `offset register + immediate`.  The k-range guard of the pieces is peeled: all iterations but the last NS + 1 of a block
+      // issue tiles that lie wholly inside K.
+      auto step3 = [&](auto guard, int cur, bool fetch, const decltype(qa)& ra, const decltype(qb)& rb, int nks, int j0, int j1,
+                       int slot, int tile) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          if (c < 3 && fetch && !(TFKB_ABL & 4)) {
+#pragma unroll
+            for (int a = 0; a < FM; ++a) fa[cur ^ 1][PA[c]][a] = ra.read(smem, a, nks, PA[c]);
+#pragma unroll
+            for (int b = 0; b < FN; ++b) fb[cur ^ 1][PB[c]][b] = rb.read(smem, b, nks, PB[c]);
+          }
+#pragma unroll
+          for (int j = j0 + c * (j1 - j0) / 6; j < j0 + (c + 1) * (j1 - j0) / 6; ++j) piece_g(guard, j, slot, tile);
+          if (TFKB_ABL & 1) {
+#pragma unroll
+            for (int a = 0; a < FM; ++a) asm volatile("" : : "v"(fa[cur][PA[c]][a]));
+#pragma unroll
+            for (int b = 0; b < FN; ++b) asm volatile("" : : "v"(fb[cur][PB[c]][b]));
+          } else {
+#pragma unroll
+            for (int a = 0; a < FM; ++a)
+#pragma unroll
+              for (int b = 0; b < FN; ++b) {
+                if (c < 5)
+                  acc2[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][PA[c]][a], fb[cur][PB[c]][b], acc2[a][b], 0, 0, 0);
+                else
+                  acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][PA[c]][a], fb[cur][PB[c]][b], acc[a][b], 0, 0, 0);
+              }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if (!primed) read_frags(0, smem, 0);
+      const int n_fast = max(0, min(nk, nk_full - NS));
+      // t1 / t2: the ring tiles whose second / first half of pieces go out in front of / behind the barrier; `switch_tile`: the
+      // boundary iteration of a chained list (t2 is the next tile's ring tile 0: its loaders take over behind the barrier)
+      auto iteration = [&](auto guard, int t1, int t2, bool fetch, bool switch_tile) {
+        const auto ra = qa.at(rs * STAGE);
+        const auto rb = qb.at(rs * STAGE + NPL * A_BYTES);
+        step3(guard, 0, true, ra, rb, 1, NPH, NP, ws, t1);
+        TFKB_WAIT_BARRIER((NS - 2) * NP);
+        rs = rs + 1 == NS ? 0 : rs + 1;
+        ws = ws + 1 == NS ? 0 : ws + 1;
+        if constexpr (CHAIN) {
+          if (switch_tile) {
+            tile_of_seq(tiles_m, tiles_n, group_rows, seq0 + ti + 1, tm, tn);
+            m0 = tm * BM;
+            n0 = tn * BN;
+            init_loaders();
+          }
+        }
+        const auto na = qa.at(rs * STAGE);
+        const auto nb = qb.at(rs * STAGE + NPL * A_BYTES);
+        step3(guard, 1, fetch, na, nb, 0, 0, NPH, ws, t2);
+      };
+      // (a chained list: iterations [nk - NS, nk) issue the next tile's ring tiles 0 .. NS - 1, the last of them by half)
+      const int n_own = chain_next ? nk - NS : nk;
+      TFKB_TL(1, ti);
+#pragma unroll 1
+      for (int kt = 0; kt < n_fast; ++kt) iteration(std::false_type(), kt + NS - 1, kt + NS, kt + 1 < nk, false);
+#pragma unroll 1
+      for (int kt = n_fast; kt < n_own; ++kt) iteration(std::true_type(), kt + NS - 1, kt + NS, kt + 1 < nk, false);
+      if constexpr (CHAIN) {
+        if (chain_next) {
+          iteration(std::true_type(), nk - 1, 0, true, true);
+#pragma unroll 1
+          for (int t = 0; t < NS - 1; ++t) iteration(std::true_type(), t, t + 1, true, false);
+        }
+      }
+      TFKB_TL(2, ti);
+    } else {
+    read_frags(0, smem, 0);
+#pragma unroll 1
+    for (int kt = 0; kt < nk; ++kt) {
+      const char* st = smem + rs * STAGE;
+#pragma unroll
+      for (int ks = 0; ks < KSPT - 1; ++ks) {
+        const int cur = ks & 1;
+        read_frags(cur ^ 1, st, ks + 1);
+        // this step's share of the pieces of tile kt+NS-1 (into the slot tile kt-1 left at the last barrier); all of them go
+        // out BEFORE the barrier, so that every piece keeps between one and two tile times to land
+#pragma unroll
+        for (int j = ks * NP / (KSPT - 1); j < (ks + 1) * NP / (KSPT - 1); ++j) piece(j, ws, kt + NS - 1);
+        mfma_step(cur);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // every fragment read of tile kt is complete (lgkmcnt(0)), this wave's pieces of tile kt+1 have landed (the NS-2
+      // younger tiles stay in flight); the barrier makes every wave's pieces visible and frees tile kt's slot
       TFKB_WAIT_BARRIER((NS - 2) * NP);
       rs = rs + 1 == NS ? 0 : rs + 1;
       ws = ws + 1 == NS ? 0 : ws + 1;
-      const bool fetch = kt + 1 < nk;
-      const auto na = ma.at(rs * STAGE);
-      const auto nb = mb.at(rs * STAGE + NPL * A_BYTES);
-      if (fetch) {
-        rd_a(na, 0);
-        rd_b(nb, 0, gb0n);
-      }
-      pieces(guard, 0, 0, NPH, ws, kt + NS);
-      mm(1, 0);
-      if (fetch) rd_b(nb, 2, gb[2]);
-      pieces(guard, 1, 0, NPH, ws, kt + NS);
-      mm(1, 1);
-      if (fetch) rd_b(nb, 1, gb[1]);
-      pieces(guard, 2, 0, NPH, ws, kt + NS);
-      mm(2, 0);
-      if (fetch) {
-#pragma unroll
-        for (int b = 0; b < FN16; ++b) gb[0][b] = gb0n[b];
-      }
-    };
-#pragma unroll 1
-    for (int kt = 0; kt < n_fast; ++kt) iteration(std::false_type(), kt);
-#pragma unroll 1
-    for (int kt = n_fast; kt < nk; ++kt) iteration(std::true_type(), kt);
-    // the 16x16 result tiles -> the 32x32 register layout the epilogues are written for: reg r of lane (i, h) is row
-    // 4 h + (r & 3) + 8 (r >> 2), column i of a 32x32 fragment; 16x16 tile (p, q) of it holds row 16 p + 4 (l >> 4) + s, column
-    // 16 q + (l & 15) in reg s of lane l.  One ds_bpermute per (register, column half), once per block.
-    {
-      const int src = (16 * h + (i & 15)) * 4;  // + 128 for the registers with (r >> 2) & 1
+      if (kt + 1 < nk) read_frags(0, smem + rs * STAGE, 0);
+      mfma_step((KSPT - 1) & 1);  // the last 16-k step of tile kt
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    }
+    // the epilogue reuses the ring as scratch: nothing may still be landing in it (a chained list: `red` lies behind the ring)
+    if (!chain_next) TFKB_WAIT_BARRIER(0);
+    if constexpr (NPL == 3) {
 #pragma unroll
       for (int a = 0; a < FM; ++a)
 #pragma unroll
         for (int b = 0; b < FN; ++b)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int addr = src + (((r >> 2) & 1) ? 128 : 0);
-            const f32x4& t0 = c1[2 * a + (r >> 3)][2 * b], &u0 = c2[2 * a + (r >> 3)][2 * b];
-            const f32x4& t1 = c1[2 * a + (r >> 3)][2 * b + 1], &u1 = c2[2 * a + (r >> 3)][2 * b + 1];
-            const float v0 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t0[r & 3] + u0[r & 3])));
-            const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t1[r & 3] + u1[r & 3])));
-            acc[a][b][r] = (i & 16) ? v1 : v0;
-          }
+          for (int r = 0; r < 16; ++r) acc[a][b][r] += acc2[a][b][r];
     }
-  } else if constexpr (NPL == 3) {
-    // One wave per SIMD, and per 16-k step 6 * FM * FN MFMAs for 3 * (FM + FN) fragment reads and a handful of LDS-DMA pieces:
-    // issued in bursts (every read, then every piece, then the MFMAs -- the bf16 loop below) the wave sits in the LDS / vector
-    // memory issue queues while the matrix pipe runs dry (tools/gemm_f32x3_ablate.hip: MFMAs alone 31 us, with the pieces 50,
-    // with everything 61 at 1024 x 2048 x 2048).  Here every step is SIX groups, one per plane product: a share of the next
-    // step's fragment reads (in the order of their first use; the last three groups read nothing, so the reads have three
-    // groups of MFMAs to land), a share of the pieces, then the product's FM * FN MFMAs.  A tile's pieces are spread over BOTH
-    // half-steps between two barriers: the half-step after barrier kt sends the first half of tile kt+NS into the slot tile
-    // kt just left, the half-step in front of the next barrier the second half.
-    static_assert(KSPT == 2, "fp32-emulating contraction: 32 k per ring slot");
-    // (ordering the last three products so that consecutive MFMAs share an operand plane -- (0,1) (0,0) (1,0) -- changes
-    // nothing: 94.7 / 98.4 us against 102.9 / 97.7 for the pair of a layer, run to run)
-    constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-    // Addresses: the fragment offsets of the slot being read are advanced ONCE per slot (four additions); every read is then
-    // `offset register + immediate`.  The k-range guard of the pieces is peeled: all iterations but the last NS + 1 of a block
-    // issue tiles that lie wholly inside K.
-    auto step3 = [&](auto guard, int cur, bool fetch, const decltype(qa)& ra, const decltype(qb)& rb, int nks, int j0, int j1,
-                     int slot, int tile) {
+    if constexpr (KSPLIT == 2) {
+      // The two halves of the tile meet: whoever takes the ticket first stores its partial sums (lane-linear 16-byte pieces) and
+      // raises `ready`; the other waits for that, adds them to its own and goes on to the epilogue.  The first block has its
+      // ticket before the second one can wait for it and never waits itself: no deadlock whatever order the blocks start in.
+      // Coherence by hand: the partial sums travel with sc0 sc1 (written through / read past every cache), the flag words by
+      // agent-scope atomics, and the stores are acknowledged (vmcnt 0, then the block's barrier) before `ready` goes up.  The
+      // fences of the memory model (`buffer_wbl2` / `buffer_inv sc1`) would write back and drop a whole L2 per wave instead --
+      // measured: 87 us instead of 52 for the contraction.
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+      unsigned* flags = reinterpret_cast<unsigned*>(p.splitk_ws);
+      const int tile = tm * tiles_n + tn;
+      constexpr int kSys = 1 | (1 << 4);  // sc0 sc1 (agent scope -- sc1 alone -- measured the same)
+      __amdgpu_buffer_rsrc_t part = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(p.splitk_ws + kSplitFlagWords + (size_t)tile * (BM * BN)), 0, BM * BN * 4, 0x00020000);
+      unsigned* sh = reinterpret_cast<unsigned*>(smem);
+      if (tid == 0) {
+        sh[0] = __hip_atomic_fetch_add(&flags[2 * tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the partner has said where it runs if it has started at all (it has, unless the two are not co-resident)
+        sh[1] = p.splitk_local ? __hip_atomic_load(&flags[kSplitXccWord + 2 * tile + (khalf ^ 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                               : 0u;
+      }
+      __syncthreads();
+      const bool first = sh[0] == 0;
+      if (first) {
+        // Same XCD: the sums stay in the L2 both blocks share (plain stores keep the line there; the partner's sc0 sc1 loads are
+        // served by that L2) -- no trip through the fabric and back.  Anywhere else, or unknown: written through (sc0 sc1).
+        const bool same_xcd = p.splitk_local && sh[1] == my_xcc + 1;
+        if (same_xcd) {
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        if (c < 3 && fetch && !(TFKB_ABL & 4)) {
+          for (int a = 0; a < FM; ++a)
 #pragma unroll
-          for (int a = 0; a < FM; ++a) fa[cur ^ 1][PA[c]][a] = ra.read(smem, a, nks, PA[c]);
+            for (int b = 0; b < FN; ++b)
 #pragma unroll
-          for (int b = 0; b < FN; ++b) fb[cur ^ 1][PB[c]][b] = rb.read(smem, b, nks, PB[c]);
-        }
-#pragma unroll
-        for (int j = j0 + c * (j1 - j0) / 6; j < j0 + (c + 1) * (j1 - j0) / 6; ++j) piece_g(guard, j, slot, tile);
-        if (TFKB_ABL & 1) {
-#pragma unroll
-          for (int a = 0; a < FM; ++a) asm volatile("" : : "v"(fa[cur][PA[c]][a]));
-#pragma unroll
-          for (int b = 0; b < FN; ++b) asm volatile("" : : "v"(fb[cur][PB[c]][b]));
+              for (int q = 0; q < 4; ++q)
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    __builtin_bit_cast(u32x4, f32x4{acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]}),
+                    part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, 0);
         } else {
 #pragma unroll
           for (int a = 0; a < FM; ++a)
 #pragma unroll
-            for (int b = 0; b < FN; ++b) {
-              if (c < 5)
-                acc2[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][PA[c]][a], fb[cur][PB[c]][b], acc2[a][b], 0, 0, 0);
-              else
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur][PA[c]][a], fb[cur][PB[c]][b], acc[a][b], 0, 0, 0);
-            }
+            for (int b = 0; b < FN; ++b)
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    __builtin_bit_cast(u32x4, f32x4{acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]}),
+                    part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, kSys);
         }
-        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(&flags[2 * tile + 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
       }
-    };
-    read_frags(0, smem, 0);
-    const int n_fast = max(0, min(nk, nk_full - NS));
-    auto iteration = [&](auto guard, int kt) {
-      const auto ra = qa.at(rs * STAGE);
-      const auto rb = qb.at(rs * STAGE + NPL * A_BYTES);
-      step3(guard, 0, true, ra, rb, 1, NPH, NP, ws, kt + NS - 1);
-      TFKB_WAIT_BARRIER((NS - 2) * NP);
-      rs = rs + 1 == NS ? 0 : rs + 1;
-      ws = ws + 1 == NS ? 0 : ws + 1;
-      const auto na = qa.at(rs * STAGE);
-      const auto nb = qb.at(rs * STAGE + NPL * A_BYTES);
-      step3(guard, 1, kt + 1 < nk, na, nb, 0, 0, NPH, ws, kt + NS);
-    };
-#pragma unroll 1
-    for (int kt = 0; kt < n_fast; ++kt) iteration(std::false_type(), kt);
-#pragma unroll 1
-    for (int kt = n_fast; kt < nk; ++kt) iteration(std::true_type(), kt);
-  } else {
-  read_frags(0, smem, 0);
-#pragma unroll 1
-  for (int kt = 0; kt < nk; ++kt) {
-    const char* st = smem + rs * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < KSPT - 1; ++ks) {
-      const int cur = ks & 1;
-      read_frags(cur ^ 1, st, ks + 1);
-      // this step's share of the pieces of tile kt+NS-1 (into the slot tile kt-1 left at the last barrier); all of them go
-      // out BEFORE the barrier, so that every piece keeps between one and two tile times to land
-#pragma unroll
-      for (int j = ks * NP / (KSPT - 1); j < (ks + 1) * NP / (KSPT - 1); ++j) piece(j, ws, kt + NS - 1);
-      mfma_step(cur);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // every fragment read of tile kt is complete (lgkmcnt(0)), this wave's pieces of tile kt+1 have landed (the NS-2
-    // younger tiles stay in flight); the barrier makes every wave's pieces visible and frees tile kt's slot
-    TFKB_WAIT_BARRIER((NS - 2) * NP);
-    rs = rs + 1 == NS ? 0 : rs + 1;
-    ws = ws + 1 == NS ? 0 : ws + 1;
-    if (kt + 1 < nk) read_frags(0, smem + rs * STAGE, 0);
-    mfma_step((KSPT - 1) & 1);  // the last 16-k step of tile kt
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  }
-  TFKB_WAIT_BARRIER(0);  // the epilogue reuses the ring as scratch: nothing may still be landing in it
-  if constexpr (NPL == 3) {
-#pragma unroll
-    for (int a = 0; a < FM; ++a)
-#pragma unroll
-      for (int b = 0; b < FN; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] += acc2[a][b][r];
-  }
-  if constexpr (KSPLIT == 2) {
-    // The two halves of the tile meet: whoever takes the ticket first stores its partial sums (lane-linear 16-byte pieces) and
-    // raises `ready`; the other waits for that, adds them to its own and goes on to the epilogue.  The first block has its
-    // ticket before the second one can wait for it and never waits itself: no deadlock whatever order the blocks start in.
-    // Coherence by hand: the partial sums travel with sc0 sc1 (written through / read past every cache), the flag words by
-    // agent-scope atomics, and the stores are acknowledged (vmcnt 0, then the block's barrier) before `ready` goes up.  The
-    // fences of the memory model (`buffer_wbl2` / `buffer_inv sc1`) would write back and drop a whole L2 per wave instead --
-    // measured: 87 us instead of 52 for the contraction.
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    unsigned* flags = reinterpret_cast<unsigned*>(p.splitk_ws);
-    const int tile = tm * tiles_n + tn;
-    constexpr int kSys = 1 | (1 << 4);  // sc0 sc1 (agent scope -- sc1 alone -- measured the same)
-    __amdgpu_buffer_rsrc_t part = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.splitk_ws + kSplitFlagWords + (size_t)tile * (BM * BN)), 0, BM * BN * 4, 0x00020000);
-    unsigned* sh = reinterpret_cast<unsigned*>(smem);
-    if (tid == 0) {
-      sh[0] = __hip_atomic_fetch_add(&flags[2 * tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // the partner has said where it runs if it has started at all (it has, unless the two are not co-resident)
-      sh[1] = p.splitk_local ? __hip_atomic_load(&flags[kSplitXccWord + 2 * tile + (khalf ^ 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : 0u;
-    }
-    __syncthreads();
-    const bool first = sh[0] == 0;
-    if (first) {
-      // Same XCD: the sums stay in the L2 both blocks share (plain stores keep the line there; the partner's sc0 sc1 loads are
-      // served by that L2) -- no trip through the fabric and back.  Anywhere else, or unknown: written through (sc0 sc1).
-      const bool same_xcd = p.splitk_local && sh[1] == my_xcc + 1;
-      if (same_xcd) {
-#pragma unroll
-        for (int a = 0; a < FM; ++a)
-#pragma unroll
-          for (int b = 0; b < FN; ++b)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              __builtin_amdgcn_raw_buffer_store_b128(
-                  __builtin_bit_cast(u32x4, f32x4{acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]}),
-                  part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, 0);
-      } else {
-#pragma unroll
-        for (int a = 0; a < FM; ++a)
-#pragma unroll
-          for (int b = 0; b < FN; ++b)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              __builtin_amdgcn_raw_buffer_store_b128(
-                  __builtin_bit_cast(u32x4, f32x4{acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]}),
-                  part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, kSys);
+      if (tid == 0) {
+        // (the bound -- about a second -- only keeps a broken workspace from hanging the device: the partner holds its
+        // ticket, so it is running and a few microseconds from its store)
+        int spin = 0;
+        for (; spin < (1 << 23) && __hip_atomic_load(&flags[2 * tile + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0; ++spin)
+          __builtin_amdgcn_s_sleep(2);
+        // timed out: what this block is about to add is not the partner's sum.  Say so where the host will look before it
+        // hands out anything computed from this launch (round 4 carried on silently).
+        if (spin == (1 << 23) && p.err) __hip_atomic_store(p.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // (both words back to zero for the next launch: the other block is past them)
+        __hip_atomic_store(&flags[2 * tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&flags[2 * tile + 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&flags[kSplitXccWord + 2 * tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&flags[kSplitXccWord + 2 * tile + 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
       __syncthreads();
-      if (tid == 0) __hip_atomic_store(&flags[2 * tile + 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
+#pragma unroll
+      for (int a = 0; a < FM; ++a)
+#pragma unroll
+        for (int b = 0; b < FN; ++b)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 o = __builtin_bit_cast(
+                f32x4, __builtin_amdgcn_raw_buffer_load_b128(part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, kSys));
+            acc[a][b][4 * q] += o.x;
+            acc[a][b][4 * q + 1] += o.y;
+            acc[a][b][4 * q + 2] += o.z;
+            acc[a][b][4 * q + 3] += o.w;
+          }
+      __syncthreads();  // (the epilogue reuses smem)
     }
-    if (tid == 0) {
-      // (the bound -- about a second -- only keeps a broken workspace from hanging the device: the partner holds its
-      // ticket, so it is running and a few microseconds from its store)
-      int spin = 0;
-      for (; spin < (1 << 23) && __hip_atomic_load(&flags[2 * tile + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0; ++spin)
-        __builtin_amdgcn_s_sleep(2);
-      // timed out: what this block is about to add is not the partner's sum.  Say so where the host will look before it
-      // hands out anything computed from this launch (round 4 carried on silently).
-      if (spin == (1 << 23) && p.err) __hip_atomic_store(p.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      // (both words back to zero for the next launch: the other block is past them)
-      __hip_atomic_store(&flags[2 * tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&flags[2 * tile + 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&flags[kSplitXccWord + 2 * tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&flags[kSplitXccWord + 2 * tile + 1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    epilogue<EPI, WAVES_M, WAVES_N, FM, FN, CBUF>(p, acc, tiles_m, tm_out, m0_out, n0_out, wm, wn, i, h, red);
+    TFKB_TL(3, ti);
+    if constexpr (LIST) {
+      primed = chain_next;
+      // (no chain: the next tile's prologue overwrites what this epilogue may still be reading from the ring)
+      if (!chain_next && ti + 1 < nlist) __syncthreads();
     }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < FM; ++a)
-#pragma unroll
-      for (int b = 0; b < FN; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 o = __builtin_bit_cast(
-              f32x4, __builtin_amdgcn_raw_buffer_load_b128(part, ((((wave * FM + a) * FN + b) * 4 + q) * 64 + lane) * 16, 0, kSys));
-          acc[a][b][4 * q] += o.x;
-          acc[a][b][4 * q + 1] += o.y;
-          acc[a][b][4 * q + 2] += o.z;
-          acc[a][b][4 * q + 3] += o.w;
-        }
-    __syncthreads();  // (the epilogue reuses smem)
   }
-  epilogue<EPI, WAVES_M, WAVES_N, FM, FN>(p, acc, tiles_m, tm, m0, n0, wm, wn, i, h, reinterpret_cast<float*>(smem));
 }
 
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
@@ -1276,22 +1384,38 @@ gemm_bf16_kernel(GemmArgsB p, int tiles_m, int tiles_n, int group_rows) {
 // dA tile (64 ring tiles) or two dW tiles (32 each): no partial-sum exchange, one ramp and one tail instead of two.
 // WN: waves along n -- 2 (four waves of 64x64), 4 (EIGHT waves of 64x32, two per SIMD) or 0 (four waves of 64x64 + four loader
 // waves): see launch_x3
+// per: tiles per block of the problem with the SHORTER K (x3_layout.h: dual_tiles_per_block) -- at 1024 frames 128 dA blocks of
+// 64 ring tiles and 128 blocks of two dW tiles (2 x 32), one block per CU, the ring running on from a block's first tile into
+// its second (dma_tile: LIST).  The form with loader waves keeps one tile per block (per = 1: its loader waves end with the K
+// loop).
 template <int EPI_NT, int EPI_TN, int WN>
 __global__ void __launch_bounds__(WN == 2 ? 256 : 512)
 gemm_bf16x3_dual_kernel(GemmArgsB p1, GemmArgsB p2, int tiles_m1, int tiles_n1, int group1, int tiles_m2, int tiles_n2, int group2,
-                        int tn_first) {
+                        int tn_first, int per) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // the tiles with the longer K go first in block order (dA at 1024 frames: K = d_out against K = frames; dW in a stacked pass
   // of 8192 rows): the short ones fill the tail
   const int n1 = tiles_m1 * tiles_n1, n2 = tiles_m2 * tiles_n2;
   const int b = blockIdx.x;
-  const bool nt = tn_first ? b >= n2 : b < n1;
-  if (nt)
-    dma_tile<true, true, EPI_NT, 2, WN ? WN : 2, 2, WN ? 4 / WN : 2, 3, 32, 0, 3, 1, WN ? 0 : 4>(p1, tiles_m1, tiles_n1, group1,
-                                                                                              tn_first ? b - n2 : b, smem);
+  constexpr bool LIST = WN != 0;
+  constexpr int WNN = WN ? WN : 2, FNN = WN ? 4 / WN : 2, LD = WN ? 0 : 4;
+  const int n_long = tn_first ? n2 : n1;
+  if (b < n_long) {  // one tile of the long problem
+    if (tn_first) dma_tile<false, false, EPI_TN, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, false, true>(p2, tiles_m2, tiles_n2, group2, b, smem);
+    else dma_tile<true, true, EPI_NT, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, false, true>(p1, tiles_m1, tiles_n1, group1, b, smem);
+    return;
+  }
+  int seq0 = 0, count = 1;
+  if constexpr (LIST) {
+    x3::dual_block_tiles(tn_first ? n1 : n2, per, b - n_long, seq0, count);
+    if (count == 0) return;
+  }
+  if (tn_first)
+    dma_tile<true, true, EPI_NT, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, LIST, true>(p1, tiles_m1, tiles_n1, group1, b - n_long, smem, seq0,
+                                                                                 count);
   else
-    dma_tile<false, false, EPI_TN, 2, WN ? WN : 2, 2, WN ? 4 / WN : 2, 3, 32, 0, 3, 1, WN ? 0 : 4>(p2, tiles_m2, tiles_n2, group2,
-                                                                                                tn_first ? b : b - n1, smem);
+    dma_tile<false, false, EPI_TN, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, LIST, true>(p2, tiles_m2, tiles_n2, group2, b - n_long, smem, seq0,
+                                                                                  count);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -1576,7 +1700,8 @@ size_t gemm_bf16x3_splitk_floats(GemmLayout layout, int M, int N, int K) {
 namespace {
 template <int EPI_NT, int EPI_TN, int WN>
 int launch_x3_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
-  constexpr size_t lds = (size_t)3 * 3 * (128 + 128) * 32 * 2;
+  // three ring slots + the epilogues' column-sum scratch behind them (a tile list's epilogue runs while the ring is being filled)
+  constexpr size_t lds = (size_t)3 * 3 * (128 + 128) * 32 * 2 + 2 * 2 * 128 * sizeof(float);
   auto kern = &gemm_bf16x3_dual_kernel<EPI_NT, EPI_TN, WN>;
   static bool attr_done = false;
   if (!attr_done) {
@@ -1585,8 +1710,13 @@ int launch_x3_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
     attr_done = true;
   }
   const int tma = (a.M + 127) / 128, tna = (a.N + 127) / 128, tmw = (w.M + 127) / 128, tnw = (w.N + 127) / 128;
-  hipLaunchKernelGGL(kern, dim3(tma * tna + tmw * tnw), dim3(WN == 2 ? 256 : 512), lds, stream, a, w, tma, tna, pick_group_rows(tma, tna, 128, 128),
-                     tmw, tnw, pick_group_rows(tmw, tnw, 128, 128), w.K > a.K ? 1 : 0);
+  const int tn_first = w.K > a.K ? 1 : 0;
+  const int n_long = tn_first ? tmw * tnw : tma * tna, n_short = tn_first ? tma * tna : tmw * tnw;
+  const int nk_long = ((tn_first ? w.K : a.K) + 31) / 32, nk_short = ((tn_first ? a.K : w.K) + 31) / 32;
+  const int per = WN == 0 ? 1 : x3::dual_tiles_per_block(n_long, nk_long, n_short, nk_short);
+  const int blocks = n_long + (WN == 0 ? n_short : x3::dual_short_blocks(n_short, per));
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(WN == 2 ? 256 : 512), lds, stream, a, w, tma, tna, pick_group_rows(tma, tna, 128, 128), tmw, tnw,
+                     pick_group_rows(tmw, tnw, 128, 128), tn_first, per);
   return (int)hipGetLastError();
 }
 bool x3_operands_ok(const GemmArgsB& p, long a_rows, long b_rows) {
@@ -1602,6 +1732,8 @@ int gemm_bf16x3_dual(const GemmArgsB& nt, const GemmArgsB& tn, hipStream_t strea
   static const bool on = !getenv("TFK_BF16X3_DUAL") || atoi(getenv("TFK_BF16X3_DUAL")) != 0;
   const long tiles = (long)((nt.M + 127) / 128) * ((nt.N + 127) / 128) + (long)((tn.M + 127) / 128) * ((tn.N + 127) / 128);
   if (!on || tiles < 256) return -1;
+  // (the dual kernel writes both results through buffer resources with 32-bit byte offsets: epilogue<>, CBUF)
+  if ((long)nt.M * nt.ldc * 4 >= (1L << 31) || (long)tn.M * tn.ldc * 4 >= (1L << 31)) return -1;
   const int key = (nt.epi == EPI_DACT ? 2 : 0) + (tn.epi == EPI_ACCUM ? 1 : 0);
   switch (key) {
 #define TFK_X3_DUAL(E1, E2)                                                                \

@@ -147,6 +147,44 @@ X3_HD int ks16_imm(int X, int hi) {
   return 128 * (X & ~1) + hi * 2 * (EXT / 32 * 384);
 }
 
+// ---- tile lists of the dual (dA + dW) launch ---------------------------------------------------------------------
+// The two problems of a dual launch have tiles of different LENGTH (ring tiles of 32 k: 64 for dA against 32 for dW at 1024
+// frames).  With one tile per block a CU that draws short tiles runs several blocks back to back and pays block dispatch, the
+// ring's ramp and the drain in front of the epilogue once per tile, exposed; so a block of the SHORT problem is given a list of
+// `per` consecutive tiles of the XCD-grouped tile sequence (tile_of_block in gemm_bf16.hip) and runs them without leaving its CU,
+// the ring carrying on across the tile boundary.  Blocks of the long problem keep one tile each and come first in block order.
+constexpr int kXcds = 8;
+constexpr int kCus = 256;
+// tiles per block of the short problem: the count that brings a block's ring tiles closest to a long block's (ties go down) --
+// lowered, one by one, while the grouped grid would have fewer blocks than the chip has CUs (a CU left idle costs more than a
+// second ramp)
+X3_HD int dual_tiles_per_block(int n_long, int nk_long, int n_short, int nk_short) {
+  int per = (nk_long + (nk_short - 1) / 2) / nk_short;
+  if (per < 1) per = 1;
+  while (per > 1 && n_long + (n_short + per - 1) / per < kCus) --per;
+  return per;
+}
+// Block g of the short problem's blocks runs on the XCD that all blocks with g % 8 share and takes tiles [seq0, seq0 + count) of
+// that XCD's contiguous run of the tile sequence (q or q + 1 tiles, as tile_of_block deals them): consecutive sequence numbers
+// walk down a column of tiles first, so the tiles of a list share an operand panel and the second finds it in that XCD's L2.
+// count == 0: a block past the end of a run that is one list shorter than another XCD's (it ends at once).
+X3_HD void dual_block_tiles(int n_short, int per, int g, int& seq0, int& count) {
+  const int xcd = g % kXcds, j = g / kXcds;
+  const int q = n_short / kXcds, r = n_short % kXcds;
+  const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  const int cnt = q + (xcd < r ? 1 : 0);
+  const int left = cnt - j * per;
+  seq0 = start + j * per;
+  count = left <= 0 ? 0 : left < per ? left : per;
+}
+// blocks the short problem needs: up to the last block with a tile (at most seven empty ones in front of it)
+X3_HD int dual_short_blocks(int n_short, int per) {
+  const int q = n_short / kXcds, r = n_short % kXcds;
+  if (q == 0) return r;
+  const int j_q = (q + per - 1) / per, j_q1 = (q + 1 + per - 1) / per;  // lists of a run of q / of q + 1 tiles
+  return (r > 0 && j_q1 > j_q) ? kXcds * j_q + r : kXcds * j_q;
+}
+
 #if defined(__HIPCC__)
 // x = p1 + p2 + p3 exactly, each a bf16, by ROUND TO NEAREST (even): p1 = RN(x), p2 = RN(x - p1), p3 = x - p1 - p2.
 // Both subtractions are exact in fp32 (x - p1 keeps the low 16 bits of x's significand, sign included; the remainder after
