@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 9
+#define TFK_ABI_VERSION 10
 
 typedef struct tfk_engine tfk_engine;
 
@@ -265,6 +265,41 @@ int tfk_ctc_greedy(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const 
 int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
                        int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
                        int32_t* hyp, int32_t* hyp_len, int32_t* edits, int flags);
+/* (ABI 10) CTC prefix beam search without a language model (Graves 2012; Hannun et al. 2014) with the conventions of
+ * tf.nn.ctc_beam_search_decoder(merge_repeated=False), and the label errors of its best path.  Eval-mode forward of the flat
+ * utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); the LOGITS are log-softmaxed per row; blank = the
+ * LAST class; utterances are independent.  The algorithm (this comment is the contract):
+ *   Per utterance a beam of at most beam_width prefixes; every prefix p carries (pb, pnb) = the log-probability of all
+ *   alignments of p so far that end in a blank / in a non-blank.  Start: {(): (0, -inf)}.  For frame t with
+ *   log-probabilities lp, from every beam prefix p with tot = logaddexp(pb, pnb):
+ *     stay:    p receives pb' (+)= tot + lp[blank] and, if p is not empty, pnb' (+)= pnb + lp[last(p)];
+ *     extend:  for every label c in [0, output_dim - 1), q = p + (c,) receives pnb' (+)= (pb if c == last(p) else tot) + lp[c];
+ *     contributions to the same label sequence merge by logaddexp (a q that is itself in the beam collects its own stay terms
+ *     and its parent's extension: at most three terms, summed in a fixed order);
+ *     the beam_width candidates with the largest logaddexp(pb', pnb') are kept.  Ties: the shorter prefix, then the candidate
+ *     with the lower (beam slot of p, label) pair -- a fixed function of the input, so two calls agree bit for bit; it is
+ *     NOT the lexicographic order of the label sequences, and nothing should rest on how an exact tie falls.
+ *   After the last frame: the top_paths <= beam_width best prefixes by total score, best first.
+ * hyp[n * T + row]: path n of utterance u starts at row sum_{v<u} utt_len[v] of plane n, the rest of its rows are -1 (a
+ * hypothesis never has more labels than frames); hyp_len[n * U + u]: its label count; score[n * U + u]: its natural-log
+ * probability (float; summed in fp32 relative to a running offset kept in double).  A zero-frame utterance has one hypothesis,
+ * the empty one with score 0; paths beyond the surviving prefixes have length 0 and score -inf.  With ref_labels / ref_len
+ * (as tfk_ctc_greedy) and edits[U] non-NULL: edits[u] = Levenshtein distance of the BEST path to the reference.  NaN logits:
+ * the result is unspecified, the call returns.  Limits: 1 <= top_paths <= beam_width <= 128, output_dim <= 64 (63 labels +
+ * blank), T <= 524286; a shape outside them returns non-zero and tfk_last_error names the limit.  Host pointers.  Evaluation
+ * mode; parameters, accumulators and statistics are not touched (same rules as tfk_ctc_greedy).  flags: 0. */
+int tfk_ctc_beam(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                 int32_t beam_width, int32_t top_paths, const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp,
+                 int32_t* hyp_len, float* score, int32_t* edits, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                     int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths,
+                     const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score,
+                     int32_t* edits, int flags);
+/* (ABI 10) Tests / tools: the beam search alone on logits [T, ld] of O classes, stream-ordered on `stream`, DEVICE pointers:
+ * seg[U + 1] = first row of every utterance (seg[U] = T); hyp [top_paths * T], hyp_len / score [top_paths * U] as above. */
+int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score);
 /* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
  * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */

@@ -48,6 +48,27 @@ void ctc_loss_reduce(hipStream_t s, const float* utt_loss, const int32_t* lab_of
 // n-th label (repeats merged, then the blank O - 1 removed), -1 on its remaining rows; hyp_len[u] = its label count.
 void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int32_t* cls,
                    int32_t* hyp, int32_t* hyp_len);
+// Prefix beam search without a language model (Graves 2012; Hannun et al. 2014) with the conventions of
+// tf.nn.ctc_beam_search_decoder(merge_repeated=False), on the logits [T, ld] of the utterances seg[U + 1]; blank = the
+// LAST class; rows are log-softmaxed inside the kernel.  Per utterance a beam of at most W prefixes, each with (pb, pnb) =
+// log-probability of its alignments so far that end in a blank / a non-blank, start {(): (0, -inf)}.  Per frame with
+// log-probabilities lp, from every beam prefix p with tot = logaddexp(pb, pnb):
+//   stay      p gets pb' (+)= tot + lp[blank] and, if p is not empty, pnb' (+)= pnb + lp[last(p)]
+//   extend    q = p + (c,), c in [0, O - 1), gets pnb' (+)= (pb if c == last(p) else tot) + lp[c]
+// contributions to one label sequence merge by logaddexp (a q that is itself in the beam: its own pnb term, then its
+// parent's extension -- a fixed order); the W candidates with the largest logaddexp(pb', pnb') survive -- ties: shorter
+// prefix, then the lower (beam slot, label) of the candidate, which is a fixed function of the input, not of scheduling.
+// Out: hyp[n * T + seg[u] + k] = k-th label of utterance u's n-th best prefix (-1 on its remaining rows),
+// hyp_len[n * U + u], score[n * U + u] = its natural-log probability; n < top_paths, best first; paths beyond the
+// surviving prefixes have length 0 and score -inf (a zero-frame utterance: the empty prefix with score 0, then those).
+// trie: ctc_beam_scratch_words(T, U, W) 64-bit words of scratch.  ctc_beam_limits: NULL, or the limit a shape breaks.
+constexpr int kCtcBeamMaxWidth = 128;
+constexpr int kCtcBeamMaxClasses = 64;
+constexpr int kCtcBeamMaxFrames = (1 << 19) - 2;
+size_t ctc_beam_scratch_words(int T, int U, int W);
+const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths);
+void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
+                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score);
 // tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
 // ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
 // length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,

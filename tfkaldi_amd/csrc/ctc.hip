@@ -469,6 +469,315 @@ edit_distance_kernel(const int32_t* __restrict__ hyp, const int32_t* __restrict_
   if (lane == (S - 1) / R) dist[u] = res;
 }
 
+
+// ---- prefix beam search (tf.nn.ctc_beam_search_decoder, merge_repeated=False; the algorithm is stated in ctc.h) ----
+//
+// ONE WORKGROUP PER UTTERANCE, the beam resident in LDS (two sides, swapped per frame).  A frame step:
+//   A  wave 0 turns the frame's logits (loaded one step ahead) into log-probabilities lp[c] in LDS; waves 1-2 mark, per
+//      beam slot i, the labels c for which the extension (i, c) IS a prefix already in the beam (childmask)
+//   B  the nb * O candidates -- (slot i, label c) = extension, (slot i, blank column) = "stay" -- are scored, a
+//      contiguous run per thread; a stay candidate collects its parent's extension (at most three terms, fixed order);
+//      an extension that equals a beam prefix is dead.  Keys (order-preserving uint32 of the total) go to LDS
+//   C  the best W by an 8-bit radix select over the keys (4 histogram passes; integer LDS atomics, so the counts do
+//      not depend on scheduling); only when the W-th and (W+1)-th key are equal, 4 more passes over the secondary key
+//      (shorter prefix, then lower candidate index)
+//   D  compaction in candidate order (block prefix sum), the survivors' (pb, pnb) re-centred on the best total (the
+//      sum of the offsets is kept in double: the scores stay exact to ~1e-6 whatever T is); a surviving extension
+//      finds or inserts its trie node
+//   E  src[j] = the slot of prefix j's parent in the new beam (what A and B need at the next frame)
+// The trie is an open-addressing table in global scratch keyed by (parent node, label); a node's id is its slot, so
+// one label sequence has one id however often it leaves and re-enters the beam, and "extension (p, c) equals q" is
+// q.parent == p.node && q.last == c.  Ids depend on the insertion order, results do not: nothing is ordered by id.
+constexpr int kBeamThreads = 256;
+constexpr int kBeamKeys = kCtcBeamMaxWidth * kCtcBeamMaxClasses;
+constexpr int kBeamRoot = 0x7fffffff;  // node id of the empty prefix (never a table slot)
+constexpr unsigned long long kTrieEmpty = ~0ull;
+
+struct BeamSide {
+  float pb[kCtcBeamMaxWidth], pnb[kCtcBeamMaxWidth], tot[kCtcBeamMaxWidth];
+  int node[kCtcBeamMaxWidth], parent[kCtcBeamMaxWidth], last[kCtcBeamMaxWidth], len[kCtcBeamMaxWidth],
+      src[kCtcBeamMaxWidth];
+};
+
+__device__ __forceinline__ float lae(float a, float b) {
+  const float m = fmaxf(a, b), n = fminf(a, b);
+  if (!(m > -1e29f)) return NEG;
+  return m + __logf(1.f + __expf(n - m));
+}
+// order-preserving map of a float onto uint32; 0 is kept free for "no candidate"
+__device__ __forceinline__ uint32_t sortable(float x) {
+  const uint32_t b = __builtin_bit_cast(uint32_t, x);
+  const uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return k ? k : 1u;
+}
+// (pb', pnb') of candidate (slot i, class c); c == blank is the stay candidate
+__device__ __forceinline__ void beam_candidate(const BeamSide& b, const float* lp, int i, int c, int blank, float* pbn,
+                                               float* pnbn) {
+  if (c == blank) {
+    const int l = b.last[i];
+    *pbn = fmaxf(b.tot[i] + lp[blank], NEG);
+    float v = l >= 0 ? fmaxf(b.pnb[i] + lp[l], NEG) : NEG;
+    const int s = b.src[i];
+    if (s >= 0) v = lae(v, fmaxf((b.last[s] == l ? b.pb[s] : b.tot[s]) + lp[l], NEG));
+    *pnbn = v;
+  } else {
+    *pbn = NEG;
+    *pnbn = fmaxf((c == b.last[i] ? b.pb[i] : b.tot[i]) + lp[c], NEG);
+  }
+}
+// secondary key of candidate k (larger = preferred): shorter prefix, then lower candidate index
+__device__ __forceinline__ uint32_t beam_tiebreak(int len, int k) {
+  return ((uint32_t)(kCtcBeamMaxFrames + 1 - len) << 13) | (uint32_t)(kBeamKeys - 1 - k);
+}
+
+// The `need`-th largest of the non-zero keys keyf(k), k in [k0, k1) over the block's threads (need <= their number):
+// returns it; *take = how many candidates EQUAL to it belong to the best `need`, *have = how many there are.
+template <class F>
+__device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, int need, uint32_t* hist, int* sel,
+                                                      int* take, int* have) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  uint32_t prefix = 0;
+  int cnt = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t key = keyf(k);
+      if (key != 0 && (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))))
+        atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {
+      const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
+      const int s = (int)(h.x + h.y + h.z + h.w);
+      int incl = s;  // this lane's bins and every higher one
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_down(incl, o);
+        if (lane + o < 64) incl += v;
+      }
+      int above = incl - s;
+      const uint32_t hv[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+      for (int q = 3; q >= 0; --q) {
+        const int c = (int)hv[q];
+        if (need > above && need <= above + c) {
+          sel[0] = 4 * lane + q;
+          sel[1] = need - above;
+          sel[2] = c;
+        }
+        above += c;
+      }
+      reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    prefix |= (uint32_t)sel[0] << shift;
+    need = sel[1];
+    cnt = sel[2];
+  }
+  *take = need;
+  *have = cnt;
+  return prefix;
+}
+
+__global__ void __launch_bounds__(kBeamThreads)
+ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U, int T, int W,
+                int top_paths, unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp,
+                int32_t* __restrict__ hyp_len, float* __restrict__ score) {
+  __shared__ BeamSide beam[2];
+  __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ unsigned long long childmask[kCtcBeamMaxWidth];
+  __shared__ float lp[kCtcBeamMaxClasses];
+  __shared__ float wmax[4];
+  __shared__ int wsum[4];
+  __shared__ int sel[4];
+  __shared__ int s_nb, s_ndead;
+  __shared__ int path[kCtcBeamMaxWidth];
+
+  const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int blank = O - 1;
+  const uint32_t cap = 2u * (uint32_t)Tn * (uint32_t)W + 64u;  // this utterance's share of the table: load <= 1/2
+  unsigned long long* tab = trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
+  const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)O - 1u) / (unsigned)O);  // k / O for k < 2^13
+
+  hist[tid] = 0u;
+  if (tid < kCtcBeamMaxWidth) {
+    childmask[tid] = 0ull;
+    path[tid] = -1;
+  }
+  if (tid == 0) {  // the beam starts as {(): (0, -inf)}
+    BeamSide& b = beam[0];
+    b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
+    b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
+    s_nb = 1;
+    s_ndead = 0;
+  }
+  int cur = 0;
+  double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
+  float z_next = (wave == 0 && lane < O && Tn > 0) ? logits[(size_t)r0 * ld + lane] : 0.f;
+  __syncthreads();
+
+  for (int t = 0; t < Tn; ++t) {
+    const BeamSide& b = beam[cur];
+    BeamSide& nx = beam[cur ^ 1];
+    const int nb = s_nb, ndead = s_ndead;
+    // A
+    if (wave == 0) {
+      const float z = lane < O ? z_next : -INFINITY;
+      if (t + 1 < Tn && lane < O) z_next = logits[(size_t)(r0 + t + 1) * ld + lane];
+      const float mx = wave_max(z);
+      float se = lane < O ? expf(z - mx) : 0.f;
+      for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+      if (lane < O) lp[lane] = z - (mx + logf(se));
+    } else if (tid - 64 < nb) {
+      const int j = tid - 64, s = b.src[j];
+      if (s >= 0) atomicOr(&childmask[s], 1ull << b.last[j]);
+    }
+    __syncthreads();
+    // B
+    const int N = nb * O;
+    const int cpt = ((N + kBeamThreads - 1) / kBeamThreads) | 1;  // an odd run per thread: conflict-free LDS strides
+    const int k0 = min(tid * cpt, N), k1 = min(k0 + cpt, N);
+    float lmax = NEG;
+    for (int k = k0; k < k1; ++k) {
+      const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
+      float pbn, pnbn;
+      beam_candidate(b, lp, i, c, blank, &pbn, &pnbn);
+      const bool live = c == blank || !((childmask[i] >> c) & 1ull);
+      const float tot = lae(pbn, pnbn);
+      keys[k] = live ? sortable(tot) : 0u;
+      if (live) lmax = fmaxf(lmax, tot);
+    }
+    lmax = wave_max(lmax);
+    if (lane == 0) wmax[wave] = lmax;
+    __syncthreads();
+    float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (!(m > -1e29f)) m = 0.f;
+    // C
+    uint32_t K = 0u, K2 = 0xffffffffu;  // select: key > K, or key == K and tie-break key >= K2
+    if (N - ndead > W) {
+      int take, have;
+      K = beam_radix_select([&](int k) { return keys[k]; }, k0, k1, W, hist, sel, &take, &have);
+      K2 = 0u;
+      if (take < have) {
+        int t2, h2;
+        K2 = beam_radix_select(
+            [&](int k) {
+              const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
+              return keys[k] == K ? beam_tiebreak(b.len[i] + (c != blank), k) : 0u;
+            },
+            k0, k1, take, hist, sel, &t2, &h2);
+      }
+    }
+    // D
+    int cnt = 0;
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t key = keys[k];
+      if (key > K) { ++cnt; continue; }
+      if (key == K && K2 != 0xffffffffu) {
+        const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
+        cnt += beam_tiebreak(b.len[i] + (c != blank), k) >= K2;
+      }
+    }
+    int incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int slot = incl - cnt;
+    for (int w = 0; w < wave; ++w) slot += wsum[w];
+    const int nb_new = min(wsum[0] + wsum[1] + wsum[2] + wsum[3], W);
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t key = keys[k];
+      const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
+      const bool chosen = key > K || (key == K && K2 != 0xffffffffu && beam_tiebreak(b.len[i] + (c != blank), k) >= K2);
+      if (!chosen) continue;
+      if (slot < W) {
+        float pbn, pnbn;
+        beam_candidate(b, lp, i, c, blank, &pbn, &pnbn);
+        pbn = fmaxf(pbn - m, NEG);
+        pnbn = fmaxf(pnbn - m, NEG);
+        nx.pb[slot] = pbn;
+        nx.pnb[slot] = pnbn;
+        nx.tot[slot] = lae(pbn, pnbn);
+        if (c == blank) {
+          nx.node[slot] = b.node[i]; nx.parent[slot] = b.parent[i]; nx.last[slot] = b.last[i]; nx.len[slot] = b.len[i];
+        } else {
+          // find or insert (parent node, label): the slot is the node's id
+          const unsigned long long nk = ((unsigned long long)(uint32_t)b.node[i] << 6) | (unsigned long long)c;
+          uint32_t pos = __umulhi((uint32_t)((nk * 0x9E3779B97F4A7C15ull) >> 32), cap);
+          int id = 0;
+          for (uint32_t n = 0; n < cap; ++n) {
+            const unsigned long long old = atomicCAS(&tab[pos], kTrieEmpty, nk);
+            if (old == kTrieEmpty || old == nk) { id = (int)pos; break; }
+            pos = pos + 1u == cap ? 0u : pos + 1u;
+          }
+          nx.node[slot] = id; nx.parent[slot] = b.node[i]; nx.last[slot] = c; nx.len[slot] = b.len[i] + 1;
+        }
+      }
+      ++slot;
+    }
+    if (tid == 0) {
+      s_nb = nb_new;
+      s_ndead = 0;
+    }
+    off += (double)m;
+    __syncthreads();
+    // E
+    if (tid < kCtcBeamMaxWidth) childmask[tid] = 0ull;
+    {
+      int s = -1;
+      if (tid < nb_new) {
+        const int p = nx.parent[tid];
+        for (int i = 0; i < nb_new; ++i)
+          if (nx.node[i] == p) s = i;
+        nx.src[tid] = s;
+      }
+      const int dead = __popcll(__ballot(s >= 0));
+      if (lane == 0 && dead) atomicAdd(&s_ndead, dead);
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+
+  // the top_paths best of the final beam: higher total, then shorter, then lower slot
+  const BeamSide& b = beam[cur];
+  const int nb = s_nb;
+  if (tid < nb) {
+    const uint32_t kj = sortable(b.tot[tid]);
+    const int lj = b.len[tid];
+    int rank = 0;
+    for (int i = 0; i < nb; ++i) {
+      const uint32_t ki = sortable(b.tot[i]);
+      const int li = b.len[i];
+      rank += ki > kj || (ki == kj && (li < lj || (li == lj && i < tid)));
+    }
+    path[rank] = tid;
+  }
+  __syncthreads();
+  for (int n = 0; n < top_paths; ++n) {
+    const int j = path[n];
+    const int L = j >= 0 ? min(b.len[j], Tn) : 0;
+    int32_t* out = hyp + (size_t)n * T + r0;
+    for (int f = L + tid; f < Tn; f += kBeamThreads) out[f] = -1;
+    if (tid == 0) {
+      hyp_len[(size_t)n * U + u] = L;
+      score[(size_t)n * U + u] = (j >= 0 && b.tot[j] > -1e29f) ? (float)(off + (double)b.tot[j]) : -INFINITY;
+    }
+  }
+  if (tid < top_paths && path[tid] >= 0) {  // back-trace through the parent links, labels land in forward order
+    const int j = path[tid];
+    int32_t* out = hyp + (size_t)tid * T + r0;
+    uint32_t node = (uint32_t)b.node[j];
+    for (int pos = min(b.len[j], Tn) - 1; pos >= 0 && node < cap; --pos) {
+      const unsigned long long nk = __hip_atomic_load(&tab[node], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[pos] = (int32_t)(nk & 63ull);
+      node = (uint32_t)(nk >> 6);
+    }
+  }
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -498,6 +807,25 @@ void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, con
                    int32_t* hyp, int32_t* hyp_len) {
   if (T > 0) hipLaunchKernelGGL(ctc_row_argmax_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, cls);
   if (U > 0) hipLaunchKernelGGL(ctc_merge_kernel, dim3(U), dim3(64), 0, s, cls, seg, O - 1, hyp, hyp_len);
+}
+
+size_t ctc_beam_scratch_words(int T, int U, int W) { return 2 * (size_t)T * (size_t)W + 64 * (size_t)U; }
+
+const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths) {
+  if (W < 1 || W > kCtcBeamMaxWidth) return "beam_width outside [1, 128]";
+  if (O < 2 || O > kCtcBeamMaxClasses) return "output_dim outside [2, 64] (63 labels + blank)";
+  if (top_paths < 1 || top_paths > W) return "top_paths outside [1, beam_width]";
+  if (T < 0 || T > kCtcBeamMaxFrames) return "more than 524286 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  return nullptr;
+}
+
+void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
+                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score) {
+  if (U <= 0) return;
+  (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie, hyp,
+                     hyp_len, score);
 }
 
 void label_edit_distance(hipStream_t s, const int32_t* hyp, const int32_t* hyp_off, const int32_t* hyp_cnt,

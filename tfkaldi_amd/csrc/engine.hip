@@ -66,13 +66,14 @@ struct LayerLayout {
 
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
-  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_COUNT
+  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
                                      "act_forward",             "hidden_backward",  "colsum",          "softmax_xent",
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
-                                     "misc",                    "ctc_best_path",    "edit_distance"};
+                                     "misc",                    "ctc_best_path",    "edit_distance",
+                                     "ctc_beam_search"};
 
 struct ProfRec {
   int family;
@@ -184,6 +185,9 @@ struct tfk_engine {
   size_t ctc_cap_dec = 0;
   int32_t* h_dec = nullptr;
   size_t h_dec_cap = 0;
+  // prefix beam search (tfk_ctc_beam): the trie table of ctc_beam_search
+  unsigned long long* ctc_trie = nullptr;
+  size_t ctc_cap_trie = 0;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1784,7 +1788,7 @@ int tfk_destroy(tfk_engine* e) {
   if (e->ws_splitk) hipFree(e->ws_splitk);
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
-                  (void*)e->ctc_logz, (void*)e->ctc_dec})
+                  (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie})
     if (p) hipFree(p);
   if (e->h_dec) hipHostFree(e->h_dec);
   for (hipEvent_t ev : e->post_ev) hipEventDestroy(ev);
@@ -2413,6 +2417,101 @@ int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T
   const RawSpec r = {utt_len, U, context_width, cmvn};
   if (!utt_len) return fail(-1, "utt_len is NULL");
   return ctc_greedy_impl(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp, hyp_len, edits, flags, &r);
+}
+// Prefix beam search (tf.nn.ctc_beam_search_decoder, merge_repeated=False; the algorithm: tfkaldi_hip.h) + the label errors
+// of the best path: evaluation-mode forward as tfk_posteriors, then ctc_beam_search (and label_edit_distance on plane 0)
+// on the logits in HBM; top_paths * (T + 2U) + U words go back to the host.
+static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                         int32_t beam_width, int32_t top_paths, const int32_t* ref_labels, const int32_t* ref_len,
+                         int32_t* hyp, int32_t* hyp_len, float* score, int32_t* edits, int flags, const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
+    return fail(-1, "flags %d: tfk_ctc_beam takes 0, tfk_ctc_beam_raw 0 or TFK_RAW_DEVICE", flags);
+  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
+  if (!X) return fail(-1, "X is NULL");
+  if (!hyp || !hyp_len || !score) return fail(-1, "hyp / hyp_len / score is NULL");
+  if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
+  if (const char* why = ctc_beam_limits(e->O, T, U, beam_width, top_paths))
+    return fail(-1, "CTC beam search (beam_width %d, top_paths %d, output_dim %d, T %d): %s", beam_width, top_paths, e->O, T,
+                why);
+  const CtcSpec c = {utt_len, U, ref_labels, ref_len};
+  const size_t P = (size_t)top_paths;
+  const size_t back = P * (size_t)T + 2 * P * (size_t)U + (size_t)U;  // [hypotheses | lengths | scores | distances]
+  int max_ref = 0;
+  Pass p;
+  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
+    CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
+    CHK(grow(e, &e->ctc_trie, &e->ctc_cap_trie, ctc_beam_scratch_words(T, U, beam_width)));
+    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, back);
+  }));
+  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
+  int32_t* d_hyp = e->ctc_dec;
+  int32_t* d_len = d_hyp + P * T;
+  float* d_score = reinterpret_cast<float*>(d_len + P * U);
+  int32_t* d_dist = d_len + 2 * P * U;
+  {
+    const double trie_bytes = 8.0 * ctc_beam_scratch_words(T, U, beam_width);  // the memset: the call's largest traffic
+    ProfScope ps(e, KF_CTC_BEAM, 0, 4.0 * T * e->O + 4.0 * P * T + trie_bytes);
+    ctc_beam_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, e->ctc_trie, d_hyp, d_len,
+                    d_score);
+  }
+  if (edits) {
+    ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
+    label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_dist);
+  }
+  HIPCHK(hipGetLastError());
+  CHK(finish_slot(e, flags, p.slot_before));
+  if (back > e->h_dec_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
+    e->h_dec = nullptr;
+    e->h_dec_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
+    e->h_dec_cap = back + back / 2;
+  }
+  HIPCHK(hipMemcpyAsync(e->h_dec, d_hyp, (edits ? back : back - U) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  remember_pass(e, T, p.nact, p.call, p.Xd);
+  CHK(check_kernel_errors(e));
+  memcpy(hyp, e->h_dec, P * T * sizeof(int32_t));
+  memcpy(hyp_len, e->h_dec + P * T, P * U * sizeof(int32_t));
+  memcpy(score, e->h_dec + P * T + P * U, P * U * sizeof(float));
+  if (edits) memcpy(edits, e->h_dec + P * T + 2 * P * U, (size_t)U * sizeof(int32_t));
+  return 0;
+}
+
+int tfk_ctc_beam(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                 int32_t beam_width, int32_t top_paths, const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp,
+                 int32_t* hyp_len, float* score, int32_t* edits, int flags) {
+  return ctc_beam_impl(e, X, ldx, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
+                       flags, nullptr);
+}
+int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                     int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths,
+                     const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score,
+                     int32_t* edits, int flags) {
+  const RawSpec r = {utt_len, U, context_width, cmvn};
+  if (!utt_len) return fail(-1, "utt_len is NULL");
+  return ctc_beam_impl(e, raw, ldraw, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
+                       flags, &r);
+}
+int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score) {
+  if (const char* why = ctc_beam_limits(O, T, U, beam_width, top_paths))
+    return fail(-1, "CTC beam search (beam_width %d, top_paths %d, O %d, T %d, U %d): %s", beam_width, top_paths, O, T, U, why);
+  if (U == 0) return 0;
+  if (!seg || !hyp_len || !score || (T > 0 && (!logits || !hyp))) return fail(-1, "logits / seg / hyp / hyp_len / score is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  unsigned long long* trie = nullptr;  // the call's own scratch, released in stream order
+  HIPCHK(hipMallocAsync((void**)&trie, ctc_beam_scratch_words(T, U, beam_width) * sizeof(unsigned long long),
+                        (hipStream_t)stream));
+  ctc_beam_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, trie, hyp, hyp_len, score);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(trie, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
 }
 int tfk_label_edit_distance(void* stream, const int32_t* hyp, const int32_t* hyp_off, const int32_t* ref,
                             const int32_t* ref_off, int32_t U, int32_t* dist) {

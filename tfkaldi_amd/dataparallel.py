@@ -161,15 +161,22 @@ def _eval_accumulate_all(engine, mine):
         _eval_accumulate(engine, mb)
 
 
-def _label_errors(engine, mb):
-    """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding"""
+def _label_errors(engine, mb, beam_width=None):
+    """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
+    (beam_width None) or under prefix beam search of that width (its best path)"""
     if not isinstance(mb, CtcMicroBatch):
         raise TypeError("label errors need CTC micro-batches (label sequences), not %s" % type(mb).__name__)
-    if mb.context_width is not None:
-        _, edits = engine.ctc_greedy_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, labels=mb.labels,
-                                         label_lens=mb.label_lens)
+    if beam_width is None:
+        if mb.context_width is not None:
+            _, edits = engine.ctc_greedy_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, labels=mb.labels,
+                                             label_lens=mb.label_lens)
+        else:
+            _, edits = engine.ctc_greedy(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens)
+    elif mb.context_width is not None:
+        _, _, edits = engine.ctc_beam_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, beam_width=beam_width,
+                                          labels=mb.labels, label_lens=mb.label_lens)
     else:
-        _, edits = engine.ctc_greedy(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens)
+        _, _, edits = engine.ctc_beam(mb.X, mb.utt_lens, beam_width=beam_width, labels=mb.labels, label_lens=mb.label_lens)
     import numpy as np
     return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
 
@@ -1286,17 +1293,18 @@ class DataParallel(object):
         start, end = partition(len(microbatches), self.world)[self.rank]
         return self.eval_own(engine, microbatches[start:end])
 
-    def label_errors(self, engine, microbatches):
-        """(edits, reference labels): best-path label errors summed over the CTC micro-batches of the WHOLE batch (identical
-        on every rank).  COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and
-        the two counts are SUM all-reduced as one int64 tensor over self.group (on the device for an NCCL / RCCL group)."""
+    def label_errors(self, engine, microbatches, beam_width=None):
+        """(edits, reference labels): label errors summed over the CTC micro-batches of the WHOLE batch (identical on every
+        rank) under best-path decoding (beam_width None) or the best path of a prefix beam search of that width.
+        COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and the two counts
+        are SUM all-reduced as one int64 tensor over self.group (on the device for an NCCL / RCCL group)."""
         mine = microbatches
         if self.enabled:
             start, end = partition(len(microbatches), self.world)[self.rank]
             mine = microbatches[start:end]
         edits = labels = 0
         for mb in mine:
-            e, n = _label_errors(engine, mb)
+            e, n = _label_errors(engine, mb, beam_width)
             edits += e
             labels += n
         if not self.enabled:

@@ -417,6 +417,86 @@ class Engine(object):
             self._raw_release()
         return self._greedy_result(hyp, hyp_len, utt_lens, edits)
 
+    # ---- CTC prefix beam search: tf.nn.ctc_beam_search_decoder(merge_repeated=False), N best with log-probabilities ----
+    @staticmethod
+    def _beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits):
+        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
+        hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
+        return hyps, np.ascontiguousarray(score.T), edits
+
+    @staticmethod
+    def _beam_empty(utt_lens, top_paths, edits, label_lens):
+        """only zero-frame utterances: the empty hypothesis with score 0, the other paths empty with score -inf"""
+        scores = np.full((utt_lens.size, top_paths), -np.inf, dtype=np.float32)
+        scores[:, 0] = 0.0
+        hyps = [[np.zeros(0, dtype=np.int32) for _ in range(top_paths)] for _ in utt_lens]
+        return hyps, scores, None if edits is None else label_lens.copy()
+
+    @staticmethod
+    def _beam_args(beam_width, top_paths):
+        beam_width, top_paths = int(beam_width), int(top_paths)
+        if not 1 <= top_paths <= beam_width:
+            raise ValueError("top_paths %d outside [1, beam_width = %d]" % (top_paths, beam_width))
+        return beam_width, top_paths
+
+    def ctc_beam(self, X, utt_lens, beam_width=100, top_paths=1, labels=None, label_lens=None):
+        """Prefix beam search over the utterances X [sum(utt_lens), F] (tfk_ctc_beam; the algorithm is stated in
+        include/tfkaldi_hip.h): the `top_paths` most probable label sequences of every utterance among those that stay in a
+        beam of `beam_width`, best first, with their natural-log probabilities.  Returns (hyps, scores, edits): hyps[u][n]
+        int32 label arrays, scores float32 [U, top_paths] (-inf where fewer prefixes survived), edits int32 [U] = Levenshtein
+        distance of the BEST path to the reference (labels back to back, label_lens per utterance) or None."""
+        X = _f32(X)
+        beam_width, top_paths = self._beam_args(beam_width, top_paths)
+        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
+        if int(utt_lens.sum()) != X.shape[0]:
+            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
+        if X.shape[0] == 0:
+            return self._beam_empty(utt_lens, top_paths, edits, label_lens)
+        hyp = np.empty((top_paths, X.shape[0]), dtype=np.int32)
+        hyp_len = np.empty((top_paths, utt_lens.size), dtype=np.int32)
+        score = np.empty((top_paths, utt_lens.size), dtype=np.float32)
+        check(self.lib.tfk_ctc_beam(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
+                                    utt_lens.ctypes.data_as(c_void_p), utt_lens.size, beam_width, top_paths, lab_ptr, len_ptr,
+                                    hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
+                                    score.ctypes.data_as(c_void_p),
+                                    c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), 0))
+        return self._beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits)
+
+    def ctc_beam_raw(self, raw, utt_lens, context_width, cmvn=None, beam_width=100, top_paths=1, labels=None,
+                     label_lens=None):
+        """ctc_beam on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        flags = 0
+        beam_width, top_paths = self._beam_args(beam_width, top_paths)
+        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
+        if self._on_device(raw):
+            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
+            flags |= _lib.RAW_DEVICE
+            cols = raw.shape[1]
+        else:
+            raw, utt_lens = self._raw_batch(raw, utt_lens)
+            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
+        if rows == 0:
+            self._raw_release()
+            return self._beam_empty(utt_lens, top_paths, edits, label_lens)
+        if cmvn is not None:
+            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
+            if cmvn.shape != (utt_lens.size, 2, cols):
+                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
+        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
+        hyp = np.empty((top_paths, rows), dtype=np.int32)
+        hyp_len = np.empty((top_paths, utt_lens.size), dtype=np.int32)
+        score = np.empty((top_paths, utt_lens.size), dtype=np.float32)
+        try:
+            check(self.lib.tfk_ctc_beam_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
+                                            int(context_width), cmvn_ptr, beam_width, top_paths, lab_ptr, len_ptr,
+                                            hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
+                                            score.ctypes.data_as(c_void_p),
+                                            c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), flags))
+        finally:
+            self._raw_release()
+        return self._beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits)
+
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):
         X = _f32(X)

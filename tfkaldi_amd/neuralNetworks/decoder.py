@@ -88,6 +88,26 @@ class Decoder(object):
             hyps, _ = self.engine.ctc_greedy(stack, lens)
         return hyps
 
+    def ctc_beam_search(self, utterances, beam_width=100, top_paths=1):
+        """Prefix beam search decoding of a CTC model (tf.nn.ctc_beam_search_decoder with merge_repeated=False, its default
+        beam_width): every utterance in ONE forward pass, the search on the device (tfk_ctc_beam).  Returns (hyps, scores):
+        hyps[u][n] the n-th best int32 label array of utterance u, scores float32 [U, top_paths] their natural-log
+        probabilities.  All `Unspliced` -> device-side splice, as decode_batch."""
+        if len(utterances) == 0:
+            return [], np.zeros((0, top_paths), dtype=np.float32)
+        lens = [u.shape[0] for u in utterances]
+        for u in utterances:
+            self._check(u)
+        if all(isinstance(u, Unspliced) for u in utterances):
+            hyps, scores, _ = self.engine.ctc_beam_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
+                                                       utterances[0].context_width, cmvn=cmvn_table(utterances),
+                                                       beam_width=beam_width, top_paths=top_paths)
+        else:
+            stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
+                                    for u in utterances])
+            hyps, scores, _ = self.engine.ctc_beam(stack, lens, beam_width=beam_width, top_paths=top_paths)
+        return hyps, scores
+
     def set_prior(self, prior):
         self.engine.set_prior(prior)
 

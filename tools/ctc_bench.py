@@ -3,7 +3,10 @@ blank, 16 utterances x 800 frames, 100 labels each) and print the per-kernel-fam
 best-path decoding + label edit distances on the device (tfk_ctc_greedy) against the eval-mode forward alone and against the
 host alternative (logits to the host, numpy argmax + merge, a Python Levenshtein), once with random output weights (long
 hypotheses: the edit distance's worst case) and once with the blank biased so that hypotheses come out near the reference
-length.  `--decode-only` skips the training step (e.g. under rocprofv3)."""
+length; then, on the same two workloads, the beam leg: prefix beam search on the device (tfk_ctc_beam) at W = 1, 10, 100 --
+ms per call, the engine profiler's time of the ctc_beam_search kernel, label error rate greedy vs beam, the largest
+|device - float64| of a best score, and the host alternative (the float64 numpy restatement the tests use, timed on ONE
+utterance of the same logits and scaled to the batch).  `--decode-only` skips the training step (e.g. under rocprofv3)."""
 import os
 import sys
 import time
@@ -13,6 +16,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tfkaldi_amd import _lib  # noqa: E402
 from tfkaldi_amd.engine import Engine  # noqa: E402
+# the beam leg's host alternative is the float64 numpy restatement the tests check the device against; it lives in the test
+# tree (tests/test_ctc_beam_host.py), not in the product
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from test_ctc_beam_host import prefix_beam_search  # noqa: E402
 
 
 def main():
@@ -126,6 +133,34 @@ def decode_leg(eng, X, utt, labels, lab, rng):
             print("    %-28s n=%4d %9.1f us/call" % (s["name"], s["launches"] // K, s["total_ms"] / K * 1e3))
         print("    eval forward device time %.1f us, decode kernels %.1f us (%.1f %% of the forward)" % (fwd * 1e3, dec * 1e3,
                                                                                                      100.0 * dec / fwd))
+        beam_leg(eng, X, utt, labels, lab, case, edits)
+
+
+def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
+    K = 10
+    logits = eng.posteriors(X, raw_logits=True)
+    for W in (1, 10, 100):
+        hyps, scores, edits = eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)
+        for _ in range(2):
+            eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)
+        t0 = time.perf_counter()
+        for _ in range(K):
+            eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)
+        ms = (time.perf_counter() - t0) / K * 1e3
+        eng.profile_begin()
+        for _ in range(K):
+            eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)
+        stats = {s["name"]: s for s in eng.profile_end()}
+        kern = stats["ctc_beam_search"]["total_ms"] / K
+        t0 = time.perf_counter()
+        h64, s64 = prefix_beam_search(logits[:utt[0]], utt[:1], W, 1)
+        host = (time.perf_counter() - t0) * 1e3
+        print("  beam (%s) W=%3d: tfk_ctc_beam %8.3f ms/call, ctc_beam_search kernel %8.3f ms (%.2f us per frame step); label error "
+              "rate beam %.3f greedy %.3f; best score of utterance 0: device %.5f float64 %.5f (|diff| %.1e, same labels: %s); "
+              "host alternative (numpy float64 restatement) %.0f ms for ONE utterance = %.0f ms scaled to %d"
+              % (case, W, ms, kern, kern * 1e3 / max(utt), edits.sum() / np.sum(lab), greedy_edits.sum() / np.sum(lab),
+                 scores[0, 0], s64[0, 0], abs(scores[0, 0] - s64[0, 0]), np.array_equal(hyps[0][0], h64[0][0]), host,
+                 host * len(utt), len(utt)))
 
 
 if __name__ == "__main__":
