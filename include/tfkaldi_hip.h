@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 10
+#define TFK_ABI_VERSION 11
 
 typedef struct tfk_engine tfk_engine;
 
@@ -300,6 +300,44 @@ int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
  * seg[U + 1] = first row of every utterance (seg[U] = T); hyp [top_paths * T], hyp_len / score [top_paths * U] as above. */
 int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                         int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score);
+/* (ABI 11) CTC forced alignment: the most probable alignment of every utterance's KNOWN label sequence -- which frames emit
+ * which label, and with what probability (time stamps and segments, corpus cleaning by alignment score, frame-level targets).
+ * Eval-mode forward of the flat utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); labels / label_len as
+ * tfk_accumulate_ctc takes them (back to back, values in [0, output_dim - 1), at most 511 per utterance); blank = the LAST
+ * class; utterances are independent.  The algorithm (this comment is the contract), for an utterance of Tn frames with logits
+ * z [Tn, O] and labels l_0 ... l_{S-1}:
+ *   States as the loss: n = 2S + 1, ordered blank, l_0, blank, l_1, ..., blank; class(s) = the blank for even s, l_{s>>1} for
+ *   odd s.  A valid path s_0 ... s_{Tn-1} starts in state 0 or 1, ends in state n - 1 or n - 2, and every step stays, advances
+ *   by 1, or advances by 2 -- by 2 only INTO a label state whose label differs from the label two states back.  The result is
+ *   the valid path that maximises sum_t z[t, class(s_t)].
+ *   The max-plus recursion runs on the RAW LOGITS, not on their log-softmax: a per-row constant does not move the argmax, and
+ *   for logits that are small integers every fp32 intermediate is then exact (the state vector is re-centred on its maximum,
+ *   which keeps that exactness; the sum of the shifts is kept in double) -- which makes the tie rule a testable, fixed function
+ *   of the input.  Ties: at a state the candidates are taken in the order stay, advance by 1, advance by 2, and a later
+ *   candidate replaces an earlier one only if it is STRICTLY larger; at the end n - 1 wins unless n - 2 is strictly larger.
+ *   In words: of equal predecessors the higher-numbered one wins.
+ * ali[T] (on the utterance's rows): for a frame that emits a label the POSITION j of that label, 0 <= j < S (its class is
+ * labels[j]; the position, not the class, separates repeated labels); -1 for a blank frame.  score[U]: the natural-log
+ * probability of that alignment, sum_t (z[t, class(s_t)] - logsumexp(z[t, :])) (float; fp32 values relative to a running
+ * offset kept in double, the rows' log-sum-exps summed in double, as the loss forms log Z).  An utterance too short for its
+ * labels (no valid path): score -inf and -2 on all its rows.  A zero-frame utterance: score 0 if S == 0, else -inf.  NaN
+ * logits: the result is unspecified, the call returns.  Errors (non-zero, tfk_last_error names the cause): NULL pointers,
+ * T <= 0, more than 511 labels, a negative length, a label outside [0, output_dim - 1) (the utterance is named).  Host
+ * pointers.  Evaluation mode; parameters, accumulators and statistics are not touched (same rules as tfk_ctc_greedy).
+ * flags: 0. */
+int tfk_ctc_align(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                  const int32_t* labels, const int32_t* label_len, int32_t* ali, float* score, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_align_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                      int32_t* ali, float* score, int flags);
+/* (ABI 11) Tests / tools: the alignment alone on logits [T, ld] of O classes, DEVICE pointers: seg[U + 1] = first row of every
+ * utterance, lab_off[U + 1] = first label of every utterance in labels; ali [T] (rows outside [seg[0], seg[U]) are not
+ * written), score [U] as above.  The two offset tables are read back first (the longest label sequence selects the kernel:
+ * one synchronisation of `stream`); the kernels and the call's own scratch are stream-ordered.  Labels are not validated
+ * (a value outside [0, O) is clamped). */
+int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                         const int32_t* labels, const int32_t* lab_off, int32_t* ali, float* score);
 /* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
  * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -141,6 +141,11 @@ SYMBOLS = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "tfk_ctc_beam_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p]),
+    "tfk_ctc_align": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "tfk_ctc_align_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_int]),
+    "tfk_ctc_align_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     "tfk_label_edit_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "tfk_set_prior": (c_int, [_E, c_void_p, c_size_t]),
     "tfk_reduce_region": (c_int, [_E, POINTER(c_void_p), POINTER(c_size_t)]),

@@ -69,6 +69,23 @@ size_t ctc_beam_scratch_words(int T, int U, int W);
 const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths);
 void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
                      int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score);
+// Forced alignment: the most probable path through the CTC lattice of every utterance's KNOWN label sequence (the contract
+// is the comment at tfk_ctc_align in tfkaldi_hip.h).  States as the loss: n = 2S + 1, blank, l_0, blank, ..., blank;
+// transitions as ctc_alpha_beta (stay, +1, +2 into a label that differs from the label two states back); start in state
+// 0 or 1, end in n - 1 or n - 2.  The max-plus recursion runs on the RAW logits (a per-row constant does not move the
+// argmax), so for logits that are small integers every fp32 value is exact and the tie rule is a fixed function of the
+// input: candidates in the order stay, +1, +2, a later one wins only if STRICTLY larger; at the end n - 1 wins unless
+// n - 2 is strictly larger.  Out: ali[seg[u] + t] = position j in [0, S) of the label frame t emits, -1 for a blank frame,
+// -2 on every row of an utterance without a valid path; score[u] = sum_t (z[t, class] - logsumexp(z[t, :])), -inf without
+// a path, for a zero-frame utterance 0 if S == 0 else -inf.  Rows outside every utterance are not written.
+// scratch: ctc_align_scratch_bytes(T, max_labels) bytes, 16-byte aligned; max_labels >= every label count (it selects the
+// register tile).  ctc_align_limits: NULL, or the limit a shape breaks.
+constexpr int kCtcAlignMaxFrames = (1 << 23) - 1;
+size_t ctc_align_scratch_bytes(int T, int max_labels);
+const char* ctc_align_limits(int O, int T, int U, int max_labels);
+void ctc_viterbi_align(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+                       const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch, int32_t* ali,
+                       float* score);
 // tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
 // ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
 // length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,

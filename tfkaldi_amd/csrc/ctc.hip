@@ -9,6 +9,9 @@
 //   ctc_grad         one wave per frame: state posteriors from alpha, beta and log Z, folded onto the classes in
 //                    LABEL ORDER (repeated labels
 //                    and the S+1 blanks are summed in a fixed order, so the result is bitwise reproducible)
+//   ctc_viterbi      forced alignment, ONE WAVE PER UTTERANCE: the max-plus twin of the forward sweep on the raw logits
+//                    with 2-bit back-pointers, then the backtrace over back-pointer rows staged 64 frames at a time in LDS
+//                    (ctc_row_lse supplies the rows' log-sum-exps for the score)
 // Log space, fp32, with a large finite "minus infinity" so that no inf - inf can arise.
 #include "ctc.h"
 
@@ -778,6 +781,174 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   }
 }
 
+// ---- forced alignment (the Viterbi path of the CTC lattice; the contract is stated in ctc.h) ----
+
+// one wave per row: lse[t] = log-sum-exp of logits row t (what the alignment score subtracts per frame)
+__global__ void __launch_bounds__(256)
+ctc_row_lse_kernel(const float* __restrict__ logits, int ld, int O, int T, float* __restrict__ lse) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= T) return;
+  const float* z = logits + (size_t)row * ld;
+  float mx = -INFINITY;
+  for (int c = lane; c < O; c += 64) mx = fmaxf(mx, z[c]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float se = 0.f;
+  for (int c = lane; c < O; c += 64) se += expf(z[c] - mx);
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+  if (lane == 0) lse[row] = mx + logf(se);
+}
+
+// back-pointers of one lane and one frame: 2 bits per state, the lane's R states in one unit (R = 2 uses half a byte)
+template <int R> struct BpUnit { typedef uint8_t type; };
+template <> struct BpUnit<8> { typedef uint16_t type; };
+template <> struct BpUnit<16> { typedef uint32_t type; };
+constexpr int bp_row_bytes(int R) { return 64 * (R <= 4 ? 1 : R / 4); }
+
+// ONE WAVE PER UTTERANCE, two chains of Tn dependent steps:
+//   forward    the max-plus twin of ctc_alpha_beta's forward sweep on the RAW logits of the states' classes (gathered here,
+//              PFD rows in flight in a register ring): lane-owned states, DPP neighbour shifts, the state vector re-centred
+//              on its maximum with the sum of the shifts in double.  lse3 becomes the ordered max of (stay, advance by 1,
+//              advance by 2) -- a later candidate wins only if strictly larger -- whose index is the back-pointer; a lane
+//              stores the 2-bit back-pointers of its R states of a frame as ONE unit, a frame is bp_row_bytes(R) bytes
+//   backtrace  the back-pointer rows of 64 frames (<= 16 KB) are staged in LDS by all lanes (the block before it is already
+//              in flight in registers), then walked at LDS latency: one dependent ds_read per frame instead of one L2 round
+//              trip; the walk is wave-uniform, lane j keeps the state of the block's frame j and all lanes store ali
+// score = (offset + value of the end state) - sum of the rows' log-sum-exps, both sums in double.
+template <int R>
+__global__ void __launch_bounds__(64)
+ctc_viterbi_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg,
+                   const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_off, const float* __restrict__ lse,
+                   unsigned char* __restrict__ bp, int32_t* __restrict__ ali, float* __restrict__ score) {
+  typedef typename BpUnit<R>::type Unit;
+  constexpr int kRowBytes = bp_row_bytes(R);
+  constexpr int NV = kRowBytes / 16;  // 16-byte words per lane of a 64-frame block = per frame row
+  __shared__ uint4 stage[64 * NV];
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int l0 = lab_off[u], S = lab_off[u + 1] - l0, n = 2 * S + 1;
+  if (Tn <= 0) {  // an utterance without frames: only the empty labelling has a path (the empty one)
+    if (lane == 0) score[u] = S == 0 ? 0.f : -INFINITY;
+    return;
+  }
+  const int s0 = lane * R;
+  int cls[R];
+  bool skip_in[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int s = s0 + r, j = s >> 1;
+    const bool lab = (s & 1) && s < n;
+    cls[r] = lab ? min(max(labels[l0 + j], 0), O - 1) : O - 1;  // (clamped: a bad label must not become a bad address)
+    skip_in[r] = lab && j >= 1 && labels[l0 + j] != labels[l0 + j - 1];
+  }
+  const float* zu = logits + (size_t)r0 * ld;
+  Unit* bpu = reinterpret_cast<Unit*>(bp + (size_t)r0 * kRowBytes) + lane;
+  constexpr int PFD = 8;
+  float pre[PFD][R];
+  double off = 0.0;
+  float a[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) a[r] = (s0 + r < 2 && s0 + r < n) ? zu[cls[r]] : NEG;
+  bpu[0] = (Unit)0;  // the first frame has no predecessor; the walk reads the row all the same
+#pragma unroll
+  for (int j = 0; j < PFD; ++j)
+#pragma unroll
+    for (int r = 0; r < R; ++r) pre[j][r] = zu[(size_t)min(1 + j, Tn - 1) * ld + cls[r]];
+  for (int t0 = 1; t0 < Tn; t0 += PFD) {
+#pragma unroll
+    for (int j = 0; j < PFD; ++j) {
+      const int t = t0 + j;
+      const bool live = t < Tn;
+      float cur[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        cur[r] = pre[j][r];
+        pre[j][r] = zu[(size_t)min(t + PFD, Tn - 1) * ld + cls[r]];
+      }
+      const float up1 = lane_prev(a[R - 1], NEG, lane), up2 = lane_prev(a[R - 2], NEG, lane);
+      float na[R];
+      uint32_t code = 0u;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float p1 = r >= 1 ? a[r - 1] : up1;
+        const float p2 = r >= 2 ? a[r - 2] : (r == 1 ? up1 : up2);
+        float best = a[r];
+        uint32_t d = 0u;
+        if (p1 > best) { best = p1; d = 1u; }
+        if (skip_in[r] && p2 > best) { best = p2; d = 2u; }
+        const float v = (s0 + r < n) ? best + cur[r] : NEG;
+        na[r] = live ? v : a[r];
+        code |= d << (2 * r);
+      }
+      if (j == PFD - 1) {  // compile-time: re-centre the state vector on its maximum
+        float m = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) m = fmaxf(m, na[r]);
+        m = wave_max(m);
+        if (live && m > -1e29f) {
+          off += (double)m;
+#pragma unroll
+          for (int r = 0; r < R; ++r) na[r] = fmaxf(na[r] - m, NEG);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) a[r] = na[r];
+      if (live) bpu[(size_t)t * (kRowBytes / sizeof(Unit))] = (Unit)code;  // (a surplus step holds the state and stores nothing)
+    }
+  }
+  // the end state: n - 1 unless n - 2 is strictly larger
+  float e1 = -INFINITY, e2 = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (s0 + r == n - 1) e1 = a[r];
+    if (s0 + r == n - 2) e2 = a[r];
+  }
+  e1 = wave_max(e1);
+  e2 = wave_max(e2);
+  int s = e2 > e1 ? n - 2 : n - 1;
+  const float vend = fmaxf(e1, e2);
+  if (!(vend > -1e29f)) {  // too short for its labels: no path
+    for (int f = lane; f < Tn; f += 64) ali[r0 + f] = -2;
+    if (lane == 0) score[u] = -INFINITY;
+    return;
+  }
+  double ls = 0.0;
+  for (int f = lane; f < Tn; f += 64) ls += (double)lse[r0 + f];
+  for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+  if (lane == 0) score[u] = (float)((off + (double)vend) - ls);
+
+  __threadfence();  // the back-pointers this wave stored, read back by other lanes
+  const uint4* g = reinterpret_cast<const uint4*>(bp + (size_t)r0 * kRowBytes);
+  const int words = Tn * NV;  // the utterance's rows in 16-byte words (Tn <= T, NV <= 16)
+  uint4 nxt[NV];
+  const int nblk = (Tn + 63) >> 6;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int w = (nblk - 1) * 64 * NV + i * 64 + lane;
+    nxt[i] = w < words ? g[w] : make_uint4(0u, 0u, 0u, 0u);
+  }
+  const uint32_t* rows = reinterpret_cast<const uint32_t*>(stage);
+  for (int b = nblk - 1; b >= 0; --b) {
+    __syncthreads();  // (one wave: orders the walk's reads before the next block's writes)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) stage[i * 64 + lane] = nxt[i];
+    if (b > 0) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) nxt[i] = g[(b - 1) * 64 * NV + i * 64 + lane];  // a full block of the utterance's rows
+    }
+    __syncthreads();
+    const int f0 = 64 * b, cnt = min(64, Tn - f0);
+    int mine = 0;
+    for (int j = cnt - 1; j >= 0; --j) {
+      if (lane == j) mine = s;
+      const int bit = R == 2 ? 8 * (s >> 1) + 2 * (s & 1) : 2 * s;
+      const uint32_t w = rows[j * (kRowBytes / 4) + (bit >> 5)];
+      s = max(s - (int)((w >> (bit & 31)) & 3u), 0);
+    }
+    if (lane < cnt) ali[r0 + f0 + lane] = (mine & 1) ? mine >> 1 : -1;
+  }
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -826,6 +997,36 @@ void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, c
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie, hyp,
                      hyp_len, score);
+}
+
+// scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]
+size_t ctc_align_scratch_bytes(int T, int max_labels) {
+  return (size_t)(T > 0 ? T : 0) * ((size_t)bp_row_bytes(regs_for(max_labels)) + sizeof(float));
+}
+
+const char* ctc_align_limits(int O, int T, int U, int max_labels) {
+  if (O < 2) return "output_dim < 2 (one label + blank)";
+  if (max_labels < 0) return "a negative length";
+  if (max_labels > kCtcMaxLabels) return "more than 511 labels in one utterance";
+  if (T < 0 || T > kCtcAlignMaxFrames) return "more than 8388607 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  return nullptr;
+}
+
+void ctc_viterbi_align(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+                       const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch, int32_t* ali,
+                       float* score) {
+  if (U <= 0) return;
+  const int R = regs_for(max_labels);
+  unsigned char* bp = static_cast<unsigned char*>(scratch);
+  float* lse = reinterpret_cast<float*>(bp + (size_t)(T > 0 ? T : 0) * bp_row_bytes(R));
+  if (T > 0) hipLaunchKernelGGL(ctc_row_lse_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, lse);
+  switch (R) {
+    case 2: hipLaunchKernelGGL(ctc_viterbi_kernel<2>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
+    case 4: hipLaunchKernelGGL(ctc_viterbi_kernel<4>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
+    case 8: hipLaunchKernelGGL(ctc_viterbi_kernel<8>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
+    default: hipLaunchKernelGGL(ctc_viterbi_kernel<16>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
+  }
 }
 
 void label_edit_distance(hipStream_t s, const int32_t* hyp, const int32_t* hyp_off, const int32_t* hyp_cnt,

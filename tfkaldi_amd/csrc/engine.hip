@@ -66,14 +66,14 @@ struct LayerLayout {
 
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
-  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_COUNT
+  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
                                      "act_forward",             "hidden_backward",  "colsum",          "softmax_xent",
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
                                      "misc",                    "ctc_best_path",    "edit_distance",
-                                     "ctc_beam_search"};
+                                     "ctc_beam_search",         "ctc_align"};
 
 struct ProfRec {
   int family;
@@ -188,6 +188,9 @@ struct tfk_engine {
   // prefix beam search (tfk_ctc_beam): the trie table of ctc_beam_search
   unsigned long long* ctc_trie = nullptr;
   size_t ctc_cap_trie = 0;
+  // forced alignment (tfk_ctc_align): the back-pointer rows and row log-sum-exps of ctc_viterbi_align
+  unsigned char* ctc_bp = nullptr;
+  size_t ctc_cap_bp = 0;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1788,7 +1791,7 @@ int tfk_destroy(tfk_engine* e) {
   if (e->ws_splitk) hipFree(e->ws_splitk);
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
-                  (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie})
+                  (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp})
     if (p) hipFree(p);
   if (e->h_dec) hipHostFree(e->h_dec);
   for (hipEvent_t ev : e->post_ev) hipEventDestroy(ev);
@@ -2509,6 +2512,112 @@ int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O
   ctc_beam_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, trie, hyp, hyp_len, score);
   const hipError_t launched = hipGetLastError();
   const hipError_t freed = hipFreeAsync(trie, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+// Forced alignment (the Viterbi path of every utterance's known label sequence; the contract: tfkaldi_hip.h):
+// evaluation-mode forward as tfk_posteriors, then ctc_viterbi_align on the logits in HBM; T + U words go back to the host.
+static int ctc_align_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                          const int32_t* labels, const int32_t* label_len, int32_t* ali, float* score, int flags,
+                          const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
+    return fail(-1, "flags %d: tfk_ctc_align takes 0, tfk_ctc_align_raw 0 or TFK_RAW_DEVICE", flags);
+  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
+  if (!X) return fail(-1, "X is NULL");
+  if (!ali || !score) return fail(-1, "ali / score is NULL");
+  if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC align: utt_len / label_len is NULL or no utterances");
+  {  // what ctc_stage would refuse as well, with the utterance named
+    int64_t first = 0;
+    for (int u = 0; u < U; ++u) {
+      const int32_t n = label_len[u];
+      if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
+      if (n > kCtcMaxLabels) return fail(-1, "CTC align: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
+      if (n > 0 && !labels) return fail(-1, "CTC align: labels is NULL");
+      for (int32_t i = 0; i < n; ++i)
+        if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
+          return fail(-1, "CTC align: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
+      first += n;
+    }
+  }
+  const CtcSpec c = {utt_len, U, labels, label_len};
+  const size_t back = (size_t)T + (size_t)U;  // [ali | score]
+  int max_labels = 0;
+  Pass p;
+  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
+    CHK(ctc_stage(e, c, T, true, &max_labels));
+    if (const char* why = ctc_align_limits(e->O, T, U, max_labels)) return fail(-1, "CTC align (T %d, U %d): %s", T, U, why);
+    CHK(grow(e, &e->ctc_bp, &e->ctc_cap_bp, ctc_align_scratch_bytes(T, max_labels)));
+    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, back);
+  }));
+  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
+  int32_t* d_ali = e->ctc_dec;
+  float* d_score = reinterpret_cast<float*>(d_ali + T);
+  {
+    ProfScope ps(e, KF_CTC_ALIGN, 0, 4.0 * T * e->O + 2.0 * (double)ctc_align_scratch_bytes(T, max_labels) + 4.0 * T);
+    ctc_viterbi_align(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, e->ctc_lab, e->ctc_lab_off, max_labels,
+                      e->ctc_bp, d_ali, d_score);
+  }
+  HIPCHK(hipGetLastError());
+  CHK(finish_slot(e, flags, p.slot_before));
+  if (back > e->h_dec_cap) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
+    e->h_dec = nullptr;
+    e->h_dec_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
+    e->h_dec_cap = back + back / 2;
+  }
+  HIPCHK(hipMemcpyAsync(e->h_dec, d_ali, back * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  remember_pass(e, T, p.nact, p.call, p.Xd);
+  CHK(check_kernel_errors(e));
+  memcpy(ali, e->h_dec, (size_t)T * sizeof(int32_t));
+  memcpy(score, e->h_dec + T, (size_t)U * sizeof(float));
+  return 0;
+}
+
+int tfk_ctc_align(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                  const int32_t* labels, const int32_t* label_len, int32_t* ali, float* score, int flags) {
+  return ctc_align_impl(e, X, ldx, T, utt_len, U, labels, label_len, ali, score, flags, nullptr);
+}
+int tfk_ctc_align_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                      int32_t* ali, float* score, int flags) {
+  const RawSpec r = {utt_len, U, context_width, cmvn};
+  if (!utt_len) return fail(-1, "utt_len is NULL");
+  return ctc_align_impl(e, raw, ldraw, T, utt_len, U, labels, label_len, ali, score, flags, &r);
+}
+int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                         const int32_t* labels, const int32_t* lab_off, int32_t* ali, float* score) {
+  if (U < 0) return fail(-1, "U = %d < 0", U);
+  if (U == 0) return 0;
+  if (!seg || !lab_off || !score || (T > 0 && (!logits || !ali))) return fail(-1, "logits / seg / lab_off / ali / score is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  // The register tile follows the longest label sequence, which only the device knows: the two offset tables come back
+  // first (2 (U + 1) words, one synchronisation); everything after that is stream-ordered.
+  std::vector<int32_t> h(2 * ((size_t)U + 1));
+  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  int max_labels = 0;
+  for (int u = 0; u < U; ++u) {
+    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
+    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
+    max_labels = n > max_labels ? n : max_labels;
+  }
+  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC align: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
+  if (const char* why = ctc_align_limits(O, T, U, max_labels)) return fail(-1, "CTC align (O %d, T %d, U %d): %s", O, T, U, why);
+  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC align: labels is NULL");
+  void* scratch = nullptr;  // the call's own scratch, released in stream order
+  const size_t bytes = ctc_align_scratch_bytes(T, max_labels);
+  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
+  ctc_viterbi_align((hipStream_t)stream, logits, (int)ld, O, T, seg, U, labels, lab_off, max_labels, scratch, ali, score);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
   HIPCHK(launched);
   HIPCHK(freed);
   return 0;

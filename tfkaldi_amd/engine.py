@@ -497,6 +497,79 @@ class Engine(object):
             self._raw_release()
         return self._beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits)
 
+    # ---- CTC forced alignment: the Viterbi path of the known label sequence, per frame the label POSITION it emits ----
+    @staticmethod
+    def _align_refs(utt_lens, labels, label_lens):
+        utt_lens = np.ascontiguousarray(utt_lens, dtype=np.int32).reshape(-1)
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
+        if label_lens.size != utt_lens.size or int(label_lens.sum()) != labels.size:
+            raise ValueError("alignment: %d label counts (sum %d) for %d utterances and %d labels"
+                             % (label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
+        return utt_lens, labels, label_lens
+
+    @staticmethod
+    def _align_result(ali, score, utt_lens):
+        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
+        return [ali[s:s + n].copy() if sc > -np.inf else None for s, n, sc in zip(starts, utt_lens, score)], score
+
+    @staticmethod
+    def _align_empty(utt_lens, label_lens):
+        """only zero-frame utterances: the empty alignment with score 0 where there is nothing to emit, no path otherwise"""
+        score = np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32)
+        return Engine._align_result(np.zeros(0, dtype=np.int32), score, utt_lens)
+
+    def ctc_align(self, X, utt_lens, labels, label_lens):
+        """Forced alignment of the utterances X [sum(utt_lens), F] to their label sequences (tfk_ctc_align; the algorithm and
+        its tie rule are stated in include/tfkaldi_hip.h): the most probable CTC path of every utterance.  labels back to
+        back, label_lens per utterance, as accumulate_ctc.  Returns (alis, scores): alis[u] int32 [utt_lens[u]], per frame
+        the POSITION in the utterance's label sequence of the label the frame emits, -1 for a blank frame -- None for an
+        utterance too short for its labels; scores float32 [U], the natural-log probability of the path (-inf for None)."""
+        X = _f32(X)
+        utt_lens, labels, label_lens = self._align_refs(utt_lens, labels, label_lens)
+        if int(utt_lens.sum()) != X.shape[0]:
+            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
+        if X.shape[0] == 0:
+            return self._align_empty(utt_lens, label_lens)
+        ali = np.empty(X.shape[0], dtype=np.int32)
+        score = np.empty(utt_lens.size, dtype=np.float32)
+        check(self.lib.tfk_ctc_align(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
+                                     utt_lens.ctypes.data_as(c_void_p), utt_lens.size, labels.ctypes.data_as(c_void_p),
+                                     label_lens.ctypes.data_as(c_void_p), ali.ctypes.data_as(c_void_p),
+                                     score.ctypes.data_as(c_void_p), 0))
+        return self._align_result(ali, score, utt_lens)
+
+    def ctc_align_raw(self, raw, utt_lens, context_width, labels, label_lens, cmvn=None):
+        """ctc_align on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        flags = 0
+        utt_lens, labels, label_lens = self._align_refs(utt_lens, labels, label_lens)
+        if self._on_device(raw):
+            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
+            flags |= _lib.RAW_DEVICE
+            cols = raw.shape[1]
+        else:
+            raw, utt_lens = self._raw_batch(raw, utt_lens)
+            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
+        if rows == 0:
+            self._raw_release()
+            return self._align_empty(utt_lens, label_lens)
+        if cmvn is not None:
+            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
+            if cmvn.shape != (utt_lens.size, 2, cols):
+                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
+        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
+        ali = np.empty(rows, dtype=np.int32)
+        score = np.empty(utt_lens.size, dtype=np.float32)
+        try:
+            check(self.lib.tfk_ctc_align_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
+                                             int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
+                                             label_lens.ctypes.data_as(c_void_p), ali.ctypes.data_as(c_void_p),
+                                             score.ctypes.data_as(c_void_p), flags))
+        finally:
+            self._raw_release()
+        return self._align_result(ali, score, utt_lens)
+
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):
         X = _f32(X)

@@ -7,6 +7,29 @@ from ..processing.feature_reader import Unspliced, cmvn_table
 from .classifiers.dnn import ModelSaver
 
 
+def ctc_segments(ali, labels):
+    """The segments of one utterance's alignment (Decoder.ctc_align): `ali` per frame the position of the label the frame
+    emits, -1 for a blank frame; `labels` the utterance's label sequence.  Returns [(label, first_frame,
+    end_frame_exclusive)], one entry per label, in order: the frames that emit that label (consecutive in a valid
+    alignment); blank frames belong to no segment.  `ali` None (no valid alignment) gives None."""
+    if ali is None:
+        return None
+    ali = np.asarray(ali).reshape(-1)
+    labels = np.asarray(labels).reshape(-1)
+    frames = np.nonzero(ali >= 0)[0]
+    pos = ali[frames]
+    if pos.size and (pos.max() >= labels.size or np.any(np.diff(pos) < 0)):
+        raise ValueError("not an alignment of %d labels: positions must be non-decreasing and below the label count"
+                         % labels.size)
+    first = np.searchsorted(pos, np.arange(labels.size), side="left")
+    last = np.searchsorted(pos, np.arange(labels.size), side="right")
+    if np.any(first == last):
+        raise ValueError("label %d of %d emits no frame" % (int(np.nonzero(first == last)[0][0]), labels.size))
+    if np.any(frames[last - 1] - frames[first] != last - 1 - first):
+        raise ValueError("the frames of one label are not consecutive")
+    return [(int(k), int(frames[a]), int(frames[b - 1]) + 1) for k, a, b in zip(labels, first, last)]
+
+
 class _Graph(object):
     def finalize(self):
         pass
@@ -107,6 +130,30 @@ class Decoder(object):
                                     for u in utterances])
             hyps, scores, _ = self.engine.ctc_beam(stack, lens, beam_width=beam_width, top_paths=top_paths)
         return hyps, scores
+
+    def ctc_align(self, utterances, targets):
+        """Forced alignment of a CTC model (tfk_ctc_align; the algorithm is stated in include/tfkaldi_hip.h): every
+        utterance in ONE forward pass, the Viterbi path of its known label sequence `targets[u]` (one int label array per
+        utterance) on the device.  Returns (alis, scores): alis[u] int32 [frames of u], per frame the position in
+        targets[u] of the label the frame emits, -1 for a blank frame (None for an utterance too short for its labels);
+        scores float32 [U], the natural-log probability of the alignment.  ctc_segments turns an alignment into (label,
+        first frame, end frame) triples.  All `Unspliced` -> device-side splice, as decode_batch."""
+        if len(utterances) != len(targets):
+            raise ValueError("%d utterances, %d label sequences" % (len(utterances), len(targets)))
+        if len(utterances) == 0:
+            return [], np.zeros(0, dtype=np.float32)
+        lens = [u.shape[0] for u in utterances]
+        for u in utterances:
+            self._check(u)
+        targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        labels = np.concatenate(targets) if targets else np.zeros(0, dtype=np.int32)
+        label_lens = [t.size for t in targets]
+        if all(isinstance(u, Unspliced) for u in utterances):
+            return self.engine.ctc_align_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
+                                             utterances[0].context_width, labels, label_lens, cmvn=cmvn_table(utterances))
+        stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
+                                for u in utterances])
+        return self.engine.ctc_align(stack, lens, labels, label_lens)
 
     def set_prior(self, prior):
         self.engine.set_prior(prior)

@@ -6,7 +6,10 @@ hypotheses: the edit distance's worst case) and once with the blank biased so th
 length; then, on the same two workloads, the beam leg: prefix beam search on the device (tfk_ctc_beam) at W = 1, 10, 100 --
 ms per call, the engine profiler's time of the ctc_beam_search kernel, label error rate greedy vs beam, the largest
 |device - float64| of a best score, and the host alternative (the float64 numpy restatement the tests use, timed on ONE
-utterance of the same logits and scaled to the batch).  `--decode-only` skips the training step (e.g. under rocprofv3)."""
+utterance of the same logits and scaled to the batch); then the align leg: forced alignment of every utterance to its
+reference on the device (tfk_ctc_align) -- ms per call, the profiler's time of the ctc_align kernels and that time per frame
+step, and the host alternative (the float64 numpy restatement of the tests on the same logits, all utterances).
+`--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone."""
 import os
 import sys
 import time
@@ -19,6 +22,7 @@ from tfkaldi_amd.engine import Engine  # noqa: E402
 # the beam leg's host alternative is the float64 numpy restatement the tests check the device against; it lives in the test
 # tree (tests/test_ctc_beam_host.py), not in the product
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from test_ctc_align_host import viterbi_align  # noqa: E402
 from test_ctc_beam_host import prefix_beam_search  # noqa: E402
 
 
@@ -34,6 +38,11 @@ def main():
     raw = rng.standard_normal((T, F // 11)).astype(np.float32)  # 40-dim unspliced frames, context 5
     labels = rng.integers(0, O - 1, size=U * S).astype(np.int32)
     utt, lab = [Tu] * U, [S] * U
+    if "--align-only" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        align_leg(eng, X, utt, labels, np.asarray(lab), "random output weights")
+        eng.close()
+        return
     if "--decode-only" not in sys.argv:
         train_leg(eng, X, raw, utt, labels, lab, T)
     decode_leg(eng, X, utt, labels, lab, rng)
@@ -134,6 +143,7 @@ def decode_leg(eng, X, utt, labels, lab, rng):
         print("    eval forward device time %.1f us, decode kernels %.1f us (%.1f %% of the forward)" % (fwd * 1e3, dec * 1e3,
                                                                                                      100.0 * dec / fwd))
         beam_leg(eng, X, utt, labels, lab, case, edits)
+        align_leg(eng, X, utt, labels, lab, case)
 
 
 def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
@@ -161,6 +171,36 @@ def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
               % (case, W, ms, kern, kern * 1e3 / max(utt), edits.sum() / np.sum(lab), greedy_edits.sum() / np.sum(lab),
                  scores[0, 0], s64[0, 0], abs(scores[0, 0] - s64[0, 0]), np.array_equal(hyps[0][0], h64[0][0]), host,
                  host * len(utt), len(utt)))
+
+
+def align_leg(eng, X, utt, labels, lab, case):
+    K = 20
+    alis, scores = eng.ctc_align(X, utt, labels, lab)
+    for _ in range(2):
+        eng.ctc_align(X, utt, labels, lab)
+    t0 = time.perf_counter()
+    for _ in range(K):
+        eng.ctc_align(X, utt, labels, lab)
+    ms = (time.perf_counter() - t0) / K * 1e3
+    eng.profile_begin()
+    for _ in range(K):
+        eng.ctc_align(X, utt, labels, lab)
+    stats = {s["name"]: s for s in eng.profile_end()}
+    kern = stats["ctc_align"]["total_ms"] / K
+    zs = np.split(eng.posteriors(X, raw_logits=True), np.cumsum(utt)[:-1])
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    t0 = time.perf_counter()
+    want = [viterbi_align(z, r) for z, r in zip(zs, refs)]
+    host = (time.perf_counter() - t0) * 1e3
+    same = sum(np.array_equal(a, w[0]) for a, w in zip(alis, want))
+    diff = max(abs(float(s) - w[1]) for s, w in zip(scores, want))
+    emitting = np.mean([np.mean(a >= 0) for a in alis])
+    print("  align (%s): tfk_ctc_align %8.3f ms/call, ctc_align kernels %8.3f ms (%.3f us per frame step of the longest "
+          "utterance); %d labels per utterance, %.0f %% of the frames emit a label, mean score %.2f; host alternative (numpy "
+          "float64 restatement, %d utterances) %.0f ms; same path as float64 on %d of %d utterances, largest |device - "
+          "float64| score %.1e"
+          % (case, ms, kern, kern * 1e3 / max(utt), int(np.mean(lab)), 100.0 * emitting, float(np.mean(scores)), len(utt),
+             host, same, len(utt), diff))
 
 
 if __name__ == "__main__":
