@@ -85,6 +85,33 @@ def test_raw_entry_equals_host_spliced(gpu):
     eng.close()
 
 
+def test_refused_cmvn_table_releases_the_device_tensor(gpu):
+    """a device tensor with a wrong-shaped cmvn table: ValueError, no reference to the tensor stays parked in the engine, and
+    the next valid call gives the bytes it gave before"""
+    import torch
+    from tfkaldi_amd.processing.feature_reader import Unspliced, cmvn_table
+    rng = np.random.default_rng(8)
+    D, C = 4, 2
+    eng, _ = make_pair(rng, max_frames=256, **dict(KW, input_dim=D * (2 * C + 1), output_dim=12))
+    utts = [Unspliced(rng.standard_normal((n, D)) * 2 + 1, C,
+                      np.stack([rng.standard_normal(D), 0.5 + rng.random(D)]).astype(np.float32)) for n in (40, 5, 63, 17)]
+    lens = [u.shape[0] for u in utts]
+    labels, lab = _refs(rng, len(utts), 12)
+    table = cmvn_table(utts)
+    raw = torch.from_numpy(np.concatenate([np.asarray(u) for u in utts]).astype(np.float32)).cuda()
+    call = lambda cmvn: eng.ctc_greedy_raw(raw, lens, C, cmvn=cmvn, labels=labels, label_lens=lab)
+    before = call(table)
+    assert sum(h.size for h in before[0]) > 5
+    for bad in (table[:3], table[:, :1], table[:, :, :D - 1]):
+        with pytest.raises(ValueError, match="cmvn table"):
+            call(bad)
+        assert eng._raw_pending is None
+    after = call(table)
+    assert len(after[0]) == len(before[0])
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(after[0], before[0])) and after[1].tobytes() == before[1].tobytes()
+    eng.close()
+
+
 def test_known_answers_from_a_zero_output_layer(gpu):
     """right after initialize() the output layer is zero: every logit is exactly 0, class 0 wins every frame's tie"""
     from tfkaldi_amd import _lib
@@ -197,9 +224,22 @@ def test_errors_leave_the_engine_usable(gpu):
     eng.close()
 
 
-def test_decoding_between_steps_has_no_side_effects(gpu):
-    """a training trace with ctc_greedy calls between (and inside) the steps is bit-identical to one without (no dropout)"""
-    def trace(decode):
+# the forward-only calls that share the engine's pass plumbing; refs None: the call without references (forced alignment has
+# no such form, posteriors takes none)
+FORWARD_ONLY = {
+    "posteriors": lambda eng, X, utt, refs: eng.posteriors(X, raw_logits=True),
+    "ctc_greedy": lambda eng, X, utt, refs: eng.ctc_greedy(X, utt, *(refs or ())),
+    "ctc_beam": lambda eng, X, utt, refs: eng.ctc_beam(X, utt, 8, 2, *(refs or ())),
+    "ctc_align": lambda eng, X, utt, refs: eng.ctc_align(X, utt, *refs) if refs else None,
+}
+
+
+@pytest.mark.parametrize("call", sorted(FORWARD_ONLY))
+def test_decoding_between_steps_has_no_side_effects(gpu, call):
+    """a training trace with forward-only calls between (and inside) the steps is bit-identical to one without (no dropout)"""
+    decode = FORWARD_ONLY[call]
+
+    def trace(on):
         rng = np.random.default_rng(21)
         eng, _ = make_pair(rng, max_frames=256, **KW)
         data = np.random.default_rng(22)
@@ -207,16 +247,16 @@ def test_decoding_between_steps_has_no_side_effects(gpu):
         for step in range(4):
             utt = [25 + step, 18]
             X = (data.standard_normal((sum(utt), KW["input_dim"])) * 1.5).astype(np.float32)
-            labels, lab = _refs(data, 2, KW["output_dim"], 2, 6)
-            if decode:
-                eng.ctc_greedy(X[::-1].copy(), utt[::-1], labels, lab[::-1])
+            labels, lab = _refs(data, 2, KW["output_dim"], 2, 6)  # (2..6 labels: every utterance is long enough for them)
+            if on:
+                decode(eng, X[::-1].copy(), utt[::-1], (labels, lab[::-1]))
             eng.accumulate_ctc(X[:utt[0]], [utt[0]], labels[:lab[0]], [lab[0]])
-            if decode:
-                eng.ctc_greedy(X, utt)
+            if on:
+                decode(eng, X, utt, (labels, lab) if call == "ctc_align" else None)
             eng.accumulate_ctc(X[utt[0]:], [utt[1]], labels[lab[0]:], [lab[1]], last=True)
             losses.append(eng.apply())
-            if decode:
-                eng.ctc_greedy(X, utt, labels, lab)
+            if on:
+                decode(eng, X, utt, (labels, lab))
         from tfkaldi_amd import _lib
         sums = [eng.param_checksum(w) for w in (0, 2)]
         stats = [eng.get(kind, l).tobytes() for l in range(eng.L) for kind in (_lib.BN_MOVING_MEAN, _lib.BN_MOVING_VAR)]

@@ -1365,6 +1365,20 @@ int grow(tfk_engine* e, Tp** p, size_t* cap, size_t need) {
   *cap = n;
   return 0;
 }
+// The same for a pinned host buffer.  slack: one and a half times the need, for buffers that creep up call by call;
+// sync: the stream may still be copying into the old buffer (a site that guards its buffer with an event passes false).
+template <class Tp>
+int grow_pinned(tfk_engine* e, Tp** p, size_t* cap, size_t need, bool slack, bool sync = true) {
+  if (need <= *cap) return 0;
+  if (sync) HIPCHK(hipStreamSynchronize(e->stream));
+  if (*p) HIPCHK(hipHostFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  const size_t n = slack ? need + need / 2 : need;
+  HIPCHK(hipHostMalloc((void**)p, n * sizeof(Tp), hipHostMallocDefault));
+  *cap = n;
+  return 0;
+}
 // Validate the utterance / label tables of a CTC batch and stage (seg, lab_off, labels) in e->ctc_seg / ctc_lab_off /
 // ctc_lab on the engine's stream.  Labels follow tf.nn.ctc_loss: values in [0, O - 1) (the blank is the LAST class), at most
 // kCtcMaxLabels per utterance.  label_len may be NULL only when !need_labels (no references: every label count is 0).
@@ -1396,12 +1410,7 @@ int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max
     const size_t need = 2 * ((size_t)c.U + 1) + (size_t)total;
     if (!e->ctc_staged[k]) HIPCHK(hipEventCreateWithFlags(&e->ctc_staged[k], hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(e->ctc_staged[k]));
-    if (need > e->h_ctc_cap[k]) {
-      if (e->h_ctc[k]) HIPCHK(hipHostFree(e->h_ctc[k]));
-      e->h_ctc[k] = nullptr;
-      e->h_ctc_cap[k] = need + need / 2;
-      HIPCHK(hipHostMalloc((void**)&e->h_ctc[k], e->h_ctc_cap[k] * sizeof(int32_t), hipHostMallocDefault));
-    }
+    CHK(grow_pinned(e, &e->h_ctc[k], &e->h_ctc_cap[k], need, /*slack=*/true, /*sync=*/false));  // (the event above guards it)
     int32_t* h = e->h_ctc[k];
     memcpy(h, seg.data(), ((size_t)c.U + 1) * sizeof(int32_t));
     memcpy(h + c.U + 1, off.data(), ((size_t)c.U + 1) * sizeof(int32_t));
@@ -1460,6 +1469,12 @@ struct RawSpec {  // non-null utt_len selects the device-side splice
   int U, context;
   const float* cmvn;  // nullable [U, 2, raw_dim]
 };
+// the spec of a *_raw entry point from its arguments
+int raw_spec(RawSpec* r, const int32_t* utt_len, int U, int context_width, const float* cmvn) {
+  if (!utt_len) return fail(-1, "utt_len is NULL");
+  *r = {utt_len, U, context_width, cmvn};
+  return 0;
+}
 
 // ================= stacked passes (struct Stack above) =================
 
@@ -1660,6 +1675,41 @@ int train_or_eval(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, 
   if (!X || (!y && !ctc)) return fail(-1, "X / y is NULL");
   CHK(check_raw_flags(raw, flags));
   return run_pass(e, X, ldx, y, T, flags, train, raw, ctc);
+}
+
+// The forward-only CTC entries (tfk_ctc_greedy / _beam / _align, plain and raw) share one pass.  Each entry checks the common
+// arguments with decode_args, then its own, and calls decode_pass with the two things that are its own on the device:
+// extra_tables() grows its scratch (after ctc_stage: *max_labels is known), launch() enqueues its kernels on e->logits.
+// decode_pass stages the input and the CTC tables, grows e->ctc_dec to dev_words, runs the evaluation-mode forward and the
+// launches, brings back_words words from e->ctc_dec + back_offset to the pinned e->h_dec (which holds the whole tail of the
+// layout) and waits; the entry then scatters e->h_dec into the caller's arrays.
+int decode_args(const tfk_engine* e, const char* who, const float* X, int T, int flags, const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (flags & ~(raw ? TFK_RAW_DEVICE : 0)) return fail(-1, "flags %d: %s takes 0, %s_raw 0 or TFK_RAW_DEVICE", flags, who, who);
+  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
+  if (!X) return fail(-1, "X is NULL");
+  return 0;
+}
+template <class Tables, class Launch>
+int decode_pass(tfk_engine* e, const float* X, int64_t ldx, int T, int flags, const RawSpec* raw, const CtcSpec& c,
+                bool need_labels, size_t dev_words, size_t back_offset, size_t back_words, int* max_labels,
+                Tables extra_tables, Launch launch) {
+  Pass p;
+  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
+    CHK(ctc_stage(e, c, T, need_labels, max_labels));
+    CHK(extra_tables());
+    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, dev_words);
+  }));
+  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
+  launch();
+  HIPCHK(hipGetLastError());
+  CHK(finish_slot(e, flags, p.slot_before));
+  CHK(grow_pinned(e, &e->h_dec, &e->h_dec_cap, dev_words - back_offset, /*slack=*/true));
+  HIPCHK(hipMemcpyAsync(e->h_dec, e->ctc_dec + back_offset, back_words * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  remember_pass(e, T, p.nact, p.call, p.Xd);
+  return check_kernel_errors(e);
 }
 
 // Cut the k micro-batches of a call into runs: consecutive segments that fit one stacked pass, and single segments that
@@ -1902,14 +1952,14 @@ int tfk_eval_accumulate(tfk_engine* e, const float* X, int64_t ldx, const int32_
 }
 int tfk_accumulate_raw(tfk_engine* e, const float* raw, int64_t ldraw, const int32_t* y, int32_t T,
                        const int32_t* utt_len, int32_t U, int32_t context_width, const float* cmvn, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return train_or_eval(e, raw, ldraw, y, T, flags, 1, &r);
 }
 int tfk_eval_accumulate_raw(tfk_engine* e, const float* raw, int64_t ldraw, const int32_t* y, int32_t T,
                             const int32_t* utt_len, int32_t U, int32_t context_width, const float* cmvn, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return train_or_eval(e, raw, ldraw, y, T, flags & ~TFK_LAST_MICROBATCH, 0, &r);
 }
 
@@ -2015,16 +2065,16 @@ int tfk_eval_accumulate_ctc(tfk_engine* e, const float* X, int64_t ldx, int32_t 
 int tfk_accumulate_ctc_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
                            int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
                            int flags) {
-  if (!utt_len) return fail(-1, "utt_len is NULL");
-  const RawSpec r = {utt_len, U, context_width, cmvn};
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   const CtcSpec c = {utt_len, U, labels, label_len};
   return train_or_eval(e, raw, ldraw, nullptr, T, flags, 1, &r, &c);
 }
 int tfk_eval_accumulate_ctc_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
                                 int32_t U, int32_t context_width, const float* cmvn, const int32_t* labels,
                                 const int32_t* label_len, int flags) {
-  if (!utt_len) return fail(-1, "utt_len is NULL");
-  const RawSpec r = {utt_len, U, context_width, cmvn};
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   const CtcSpec c = {utt_len, U, labels, label_len};
   return train_or_eval(e, raw, ldraw, nullptr, T, flags & ~TFK_LAST_MICROBATCH, 0, &r, &c);
 }
@@ -2323,14 +2373,7 @@ static int posteriors_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t N
       remember_pass(e, N, nact, call, Xd);
       return 0;
     }
-    const size_t need = (size_t)N * e->O;
-    if (need > e->h_post_floats) {
-      HIPCHK(hipStreamSynchronize(e->stream));
-      if (e->h_post) hipHostFree(e->h_post);
-      e->h_post = nullptr;
-      HIPCHK(hipHostMalloc((void**)&e->h_post, need * sizeof(float), hipHostMallocDefault));
-      e->h_post_floats = need;
-    }
+    CHK(grow_pinned(e, &e->h_post, &e->h_post_floats, (size_t)N * e->O, /*slack=*/false));
     HIPCHK(hipMemcpy2DAsync(e->h_post, (size_t)e->O * 4, src, (size_t)e->ldO * 4,
                             (size_t)e->O * 4, N, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -2348,8 +2391,8 @@ int tfk_posteriors(tfk_engine* e, const float* X, int64_t ldx, int32_t N, float*
 }
 int tfk_posteriors_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t N, const int32_t* utt_len, int32_t U,
                        int32_t context_width, const float* cmvn, float* out, int64_t ldo, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return posteriors_impl(e, raw, ldraw, N, out, ldo, flags, &r);
 }
 
@@ -2359,50 +2402,25 @@ int tfk_posteriors_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t N
 static int ctc_greedy_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
                            const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len,
                            int32_t* edits, int flags, const RawSpec* raw) {
-  if (!e) return fail(-1, "engine is NULL");
-  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
-    return fail(-1, "flags %d: tfk_ctc_greedy takes 0, tfk_ctc_greedy_raw 0 or TFK_RAW_DEVICE", flags);
-  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
-  if (!X) return fail(-1, "X is NULL");
+  CHK(decode_args(e, "tfk_ctc_greedy", X, T, flags, raw));
   if (!hyp || !hyp_len) return fail(-1, "hyp / hyp_len is NULL");
   if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
-  const CtcSpec c = {utt_len, U, ref_labels, ref_len};
+  const size_t back = (size_t)T + 2 * (size_t)U;  // [class ids | hypotheses | lengths | distances], back from `hypotheses` on
   int max_ref = 0;
-  Pass p;
-  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
-    CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
-    const size_t words = 2 * (size_t)T + 2 * (size_t)U;  // [class ids | hypotheses | lengths | distances]
-    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, words);
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, ref_labels, ref_len}, edits != nullptr, T + back, T,
+                  edits ? back : back - U, &max_ref, NoTables(), [&] {
+    int32_t* d_cls = e->ctc_dec;
+    int32_t* d_hyp = d_cls + T;
+    int32_t* d_len = d_hyp + T;
+    {
+      ProfScope ps(e, KF_CTC_BEST_PATH, 0, 4.0 * T * e->O + 12.0 * T);
+      ctc_best_path(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, d_cls, d_hyp, d_len);
+    }
+    if (edits) {
+      ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
+      label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_len + U);
+    }
   }));
-  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
-  int32_t* d_cls = e->ctc_dec;
-  int32_t* d_hyp = d_cls + T;
-  int32_t* d_len = d_hyp + T;
-  int32_t* d_dist = d_len + U;
-  {
-    ProfScope ps(e, KF_CTC_BEST_PATH, 0, 4.0 * T * e->O + 12.0 * T);
-    ctc_best_path(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, d_cls, d_hyp, d_len);
-  }
-  if (edits) {
-    ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
-    label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_dist);
-  }
-  HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, p.slot_before));
-  const size_t back = (size_t)T + 2 * (size_t)U;
-  if (back > e->h_dec_cap) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
-    e->h_dec = nullptr;
-    e->h_dec_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
-    e->h_dec_cap = back + back / 2;
-  }
-  HIPCHK(hipMemcpyAsync(e->h_dec, d_hyp, (edits ? back : back - U) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipGetLastError());
-  remember_pass(e, T, p.nact, p.call, p.Xd);
-  CHK(check_kernel_errors(e));
   memcpy(hyp, e->h_dec, (size_t)T * sizeof(int32_t));
   memcpy(hyp_len, e->h_dec + T, (size_t)U * sizeof(int32_t));
   if (edits) memcpy(edits, e->h_dec + T + U, (size_t)U * sizeof(int32_t));
@@ -2417,8 +2435,8 @@ int tfk_ctc_greedy(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const 
 int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
                        int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
                        int32_t* hyp, int32_t* hyp_len, int32_t* edits, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_greedy_impl(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp, hyp_len, edits, flags, &r);
 }
 // Prefix beam search (tf.nn.ctc_beam_search_decoder, merge_repeated=False; the algorithm: tfkaldi_hip.h) + the label errors
@@ -2427,56 +2445,32 @@ int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T
 static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
                          int32_t beam_width, int32_t top_paths, const int32_t* ref_labels, const int32_t* ref_len,
                          int32_t* hyp, int32_t* hyp_len, float* score, int32_t* edits, int flags, const RawSpec* raw) {
-  if (!e) return fail(-1, "engine is NULL");
-  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
-    return fail(-1, "flags %d: tfk_ctc_beam takes 0, tfk_ctc_beam_raw 0 or TFK_RAW_DEVICE", flags);
-  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
-  if (!X) return fail(-1, "X is NULL");
+  CHK(decode_args(e, "tfk_ctc_beam", X, T, flags, raw));
   if (!hyp || !hyp_len || !score) return fail(-1, "hyp / hyp_len / score is NULL");
   if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
   if (const char* why = ctc_beam_limits(e->O, T, U, beam_width, top_paths))
     return fail(-1, "CTC beam search (beam_width %d, top_paths %d, output_dim %d, T %d): %s", beam_width, top_paths, e->O, T,
                 why);
-  const CtcSpec c = {utt_len, U, ref_labels, ref_len};
   const size_t P = (size_t)top_paths;
   const size_t back = P * (size_t)T + 2 * P * (size_t)U + (size_t)U;  // [hypotheses | lengths | scores | distances]
+  const size_t trie_words = ctc_beam_scratch_words(T, U, beam_width);
   int max_ref = 0;
-  Pass p;
-  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
-    CHK(ctc_stage(e, c, T, edits != nullptr, &max_ref));
-    CHK(grow(e, &e->ctc_trie, &e->ctc_cap_trie, ctc_beam_scratch_words(T, U, beam_width)));
-    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, back);
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, ref_labels, ref_len}, edits != nullptr, back, 0,
+                  edits ? back : back - U, &max_ref,
+                  [&] { return grow(e, &e->ctc_trie, &e->ctc_cap_trie, trie_words); }, [&] {
+    int32_t* d_hyp = e->ctc_dec;
+    int32_t* d_len = d_hyp + P * T;
+    {
+      // (8 bytes per trie word: the memset, the call's largest traffic)
+      ProfScope ps(e, KF_CTC_BEAM, 0, 4.0 * T * e->O + 4.0 * P * T + 8.0 * trie_words);
+      ctc_beam_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, e->ctc_trie, d_hyp, d_len,
+                      reinterpret_cast<float*>(d_len + P * U));
+    }
+    if (edits) {
+      ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
+      label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_len + 2 * P * U);
+    }
   }));
-  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
-  int32_t* d_hyp = e->ctc_dec;
-  int32_t* d_len = d_hyp + P * T;
-  float* d_score = reinterpret_cast<float*>(d_len + P * U);
-  int32_t* d_dist = d_len + 2 * P * U;
-  {
-    const double trie_bytes = 8.0 * ctc_beam_scratch_words(T, U, beam_width);  // the memset: the call's largest traffic
-    ProfScope ps(e, KF_CTC_BEAM, 0, 4.0 * T * e->O + 4.0 * P * T + trie_bytes);
-    ctc_beam_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, e->ctc_trie, d_hyp, d_len,
-                    d_score);
-  }
-  if (edits) {
-    ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
-    label_edit_distance(e->stream, d_hyp, e->ctc_seg, d_len, e->ctc_lab, e->ctc_lab_off, U, max_ref, d_dist);
-  }
-  HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, p.slot_before));
-  if (back > e->h_dec_cap) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
-    e->h_dec = nullptr;
-    e->h_dec_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
-    e->h_dec_cap = back + back / 2;
-  }
-  HIPCHK(hipMemcpyAsync(e->h_dec, d_hyp, (edits ? back : back - U) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipGetLastError());
-  remember_pass(e, T, p.nact, p.call, p.Xd);
-  CHK(check_kernel_errors(e));
   memcpy(hyp, e->h_dec, P * T * sizeof(int32_t));
   memcpy(hyp_len, e->h_dec + P * T, P * U * sizeof(int32_t));
   memcpy(score, e->h_dec + P * T + P * U, P * U * sizeof(float));
@@ -2494,8 +2488,8 @@ int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
                      int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths,
                      const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score,
                      int32_t* edits, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_beam_impl(e, raw, ldraw, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
                        flags, &r);
 }
@@ -2521,11 +2515,7 @@ int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O
 static int ctc_align_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
                           const int32_t* labels, const int32_t* label_len, int32_t* ali, float* score, int flags,
                           const RawSpec* raw) {
-  if (!e) return fail(-1, "engine is NULL");
-  if (flags & ~(raw ? TFK_RAW_DEVICE : 0))
-    return fail(-1, "flags %d: tfk_ctc_align takes 0, tfk_ctc_align_raw 0 or TFK_RAW_DEVICE", flags);
-  if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
-  if (!X) return fail(-1, "X is NULL");
+  CHK(decode_args(e, "tfk_ctc_align", X, T, flags, raw));
   if (!ali || !score) return fail(-1, "ali / score is NULL");
   if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC align: utt_len / label_len is NULL or no utterances");
   {  // what ctc_stage would refuse as well, with the utterance named
@@ -2541,39 +2531,16 @@ static int ctc_align_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
       first += n;
     }
   }
-  const CtcSpec c = {utt_len, U, labels, label_len};
   const size_t back = (size_t)T + (size_t)U;  // [ali | score]
   int max_labels = 0;
-  Pass p;
-  CHK(stage_pass(e, X, ldx, nullptr, T, flags, raw, &p, nullptr, nullptr, [&]() -> int {
-    CHK(ctc_stage(e, c, T, true, &max_labels));
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, labels, label_len}, true, back, 0, back, &max_labels, [&]() -> int {
     if (const char* why = ctc_align_limits(e->O, T, U, max_labels)) return fail(-1, "CTC align (T %d, U %d): %s", T, U, why);
-    CHK(grow(e, &e->ctc_bp, &e->ctc_cap_bp, ctc_align_scratch_bytes(T, max_labels)));
-    return grow(e, &e->ctc_dec, &e->ctc_cap_dec, back);
-  }));
-  CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
-  int32_t* d_ali = e->ctc_dec;
-  float* d_score = reinterpret_cast<float*>(d_ali + T);
-  {
+    return grow(e, &e->ctc_bp, &e->ctc_cap_bp, ctc_align_scratch_bytes(T, max_labels));
+  }, [&] {
     ProfScope ps(e, KF_CTC_ALIGN, 0, 4.0 * T * e->O + 2.0 * (double)ctc_align_scratch_bytes(T, max_labels) + 4.0 * T);
     ctc_viterbi_align(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, e->ctc_lab, e->ctc_lab_off, max_labels,
-                      e->ctc_bp, d_ali, d_score);
-  }
-  HIPCHK(hipGetLastError());
-  CHK(finish_slot(e, flags, p.slot_before));
-  if (back > e->h_dec_cap) {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_dec) HIPCHK(hipHostFree(e->h_dec));
-    e->h_dec = nullptr;
-    e->h_dec_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&e->h_dec, (back + back / 2) * sizeof(int32_t), hipHostMallocDefault));
-    e->h_dec_cap = back + back / 2;
-  }
-  HIPCHK(hipMemcpyAsync(e->h_dec, d_ali, back * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  HIPCHK(hipGetLastError());
-  remember_pass(e, T, p.nact, p.call, p.Xd);
-  CHK(check_kernel_errors(e));
+                      e->ctc_bp, e->ctc_dec, reinterpret_cast<float*>(e->ctc_dec + T));
+  }));
   memcpy(ali, e->h_dec, (size_t)T * sizeof(int32_t));
   memcpy(score, e->h_dec + T, (size_t)U * sizeof(float));
   return 0;
@@ -2586,8 +2553,8 @@ int tfk_ctc_align(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const i
 int tfk_ctc_align_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
                       int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
                       int32_t* ali, float* score, int flags) {
-  const RawSpec r = {utt_len, U, context_width, cmvn};
-  if (!utt_len) return fail(-1, "utt_len is NULL");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_align_impl(e, raw, ldraw, T, utt_len, U, labels, label_len, ali, score, flags, &r);
 }
 int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,

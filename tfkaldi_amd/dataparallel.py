@@ -166,17 +166,10 @@ def _label_errors(engine, mb, beam_width=None):
     (beam_width None) or under prefix beam search of that width (its best path)"""
     if not isinstance(mb, CtcMicroBatch):
         raise TypeError("label errors need CTC micro-batches (label sequences), not %s" % type(mb).__name__)
-    if beam_width is None:
-        if mb.context_width is not None:
-            _, edits = engine.ctc_greedy_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, labels=mb.labels,
-                                             label_lens=mb.label_lens)
-        else:
-            _, edits = engine.ctc_greedy(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens)
-    elif mb.context_width is not None:
-        _, _, edits = engine.ctc_beam_raw(mb.X, mb.utt_lens, mb.context_width, cmvn=mb.cmvn, beam_width=beam_width,
-                                          labels=mb.labels, label_lens=mb.label_lens)
-    else:
-        _, _, edits = engine.ctc_beam(mb.X, mb.utt_lens, beam_width=beam_width, labels=mb.labels, label_lens=mb.label_lens)
+    entry, kw = ("ctc_greedy", {}) if beam_width is None else ("ctc_beam", {"beam_width": beam_width})
+    if mb.context_width is not None:  # unspliced frames: CMVN + splice on the device
+        entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
+    edits = getattr(engine, entry)(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens, **kw)[-1]
     import numpy as np
     return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
 

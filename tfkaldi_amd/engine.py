@@ -3,6 +3,7 @@
 This is plumbing only -- every FLOP of the hot path runs in libtfkaldi_hip.so.  The classes of
 tfkaldi_amd.neuralNetworks (Trainer / Decoder / DNN) are built on it.
 """
+from contextlib import contextmanager
 from ctypes import byref, c_double, c_float, c_int, c_size_t, c_uint64, c_void_p
 
 import numpy as np
@@ -15,6 +16,10 @@ from ._lib import (ADAM_STEPS, BIASES, BN_BETA, BN_MOVING_MEAN, BN_MOVING_VAR, G
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _ptr(a):
+    return c_void_p(None) if a is None else a.ctypes.data_as(c_void_p)
 
 
 class Engine(object):
@@ -208,10 +213,6 @@ class Engine(object):
         return c_void_p(raw.data_ptr()), int(raw.stride(0)), int(raw.shape[0]), lens
 
     @staticmethod
-    def _on_device(raw):
-        return hasattr(raw, "is_cuda") and raw.is_cuda
-
-    @staticmethod
     def _raw_batch(raw, lens):
         raw = _f32(raw)
         lens = np.ascontiguousarray(lens, dtype=np.int32)
@@ -229,29 +230,32 @@ class Engine(object):
             raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (lens.size, 2, raw.shape[1])))
         return cmvn, cmvn.ctypes.data_as(c_void_p)
 
+    @contextmanager
+    def _raw_args(self, raw, lens, cmvn, flags=0):
+        """The unspliced frames of one *_raw call, for the length of the call: `raw` host [T, D] frames or a float32 CUDA
+        tensor (TFK_RAW_DEVICE: adopted in place), `lens` frames per utterance, `cmvn` None or the [U, 2, D] table.  Yields
+        (pointer, leading dimension, rows, lens, cmvn pointer, flags) and, however the block ends, marks the end of the
+        tensor's use (_raw_release)."""
+        try:
+            if hasattr(raw, "is_cuda") and raw.is_cuda:
+                ptr, ld, rows, lens = self._raw_device(raw, lens)
+                flags |= _lib.RAW_DEVICE
+            else:
+                raw, lens = self._raw_batch(raw, lens)
+                ptr, ld, rows = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0]
+            cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, lens)
+            yield ptr, ld, rows, lens, cmvn_ptr, flags
+        finally:
+            self._raw_release()
+
     def accumulate_raw(self, raw, y, lens, context_width, last=False, cmvn=None):
         """`raw`: host [T, D] frames, or a float32 CUDA tensor (TFK_RAW_DEVICE)"""
         y = np.ascontiguousarray(y, dtype=np.int32)
-        flags = _lib.LAST_MICROBATCH if last else 0
-        if self._on_device(raw):
-            ptr, ld, rows, lens = self._raw_device(raw, lens)
-            flags |= _lib.RAW_DEVICE
-            cols = raw.shape[1]
-        else:
-            raw, lens = self._raw_batch(raw, lens)
-            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
-        if cmvn is not None:
-            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
-            if cmvn.shape != (lens.size, 2, cols):
-                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (lens.size, 2, cols)))
-        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
-        if y.shape != (rows,):
-            raise ValueError("targets %s do not match %d frames" % (y.shape, rows))
-        try:
+        with self._raw_args(raw, lens, cmvn, _lib.LAST_MICROBATCH if last else 0) as (ptr, ld, rows, lens, cmvn_ptr, flags):
+            if y.shape != (rows,):
+                raise ValueError("targets %s do not match %d frames" % (y.shape, rows))
             check(self.lib.tfk_accumulate_raw(self._h, ptr, ld, y.ctypes.data_as(c_void_p), rows,
                                               lens.ctypes.data_as(c_void_p), lens.size, int(context_width), cmvn_ptr, flags))
-        finally:
-            self._raw_release()
 
     # ---- several micro-batches of one optimiser step in one call (stacked pass: include/tfkaldi_hip.h) ----
     def accumulate_stacked(self, X, y, seg_rows, last=False):
@@ -326,118 +330,92 @@ class Engine(object):
     def posteriors_raw(self, raw, lens, context_width, log_div_prior=False, raw_logits=False, cmvn=None):
         """`raw`: host [T, D] frames, or a float32 CUDA tensor (TFK_RAW_DEVICE: features that never left HBM)"""
         flags = (_lib.LOG_DIV_PRIOR if log_div_prior else 0) | (_lib.RAW_LOGITS if raw_logits else 0)
-        if self._on_device(raw):
-            ptr, ld, rows, lens = self._raw_device(raw, lens)
-            flags |= _lib.RAW_DEVICE
-            shape = (rows, raw.shape[1])
-        else:
-            raw, lens = self._raw_batch(raw, lens)
-            ptr, ld, rows, shape = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape
-        out = self._out_buffer(rows)
-        if cmvn is not None:
-            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
-            if cmvn.shape != (lens.size, 2, shape[1]):
-                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (lens.size, 2, shape[1])))
-        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
-        try:
+        with self._raw_args(raw, lens, cmvn, flags) as (ptr, ld, rows, lens, cmvn_ptr, flags):
+            out = self._out_buffer(rows)
             check(self.lib.tfk_posteriors_raw(self._h, ptr, ld, rows, lens.ctypes.data_as(c_void_p), lens.size,
                                               int(context_width), cmvn_ptr, out.ctypes.data_as(c_void_p), self.O, flags))
-        finally:
-            self._raw_release()
         return out
 
-    # ---- best-path CTC decoding: tf.nn.ctc_greedy_decoder(merge_repeated=True) + tf.edit_distance(normalize=False) ----
-    def _greedy_refs(self, utt_lens, labels, label_lens):
+    # ---- the forward-only CTC entries (greedy, beam, align; plain and raw): one call shape ----
+    @staticmethod
+    def _refs(utt_lens, labels, label_lens, optional, what):
+        """utterance lengths and label sequences (labels back to back, label_lens per utterance) as int32 vectors;
+        optional: labels and label_lens may both be None (no references)"""
         utt_lens = np.ascontiguousarray(utt_lens, dtype=np.int32).reshape(-1)
-        if (labels is None) != (label_lens is None):
+        if optional and (labels is None) != (label_lens is None):
             raise ValueError("labels and label_lens go together")
-        if labels is None:
-            return utt_lens, None, None, c_void_p(None), c_void_p(None), None
+        if optional and labels is None:
+            return utt_lens, None, None
         labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
         label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
         if label_lens.size != utt_lens.size or int(label_lens.sum()) != labels.size:
-            raise ValueError("references: %d label counts (sum %d) for %d utterances and %d labels"
-                             % (label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
-        edits = np.empty(utt_lens.size, dtype=np.int32)
-        return (utt_lens, labels, label_lens, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
-                edits)
+            raise ValueError("%s: %d label counts (sum %d) for %d utterances and %d labels"
+                             % (what, label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
+        return utt_lens, labels, label_lens
 
-    @staticmethod
-    def _greedy_result(hyp, hyp_len, utt_lens, edits):
-        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
-        return [hyp[s:s + n].copy() for s, n in zip(starts, hyp_len)], edits
+    def _decode(self, fn, frames, utt_lens, refs, outputs, result, extra=(), raw=None):
+        """One call of a forward-only CTC entry `fn`: tfk_ctc_X on spliced frames [sum(utt_lens), F], or tfk_ctc_X_raw on
+        unspliced ones with raw = (context_width, cmvn).  refs: (labels, label_lens) after _refs.  outputs(rows, U) makes
+        the arrays the entry fills, in the order of its signature (None: a NULL pointer); with rows == 0 -- only zero-frame
+        utterances, the engine is not called -- it fills them itself.  extra: the entry's own integer arguments.
+        Returns result(utt_lens, *arrays)."""
+        def run(ptr, ld, rows, lens, raw_args, flags):
+            outs = outputs(rows, lens.size)
+            if rows:
+                check(fn(self._h, ptr, ld, rows, _ptr(lens), lens.size, *raw_args, *extra, _ptr(refs[0]), _ptr(refs[1]),
+                         *[_ptr(o) for o in outs], flags))
+            return result(lens, *outs)
+        if raw is None:
+            X = _f32(frames)
+            if int(utt_lens.sum()) != X.shape[0]:
+                raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
+            return run(_ptr(X), X.shape[1], X.shape[0], utt_lens, (), 0)
+        with self._raw_args(frames, utt_lens, raw[1]) as (ptr, ld, rows, lens, cmvn_ptr, flags):
+            return run(ptr, ld, rows, lens, (int(raw[0]), cmvn_ptr), flags)
+
+    # ---- best-path CTC decoding: tf.nn.ctc_greedy_decoder(merge_repeated=True) + tf.edit_distance(normalize=False) ----
+    def _greedy(self, fn, frames, utt_lens, labels, label_lens, raw=None):
+        utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, True, "references")
+
+        def outputs(rows, U):  # (no frames: empty hypotheses, the reference lengths as distances)
+            edits = None if labels is None else (np.empty(U, dtype=np.int32) if rows else label_lens.copy())
+            return np.empty(rows, dtype=np.int32), np.zeros(U, dtype=np.int32), edits
+
+        def result(lens, hyp, hyp_len, edits):
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            return [hyp[s:s + n].copy() for s, n in zip(starts, hyp_len)], edits
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, raw=raw)
 
     def ctc_greedy(self, X, utt_lens, labels=None, label_lens=None):
         """Best-path decoding of the utterances X [sum(utt_lens), F] (tfk_ctc_greedy): per frame the largest logit, repeats
         merged, blanks (the last class) removed.  With references (labels back to back, label_lens per utterance) also the
         Levenshtein distance of every hypothesis to its reference.  Returns (list of int32 label arrays, int32 [U] edit
         distances or None)."""
-        X = _f32(X)
-        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
-        if int(utt_lens.sum()) != X.shape[0]:
-            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
-        if X.shape[0] == 0:  # only zero-frame utterances: empty hypotheses, the reference lengths as distances
-            return [np.zeros(0, dtype=np.int32) for _ in utt_lens], None if edits is None else label_lens.copy()
-        hyp = np.empty(X.shape[0], dtype=np.int32)
-        hyp_len = np.empty(utt_lens.size, dtype=np.int32)
-        check(self.lib.tfk_ctc_greedy(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
-                                      utt_lens.ctypes.data_as(c_void_p), utt_lens.size, lab_ptr, len_ptr,
-                                      hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
-                                      c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), 0))
-        return self._greedy_result(hyp, hyp_len, utt_lens, edits)
+        return self._greedy(self.lib.tfk_ctc_greedy, X, utt_lens, labels, label_lens)
 
     def ctc_greedy_raw(self, raw, utt_lens, context_width, cmvn=None, labels=None, label_lens=None):
         """ctc_greedy on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
-        flags = 0
-        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
-        if self._on_device(raw):
-            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
-            flags |= _lib.RAW_DEVICE
-            cols = raw.shape[1]
-        else:
-            raw, utt_lens = self._raw_batch(raw, utt_lens)
-            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
-        if rows == 0:
-            self._raw_release()
-            return [np.zeros(0, dtype=np.int32) for _ in utt_lens], None if edits is None else label_lens.copy()
-        if cmvn is not None:
-            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
-            if cmvn.shape != (utt_lens.size, 2, cols):
-                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
-        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
-        hyp = np.empty(rows, dtype=np.int32)
-        hyp_len = np.empty(utt_lens.size, dtype=np.int32)
-        try:
-            check(self.lib.tfk_ctc_greedy_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
-                                              int(context_width), cmvn_ptr, lab_ptr, len_ptr, hyp.ctypes.data_as(c_void_p),
-                                              hyp_len.ctypes.data_as(c_void_p),
-                                              c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), flags))
-        finally:
-            self._raw_release()
-        return self._greedy_result(hyp, hyp_len, utt_lens, edits)
+        return self._greedy(self.lib.tfk_ctc_greedy_raw, raw, utt_lens, labels, label_lens, raw=(context_width, cmvn))
 
     # ---- CTC prefix beam search: tf.nn.ctc_beam_search_decoder(merge_repeated=False), N best with log-probabilities ----
-    @staticmethod
-    def _beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits):
-        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
-        hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
-        return hyps, np.ascontiguousarray(score.T), edits
-
-    @staticmethod
-    def _beam_empty(utt_lens, top_paths, edits, label_lens):
-        """only zero-frame utterances: the empty hypothesis with score 0, the other paths empty with score -inf"""
-        scores = np.full((utt_lens.size, top_paths), -np.inf, dtype=np.float32)
-        scores[:, 0] = 0.0
-        hyps = [[np.zeros(0, dtype=np.int32) for _ in range(top_paths)] for _ in utt_lens]
-        return hyps, scores, None if edits is None else label_lens.copy()
-
-    @staticmethod
-    def _beam_args(beam_width, top_paths):
+    def _beam(self, fn, frames, utt_lens, beam_width, top_paths, labels, label_lens, raw=None):
         beam_width, top_paths = int(beam_width), int(top_paths)
         if not 1 <= top_paths <= beam_width:
             raise ValueError("top_paths %d outside [1, beam_width = %d]" % (top_paths, beam_width))
-        return beam_width, top_paths
+        utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, True, "references")
+
+        def outputs(rows, U):  # (no frames: the empty hypothesis with score 0, the other paths empty with score -inf)
+            score = np.full((top_paths, U), -np.inf, dtype=np.float32)
+            score[0] = 0.0
+            edits = None if labels is None else (np.empty(U, dtype=np.int32) if rows else label_lens.copy())
+            return np.empty((top_paths, rows), dtype=np.int32), np.zeros((top_paths, U), dtype=np.int32), score, edits
+
+        def result(lens, hyp, hyp_len, score, edits):
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
+            return hyps, np.ascontiguousarray(score.T), edits
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, (beam_width, top_paths), raw)
 
     def ctc_beam(self, X, utt_lens, beam_width=100, top_paths=1, labels=None, label_lens=None):
         """Prefix beam search over the utterances X [sum(utt_lens), F] (tfk_ctc_beam; the algorithm is stated in
@@ -445,79 +423,27 @@ class Engine(object):
         beam of `beam_width`, best first, with their natural-log probabilities.  Returns (hyps, scores, edits): hyps[u][n]
         int32 label arrays, scores float32 [U, top_paths] (-inf where fewer prefixes survived), edits int32 [U] = Levenshtein
         distance of the BEST path to the reference (labels back to back, label_lens per utterance) or None."""
-        X = _f32(X)
-        beam_width, top_paths = self._beam_args(beam_width, top_paths)
-        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
-        if int(utt_lens.sum()) != X.shape[0]:
-            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
-        if X.shape[0] == 0:
-            return self._beam_empty(utt_lens, top_paths, edits, label_lens)
-        hyp = np.empty((top_paths, X.shape[0]), dtype=np.int32)
-        hyp_len = np.empty((top_paths, utt_lens.size), dtype=np.int32)
-        score = np.empty((top_paths, utt_lens.size), dtype=np.float32)
-        check(self.lib.tfk_ctc_beam(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
-                                    utt_lens.ctypes.data_as(c_void_p), utt_lens.size, beam_width, top_paths, lab_ptr, len_ptr,
-                                    hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
-                                    score.ctypes.data_as(c_void_p),
-                                    c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), 0))
-        return self._beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits)
+        return self._beam(self.lib.tfk_ctc_beam, X, utt_lens, beam_width, top_paths, labels, label_lens)
 
     def ctc_beam_raw(self, raw, utt_lens, context_width, cmvn=None, beam_width=100, top_paths=1, labels=None,
                      label_lens=None):
         """ctc_beam on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
-        flags = 0
-        beam_width, top_paths = self._beam_args(beam_width, top_paths)
-        utt_lens, labels, label_lens, lab_ptr, len_ptr, edits = self._greedy_refs(utt_lens, labels, label_lens)
-        if self._on_device(raw):
-            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
-            flags |= _lib.RAW_DEVICE
-            cols = raw.shape[1]
-        else:
-            raw, utt_lens = self._raw_batch(raw, utt_lens)
-            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
-        if rows == 0:
-            self._raw_release()
-            return self._beam_empty(utt_lens, top_paths, edits, label_lens)
-        if cmvn is not None:
-            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
-            if cmvn.shape != (utt_lens.size, 2, cols):
-                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
-        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
-        hyp = np.empty((top_paths, rows), dtype=np.int32)
-        hyp_len = np.empty((top_paths, utt_lens.size), dtype=np.int32)
-        score = np.empty((top_paths, utt_lens.size), dtype=np.float32)
-        try:
-            check(self.lib.tfk_ctc_beam_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
-                                            int(context_width), cmvn_ptr, beam_width, top_paths, lab_ptr, len_ptr,
-                                            hyp.ctypes.data_as(c_void_p), hyp_len.ctypes.data_as(c_void_p),
-                                            score.ctypes.data_as(c_void_p),
-                                            c_void_p(None) if edits is None else edits.ctypes.data_as(c_void_p), flags))
-        finally:
-            self._raw_release()
-        return self._beam_result(hyp, hyp_len, score, utt_lens, top_paths, edits)
+        return self._beam(self.lib.tfk_ctc_beam_raw, raw, utt_lens, beam_width, top_paths, labels, label_lens,
+                          raw=(context_width, cmvn))
 
     # ---- CTC forced alignment: the Viterbi path of the known label sequence, per frame the label POSITION it emits ----
-    @staticmethod
-    def _align_refs(utt_lens, labels, label_lens):
-        utt_lens = np.ascontiguousarray(utt_lens, dtype=np.int32).reshape(-1)
-        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
-        label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
-        if label_lens.size != utt_lens.size or int(label_lens.sum()) != labels.size:
-            raise ValueError("alignment: %d label counts (sum %d) for %d utterances and %d labels"
-                             % (label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
-        return utt_lens, labels, label_lens
+    def _align(self, fn, frames, utt_lens, labels, label_lens, raw=None):
+        utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, False, "alignment")
 
-    @staticmethod
-    def _align_result(ali, score, utt_lens):
-        starts = np.concatenate([[0], np.cumsum(utt_lens)[:-1]]).astype(np.int64)
-        return [ali[s:s + n].copy() if sc > -np.inf else None for s, n, sc in zip(starts, utt_lens, score)], score
+        def outputs(rows, U):  # (no frames: the empty alignment with score 0 where there is nothing to emit, else no path)
+            score = np.empty(U, dtype=np.float32) if rows else np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32)
+            return np.empty(rows, dtype=np.int32), score
 
-    @staticmethod
-    def _align_empty(utt_lens, label_lens):
-        """only zero-frame utterances: the empty alignment with score 0 where there is nothing to emit, no path otherwise"""
-        score = np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32)
-        return Engine._align_result(np.zeros(0, dtype=np.int32), score, utt_lens)
+        def result(lens, ali, score):
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            return [ali[s:s + n].copy() if sc > -np.inf else None for s, n, sc in zip(starts, lens, score)], score
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, raw=raw)
 
     def ctc_align(self, X, utt_lens, labels, label_lens):
         """Forced alignment of the utterances X [sum(utt_lens), F] to their label sequences (tfk_ctc_align; the algorithm and
@@ -525,50 +451,12 @@ class Engine(object):
         back, label_lens per utterance, as accumulate_ctc.  Returns (alis, scores): alis[u] int32 [utt_lens[u]], per frame
         the POSITION in the utterance's label sequence of the label the frame emits, -1 for a blank frame -- None for an
         utterance too short for its labels; scores float32 [U], the natural-log probability of the path (-inf for None)."""
-        X = _f32(X)
-        utt_lens, labels, label_lens = self._align_refs(utt_lens, labels, label_lens)
-        if int(utt_lens.sum()) != X.shape[0]:
-            raise ValueError("frames %s / utterance lengths (sum %d) do not match" % (X.shape, int(utt_lens.sum())))
-        if X.shape[0] == 0:
-            return self._align_empty(utt_lens, label_lens)
-        ali = np.empty(X.shape[0], dtype=np.int32)
-        score = np.empty(utt_lens.size, dtype=np.float32)
-        check(self.lib.tfk_ctc_align(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
-                                     utt_lens.ctypes.data_as(c_void_p), utt_lens.size, labels.ctypes.data_as(c_void_p),
-                                     label_lens.ctypes.data_as(c_void_p), ali.ctypes.data_as(c_void_p),
-                                     score.ctypes.data_as(c_void_p), 0))
-        return self._align_result(ali, score, utt_lens)
+        return self._align(self.lib.tfk_ctc_align, X, utt_lens, labels, label_lens)
 
     def ctc_align_raw(self, raw, utt_lens, context_width, labels, label_lens, cmvn=None):
         """ctc_align on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
-        flags = 0
-        utt_lens, labels, label_lens = self._align_refs(utt_lens, labels, label_lens)
-        if self._on_device(raw):
-            ptr, ld, rows, utt_lens = self._raw_device(raw, utt_lens)
-            flags |= _lib.RAW_DEVICE
-            cols = raw.shape[1]
-        else:
-            raw, utt_lens = self._raw_batch(raw, utt_lens)
-            ptr, ld, rows, cols = raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], raw.shape[1]
-        if rows == 0:
-            self._raw_release()
-            return self._align_empty(utt_lens, label_lens)
-        if cmvn is not None:
-            cmvn = np.ascontiguousarray(cmvn, dtype=np.float32)
-            if cmvn.shape != (utt_lens.size, 2, cols):
-                raise ValueError("cmvn table %s, expected %s" % (cmvn.shape, (utt_lens.size, 2, cols)))
-        cmvn_ptr = cmvn.ctypes.data_as(c_void_p) if cmvn is not None else c_void_p(None)
-        ali = np.empty(rows, dtype=np.int32)
-        score = np.empty(utt_lens.size, dtype=np.float32)
-        try:
-            check(self.lib.tfk_ctc_align_raw(self._h, ptr, ld, rows, utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
-                                             int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
-                                             label_lens.ctypes.data_as(c_void_p), ali.ctypes.data_as(c_void_p),
-                                             score.ctypes.data_as(c_void_p), flags))
-        finally:
-            self._raw_release()
-        return self._align_result(ali, score, utt_lens)
+        return self._align(self.lib.tfk_ctc_align_raw, raw, utt_lens, labels, label_lens, raw=(context_width, cmvn))
 
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):

@@ -75,21 +75,36 @@ class Decoder(object):
         """log(posterior / prior), fused in the softmax kernel; needs set_prior (reference nnet.py:280-286)"""
         return self._run(inputs, log_div_prior=True)
 
+    def _batch(self, utterances):
+        """The utterances of ONE forward pass: (lens, raw, frames, context_width, cmvn).  All `Unspliced`
+        -> raw: the unspliced frames back to back with their context width and CMVN table, for the device-side splice with
+        utterance boundaries; otherwise the spliced matrices stacked (frames are independent once spliced)."""
+        for u in utterances:
+            self._check(u)
+        lens = [u.shape[0] for u in utterances]
+        if all(isinstance(u, Unspliced) for u in utterances):
+            return (lens, True, np.concatenate([np.asarray(u) for u in utterances]), utterances[0].context_width,
+                    cmvn_table(utterances))
+        stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
+                                for u in utterances])
+        return lens, False, stack, None, None
+
+    def _ctc(self, entry, utterances, *args, **kw):
+        """engine.<entry> (spliced) or engine.<entry>_raw (all `Unspliced`) on the batch of `utterances`"""
+        lens, raw, frames, context_width, cmvn = self._batch(utterances)
+        if raw:
+            return getattr(self.engine, entry + "_raw")(frames, lens, context_width, *args, cmvn=cmvn, **kw)
+        return getattr(self.engine, entry)(frames, lens, *args, **kw)
+
     def decode_batch(self, utterances, log_div_prior=True):
         """Several utterances in ONE forward pass: returns a list of per-utterance [N_i, O] arrays.
         All `Unspliced` -> device-side splice with utterance boundaries; otherwise the spliced matrices are
         simply stacked (frames are independent once spliced)."""
-        lens = [u.shape[0] for u in utterances]
-        for u in utterances:
-            self._check(u)
-        if all(isinstance(u, Unspliced) for u in utterances):
-            flat = self.engine.posteriors_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
-                                              utterances[0].context_width, log_div_prior=log_div_prior,
-                                              cmvn=cmvn_table(utterances))
+        lens, raw, frames, context_width, cmvn = self._batch(utterances)
+        if raw:
+            flat = self.engine.posteriors_raw(frames, lens, context_width, log_div_prior=log_div_prior, cmvn=cmvn)
         else:
-            stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
-                                    for u in utterances])
-            flat = self.engine.posteriors(stack, log_div_prior=log_div_prior)
+            flat = self.engine.posteriors(frames, log_div_prior=log_div_prior)
         return np.split(flat, np.cumsum(lens)[:-1])
 
     def ctc_best_path(self, utterances):
@@ -99,17 +114,7 @@ class Decoder(object):
         from the trainer's TargetCoder.decode.  All `Unspliced` -> device-side splice, as decode_batch."""
         if len(utterances) == 0:
             return []
-        lens = [u.shape[0] for u in utterances]
-        for u in utterances:
-            self._check(u)
-        if all(isinstance(u, Unspliced) for u in utterances):
-            hyps, _ = self.engine.ctc_greedy_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
-                                                 utterances[0].context_width, cmvn=cmvn_table(utterances))
-        else:
-            stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
-                                    for u in utterances])
-            hyps, _ = self.engine.ctc_greedy(stack, lens)
-        return hyps
+        return self._ctc("ctc_greedy", utterances)[0]
 
     def ctc_beam_search(self, utterances, beam_width=100, top_paths=1):
         """Prefix beam search decoding of a CTC model (tf.nn.ctc_beam_search_decoder with merge_repeated=False, its default
@@ -118,18 +123,7 @@ class Decoder(object):
         probabilities.  All `Unspliced` -> device-side splice, as decode_batch."""
         if len(utterances) == 0:
             return [], np.zeros((0, top_paths), dtype=np.float32)
-        lens = [u.shape[0] for u in utterances]
-        for u in utterances:
-            self._check(u)
-        if all(isinstance(u, Unspliced) for u in utterances):
-            hyps, scores, _ = self.engine.ctc_beam_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
-                                                       utterances[0].context_width, cmvn=cmvn_table(utterances),
-                                                       beam_width=beam_width, top_paths=top_paths)
-        else:
-            stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
-                                    for u in utterances])
-            hyps, scores, _ = self.engine.ctc_beam(stack, lens, beam_width=beam_width, top_paths=top_paths)
-        return hyps, scores
+        return self._ctc("ctc_beam", utterances, beam_width=beam_width, top_paths=top_paths)[:2]
 
     def ctc_align(self, utterances, targets):
         """Forced alignment of a CTC model (tfk_ctc_align; the algorithm is stated in include/tfkaldi_hip.h): every
@@ -142,18 +136,8 @@ class Decoder(object):
             raise ValueError("%d utterances, %d label sequences" % (len(utterances), len(targets)))
         if len(utterances) == 0:
             return [], np.zeros(0, dtype=np.float32)
-        lens = [u.shape[0] for u in utterances]
-        for u in utterances:
-            self._check(u)
         targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
-        labels = np.concatenate(targets) if targets else np.zeros(0, dtype=np.int32)
-        label_lens = [t.size for t in targets]
-        if all(isinstance(u, Unspliced) for u in utterances):
-            return self.engine.ctc_align_raw(np.concatenate([np.asarray(u) for u in utterances]), lens,
-                                             utterances[0].context_width, labels, label_lens, cmvn=cmvn_table(utterances))
-        stack = np.concatenate([u.spliced() if isinstance(u, Unspliced) else np.asarray(u, dtype=np.float32)
-                                for u in utterances])
-        return self.engine.ctc_align(stack, lens, labels, label_lens)
+        return self._ctc("ctc_align", utterances, np.concatenate(targets), [t.size for t in targets])
 
     def set_prior(self, prior):
         self.engine.set_prior(prior)
