@@ -283,7 +283,8 @@ ctc_alpha_beta_kernel(CtcBatch b) {
 
 // one wave per frame; dynamic LDS: the class row, then the frame's state posteriors
 //   gamma_t(s) = exp((alpha~ + beta~ - lp) + (off_alpha(t) + off_beta(t) - log Z))
-// (the offsets cancel to a small number, which is exact enough in fp32)
+// (the exponent is summed in double and rounded once), then divided by its sum over the frame's states where
+// that sum is one up to round-off
 __global__ void __launch_bounds__(64)
 ctc_grad_kernel(CtcBatch b, float* __restrict__ dlogits, Twin tw) {
   extern __shared__ float row[];
@@ -295,11 +296,29 @@ ctc_grad_kernel(CtcBatch b, float* __restrict__ dlogits, Twin tw) {
   const float* pr = b.post + (size_t)t * b.ld;
   for (int c = lane; c < b.ld; c += 64) row[c] = live ? pr[c] : 0.f;
   {
-    const float shift = live ? (float)(b.off[t] + b.offb[t] - b.logz[u]) : 0.f;
+    // (summed in double: between two re-centrings alpha~ and beta~ of a peaky model fall to ~ -200, where an fp32 sum
+    // rounds by 1.5e-5 per state)
+    const double shift = live ? b.off[t] + b.offb[t] - b.logz[u] : 0.0;
     const float* al = b.ab + (size_t)t * b.sext;
     const float* be = b.bb + (size_t)t * b.sext;
     const float* lp = b.lp + (size_t)t * b.sext;
-    for (int s = lane; s < n; s += 64) g[s] = live ? __expf(al[s] + be[s] - lp[s] + shift) : 0.f;
+    float tot = 0.f;
+    for (int s = lane; s < n; s += 64) {
+      g[s] = live ? __expf((float)((double)al[s] + (double)be[s] - (double)lp[s] + shift)) : 0.f;
+      tot += g[s];
+    }
+    // sum_s gamma_t(s) = 1 at every frame.  alpha~ and beta~ each carry the round-off of a chain of up to Tn fp32 steps,
+    // and the part of it that the frame's states share shows as a sum of 1 +- 1e-5 .. 1e-4: divide it out, so that a
+    // row of dLogits sums to zero as far as the softmax row does (fixed order: lane-strided sums, then the butterfly).
+    // The trade: whatever the frame's states share -- off, offb, log Z -- cancels in the quotient, so the division
+    // would also hide a wrong offset or a wrong log Z from every check of the gradient.  It is therefore applied only
+    // where the sum is within 1e-2 of one, >10x the round-off of the longest utterances (1600 frames) and far
+    // below what a wrong offset gives (a re-centring moves the offset by tens; e^+-20).  Outside of that band the
+    // posteriors stay as computed -- a sum that overflowed included, so no inf * 0 can arise -- and the error shows
+    // in dLogits at its full size.
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    const float inv = fabsf(tot - 1.f) < 1e-2f ? 1.f / tot : 1.f;
+    for (int s = lane; s < n; s += 64) g[s] *= inv;
   }
   __syncthreads();
   float blank = 0.f;
