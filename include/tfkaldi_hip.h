@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 11
+#define TFK_ABI_VERSION 12
 
 typedef struct tfk_engine tfk_engine;
 
@@ -138,9 +138,10 @@ enum { /* flags */
   TFK_LAST_MICROBATCH = 2, /* last accumulate before tfk_apply: fire the bucket callback per layer */
   TFK_LOG_DIV_PRIOR = 4,   /* tfk_posteriors: write log(posterior / prior) (nnet.py:280-286) */
   TFK_RAW_LOGITS = 8,      /* tfk_posteriors: write the logits (Classifier.__call__ output, dnn.py:108) */
-  TFK_RAW_DEVICE = 16      /* the *_raw entry points: `raw` is a device pointer -- features that never left HBM, e.g. the output
+  TFK_RAW_DEVICE = 16,     /* the *_raw entry points: `raw` is a device pointer -- features that never left HBM, e.g. the output
                             * of tfk_feat_compute; everything else (y, utt_len, cmvn, out) stays a host pointer.  The producer's
                             * work must be complete, or ordered before the engine's stream (tfk_stream), when the call is made. */
+  TFK_CTC_LM_EOS = 32      /* tfk_ctc_beam_lm*: the final ranking and score add the model's end-of-sequence term */
 };
 
 /* Replaces `update_gradients_op.run(feed_dict)` (trainer.py:160-169, 325-332) for ONE micro-batch,
@@ -265,7 +266,7 @@ int tfk_ctc_greedy(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const 
 int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
                        int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
                        int32_t* hyp, int32_t* hyp_len, int32_t* edits, int flags);
-/* (ABI 10) CTC prefix beam search without a language model (Graves 2012; Hannun et al. 2014) with the conventions of
+/* (ABI 10) CTC prefix beam search by acoustic score alone (Graves 2012; Hannun et al. 2014) with the conventions of
  * tf.nn.ctc_beam_search_decoder(merge_repeated=False), and the label errors of its best path.  Eval-mode forward of the flat
  * utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); the LOGITS are log-softmaxed per row; blank = the
  * LAST class; utterances are independent.  The algorithm (this comment is the contract):
@@ -300,6 +301,51 @@ int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
  * seg[U + 1] = first row of every utterance (seg[U] = T); hyp [top_paths * T], hyp_len / score [top_paths * U] as above. */
 int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                         int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score);
+/* (ABI 12) The character n-gram language model of tfk_ctc_beam_lm: a DENSE table over the label alphabet.  With O =
+ * output_dim (O - 1 labels + the blank index O - 1), order n in [1, 4] and C = O^(n - 1):
+ *   table[C][O] float32, row-major, O^n values, all finite (smoothing and back-off are the caller's business: every lookup
+ *   is one load).  A context id holds a prefix's last n - 1 labels as base-O digits, the most recent label the least
+ *   significant; a position before the utterance's start is the digit O - 1, so the empty prefix has id C - 1 and order 1 the
+ *   single row 0; ctx(p + c) = (ctx(p) * O + c) mod C.  table[ctx][c], c < O - 1: the natural-log probability of label c
+ *   after that context.  Column O - 1: the log-probability that the sequence ENDS after it (read only under TFK_CTC_LM_EOS).
+ * `table` is a HOST pointer to O^order floats; the call copies them to the device (64 MB at O = 64, order 4) and replaces any
+ * model the engine holds; table == NULL drops it.  An order outside [1, 4] or a non-finite entry (tfk_last_error names its
+ * index) is rejected and the engine keeps the model it had.  Parameters, accumulators and statistics are not touched;
+ * tfk_ctc_beam / tfk_ctc_beam_raw ignore the model. */
+int tfk_ctc_lm_set(tfk_engine* e, const float* table, int32_t order);
+/* (ABI 12) CTC prefix beam search with that model (Hannun et al. 2014: prefixes ranked by p_ctc * p_lm^alpha * |prefix|^beta;
+ * here in log space, with a per-label bonus for beta).  Everything of tfk_ctc_beam holds unchanged -- states (pb, pnb), stay /
+ * extend, merging by logaddexp in the fixed order, log-softmax of the logits.  In addition (this comment is the contract):
+ *   every prefix carries a language-model score g and a context id.  The empty prefix has g = 0.  An extension has
+ *   g(p + c) = (g(p) + lm_weight * table[ctx(p)][c]) + label_bonus, evaluated in fp32 in exactly that order: g is a function
+ *   of the label sequence alone, every route to a prefix computes the same bits (a prefix that is re-created included).  A
+ *   prefix that stays keeps its g; an extension that merges into a prefix already in the beam takes that prefix's g.
+ *   A candidate's rank key is logaddexp(pb', pnb') + g; the beam keeps the beam_width largest keys.  Ties as tfk_ctc_beam:
+ *   the shorter prefix, then the lower (slot, label) pair.  The running offset and the per-frame re-centring stay on the
+ *   acoustic part.
+ *   After the last frame: the top_paths best prefixes by key; with flag TFK_CTC_LM_EOS the ranking and the reported score add
+ *   lm_weight * table[ctx(p)][O - 1].
+ * Two scores per path: score[n * U + u] is the combined value (fp32 relative to the double offset, as tfk_ctc_beam's);
+ * am_score[n * U + u] (may be NULL) the acoustic part alone, the log-probability of the prefix's surviving alignments --
+ * what tfk_ctc_beam calls score.  With lm_weight = label_bonus = 0 and no end flag, hyp, hyp_len and score equal
+ * tfk_ctc_beam's bit for bit and am_score == score.  A zero-frame utterance: the empty hypothesis, am_score 0, score 0 or
+ * lm_weight * table[C - 1][O - 1] under the end flag; padding paths as tfk_ctc_beam (both scores -inf).  edits[u]: the
+ * Levenshtein distance of the best path BY COMBINED SCORE.  Limits: those of tfk_ctc_beam; a model must have been set
+ * (tfk_ctc_lm_set), else the call returns non-zero.  flags: 0 or TFK_CTC_LM_EOS. */
+int tfk_ctc_beam_lm(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                    int32_t beam_width, int32_t top_paths, float lm_weight, float label_bonus, const int32_t* ref_labels,
+                    const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score, int32_t* edits,
+                    int flags);
+/* The same on UNSPLICED frames (as tfk_ctc_beam_raw; flags: TFK_RAW_DEVICE and / or TFK_CTC_LM_EOS). */
+int tfk_ctc_beam_lm_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                        int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths, float lm_weight,
+                        float label_bonus, const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp,
+                        int32_t* hyp_len, float* score, float* am_score, int32_t* edits, int flags);
+/* (ABI 12) Tests / tools: that search alone on logits, as tfk_ctc_beam_logits; DEVICE pointers, lm_dev [O^order] included
+ * (not checked for finiteness); am_score may be NULL; flags: 0 or TFK_CTC_LM_EOS. */
+int tfk_ctc_beam_lm_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                           int32_t beam_width, int32_t top_paths, const float* lm_dev, int32_t order, float lm_weight,
+                           float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score);
 /* (ABI 11) CTC forced alignment: the most probable alignment of every utterance's KNOWN label sequence -- which frames emit
  * which label, and with what probability (time stamps and segments, corpus cleaning by alignment score, frame-level targets).
  * Eval-mode forward of the flat utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); labels / label_len as

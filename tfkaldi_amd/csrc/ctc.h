@@ -48,7 +48,7 @@ void ctc_loss_reduce(hipStream_t s, const float* utt_loss, const int32_t* lab_of
 // n-th label (repeats merged, then the blank O - 1 removed), -1 on its remaining rows; hyp_len[u] = its label count.
 void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int32_t* cls,
                    int32_t* hyp, int32_t* hyp_len);
-// Prefix beam search without a language model (Graves 2012; Hannun et al. 2014) with the conventions of
+// Prefix beam search (Graves 2012; Hannun et al. 2014) with the conventions of
 // tf.nn.ctc_beam_search_decoder(merge_repeated=False), on the logits [T, ld] of the utterances seg[U + 1]; blank = the
 // LAST class; rows are log-softmaxed inside the kernel.  Per utterance a beam of at most W prefixes, each with (pb, pnb) =
 // log-probability of its alignments so far that end in a blank / a non-blank, start {(): (0, -inf)}.  Per frame with
@@ -62,13 +62,27 @@ void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, con
 // hyp_len[n * U + u], score[n * U + u] = its natural-log probability; n < top_paths, best first; paths beyond the
 // surviving prefixes have length 0 and score -inf (a zero-frame utterance: the empty prefix with score 0, then those).
 // trie: ctc_beam_scratch_words(T, U, W) 64-bit words of scratch.  ctc_beam_limits: NULL, or the limit a shape breaks.
+// lm == NULL: the search above, by acoustic score alone.  With lm -- a dense character n-gram table on the DEVICE, [C, O]
+// row-major, C = ctc_lm_contexts(O, order) = O^(order - 1) -- every prefix also carries g and a context id, candidates are
+// ranked by logaddexp(pb', pnb') + g, and the final paths by that (+ weight * lm[ctx][O - 1] with eos); `score` is the
+// combined value and am_score (NULL: not wanted) the acoustic part.  The contract is the comment at tfk_ctc_beam_lm in
+// tfkaldi_hip.h.  weight = bonus = 0 without eos gives the bits of lm == NULL.
+struct CtcLm {
+  const float* table;
+  int order;  // in [1, kCtcLmMaxOrder]
+  float weight, bonus;
+  bool eos;
+};
+constexpr int kCtcLmMaxOrder = 4;
+int ctc_lm_contexts(int O, int order);
 constexpr int kCtcBeamMaxWidth = 128;
 constexpr int kCtcBeamMaxClasses = 64;
 constexpr int kCtcBeamMaxFrames = (1 << 19) - 2;
 size_t ctc_beam_scratch_words(int T, int U, int W);
 const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths);
 void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
-                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score);
+                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score,
+                     const CtcLm* lm = nullptr, float* am_score = nullptr);
 // Forced alignment: the most probable path through the CTC lattice of every utterance's KNOWN label sequence (the contract
 // is the comment at tfk_ctc_align in tfkaldi_hip.h).  States as the loss: n = 2S + 1, blank, l_0, blank, ..., blank;
 // transitions as ctc_alpha_beta (stay, +1, +2 into a label that differs from the label two states back); start in state

@@ -520,6 +520,18 @@ struct BeamSide {
   int node[kCtcBeamMaxWidth], parent[kCtcBeamMaxWidth], last[kCtcBeamMaxWidth], len[kCtcBeamMaxWidth],
       src[kCtcBeamMaxWidth];
 };
+// with a language model every prefix also carries g = its weighted model score + label bonuses (a function of its label
+// sequence alone) and ctx = its last order - 1 labels as base-O digits, the row of the table its extensions read
+struct BeamSideLm : BeamSide {
+  float g[kCtcBeamMaxWidth];
+  int ctx[kCtcBeamMaxWidth];
+};
+template <bool LM>
+struct BeamSideOf { typedef BeamSide type; };
+template <>
+struct BeamSideOf<true> { typedef BeamSideLm type; };
+// longest run of candidates one thread owns: ceil(kBeamKeys / kBeamThreads) | 1
+constexpr int kBeamRun = ((kBeamKeys + kBeamThreads - 1) / kBeamThreads) | 1;
 
 __device__ __forceinline__ float lae(float a, float b) {
   const float m = fmaxf(a, b), n = fminf(a, b);
@@ -550,6 +562,32 @@ __device__ __forceinline__ void beam_candidate(const BeamSide& b, const float* l
 // secondary key of candidate k (larger = preferred): shorter prefix, then lower candidate index
 __device__ __forceinline__ uint32_t beam_tiebreak(int len, int k) {
   return ((uint32_t)(kCtcBeamMaxFrames + 1 - len) << 13) | (uint32_t)(kBeamKeys - 1 - k);
+}
+
+// g(p + c) = (g(p) + lm_weight * lm[ctx(p)][c]) + label_bonus: three roundings in this order wherever it is evaluated, so
+// every route to a prefix gives the same bits
+__device__ __forceinline__ float beam_lm_extend(float g, float w, float lmv, float bonus) {
+#pragma clang fp contract(off)
+  const float a = g + w * lmv;
+  return a + bonus;
+}
+// the ranking value of a final prefix under TFK_CTC_LM_EOS: (tot + g) + lm_weight * lm[ctx][O - 1]
+__device__ __forceinline__ float beam_lm_end(float key, float w, float lmv) {
+#pragma clang fp contract(off)
+  return key + w * lmv;
+}
+
+// f(q) for q in [0, cpt), cpt <= kBeamRun uniform over the wave (an SGPR): fully unrolled, so that q is a constant in every
+// copy of f and a register array indexed by it stays in registers; scalar branches skip what lies beyond cpt, eight at a time
+template <class F>
+__device__ __forceinline__ void beam_for_run(int cpt, F f) {
+#pragma unroll
+  for (int q0 = 0; q0 < kBeamRun; q0 += 8)
+    if (q0 < cpt) {
+#pragma unroll
+      for (int q = q0; q < (q0 + 8 < kBeamRun ? q0 + 8 : kBeamRun); ++q)
+        if (q < cpt) f(q);
+    }
 }
 
 // The `need`-th largest of the non-zero keys keyf(k), k in [k0, k1) over the block's threads (need <= their number):
@@ -599,11 +637,22 @@ __device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, in
   return prefix;
 }
 
+// LM: the search with a dense n-gram table lm [C, O] (the contract: tfk_ctc_beam_lm in tfkaldi_hip.h).  A frame's table
+// values depend only on the beam (slot i reads row ctx[i]), not on the frame's logits: every thread issues the loads of its
+// own run of candidates at the top of the step, into registers (a fully unrolled run of kBeamRun, cut short at the step's
+// run length, which is uniform), phase A runs under them, and behind A's barrier they are parked in the thread's own
+// keys[] entries, where phase B picks each one up before it writes the key over it.  A survivor's value is loaded once
+// more in D, ahead of its trie probe (an atomic round trip that is on the chain anyway; the reload was not timed on its
+// own).  Issuing the gathers one phase earlier, behind D's barrier of the frame before, was measured slower
+// (profiles/ctc_decode_bench.txt).
+template <bool LM>
 __global__ void __launch_bounds__(kBeamThreads)
 ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U, int T, int W,
                 int top_paths, unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp,
-                int32_t* __restrict__ hyp_len, float* __restrict__ score) {
-  __shared__ BeamSide beam[2];
+                int32_t* __restrict__ hyp_len, float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w,
+                float lm_bonus, int eos, float* __restrict__ am_score) {
+  typedef typename BeamSideOf<LM>::type Side;
+  __shared__ Side beam[2];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
   __shared__ __attribute__((aligned(16))) uint32_t hist[256];
   __shared__ unsigned long long childmask[kCtcBeamMaxWidth];
@@ -627,9 +676,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     path[tid] = -1;
   }
   if (tid == 0) {  // the beam starts as {(): (0, -inf)}
-    BeamSide& b = beam[0];
+    Side& b = beam[0];
     b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
     b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
+    if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
     s_nb = 1;
     s_ndead = 0;
   }
@@ -639,9 +689,22 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   __syncthreads();
 
   for (int t = 0; t < Tn; ++t) {
-    const BeamSide& b = beam[cur];
-    BeamSide& nx = beam[cur ^ 1];
+    const Side& b = beam[cur];
+    Side& nx = beam[cur ^ 1];
     const int nb = s_nb, ndead = s_ndead;
+    float lmv[kBeamRun];
+    if constexpr (LM) {  // this frame's table values: in flight under phase A
+      const int N = nb * O, cpt = ((N + kBeamThreads - 1) / kBeamThreads) | 1;
+      const int k0 = min(tid * cpt, N), k1 = min(k0 + cpt, N);
+      beam_for_run(__builtin_amdgcn_readfirstlane(cpt), [&](int q) {
+        const int k = k0 + q;
+        lmv[q] = 0.f;
+        if (k < k1) {
+          const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
+          lmv[q] = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)c];
+        }
+      });
+    }
     // A
     if (wave == 0) {
       const float z = lane < O ? z_next : -INFINITY;
@@ -659,6 +722,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     const int N = nb * O;
     const int cpt = ((N + kBeamThreads - 1) / kBeamThreads) | 1;  // an odd run per thread: conflict-free LDS strides
     const int k0 = min(tid * cpt, N), k1 = min(k0 + cpt, N);
+    if constexpr (LM)
+      beam_for_run(__builtin_amdgcn_readfirstlane(cpt), [&](int q) {
+        if (k0 + q < k1) keys[k0 + q] = __builtin_bit_cast(uint32_t, lmv[q]);
+      });
     float lmax = NEG;
     for (int k = k0; k < k1; ++k) {
       const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
@@ -666,7 +733,12 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
       beam_candidate(b, lp, i, c, blank, &pbn, &pnbn);
       const bool live = c == blank || !((childmask[i] >> c) & 1ull);
       const float tot = lae(pbn, pnbn);
-      keys[k] = live ? sortable(tot) : 0u;
+      float rank = tot;  // what the beam is cut by; the re-centring (lmax) stays on the acoustic part
+      if constexpr (LM) {
+        const float g = b.g[i];
+        rank = tot + (c == blank ? g : beam_lm_extend(g, lm_w, __builtin_bit_cast(float, keys[k]), lm_bonus));
+      }
+      keys[k] = live ? sortable(rank) : 0u;
       if (live) lmax = fmaxf(lmax, tot);
     }
     lmax = wave_max(lmax);
@@ -725,7 +797,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
         nx.tot[slot] = lae(pbn, pnbn);
         if (c == blank) {
           nx.node[slot] = b.node[i]; nx.parent[slot] = b.parent[i]; nx.last[slot] = b.last[i]; nx.len[slot] = b.len[i];
+          if constexpr (LM) { nx.g[slot] = b.g[i]; nx.ctx[slot] = b.ctx[i]; }
         } else {
+          float lv = 0.f;
+          if constexpr (LM) lv = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)c];  // issued ahead of the trie probe
           // find or insert (parent node, label): the slot is the node's id
           const unsigned long long nk = ((unsigned long long)(uint32_t)b.node[i] << 6) | (unsigned long long)c;
           uint32_t pos = __umulhi((uint32_t)((nk * 0x9E3779B97F4A7C15ull) >> 32), cap);
@@ -736,6 +811,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
             pos = pos + 1u == cap ? 0u : pos + 1u;
           }
           nx.node[slot] = id; nx.parent[slot] = b.node[i]; nx.last[slot] = c; nx.len[slot] = b.len[i] + 1;
+          if constexpr (LM) {
+            nx.g[slot] = beam_lm_extend(b.g[i], lm_w, lv, lm_bonus);
+            nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
+          }
         }
       }
       ++slot;
@@ -763,15 +842,28 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     __syncthreads();
   }
 
-  // the top_paths best of the final beam: higher total, then shorter, then lower slot
-  const BeamSide& b = beam[cur];
+  // the top_paths best of the final beam: higher total (LM: + g, + the end term under TFK_CTC_LM_EOS), then shorter, then
+  // lower slot
+  const Side& b = beam[cur];
   const int nb = s_nb;
+  if constexpr (LM) {  // the combined values, parked in keys[] as floats
+    if (tid < nb) {
+      float v = b.tot[tid] + b.g[tid];
+      if (eos) v = beam_lm_end(v, lm_w, lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank]);
+      keys[tid] = __builtin_bit_cast(uint32_t, v);
+    }
+    __syncthreads();
+  }
+  auto final_value = [&](int i) -> float {
+    if constexpr (LM) return __builtin_bit_cast(float, keys[i]);
+    else return b.tot[i];
+  };
   if (tid < nb) {
-    const uint32_t kj = sortable(b.tot[tid]);
+    const uint32_t kj = sortable(final_value(tid));
     const int lj = b.len[tid];
     int rank = 0;
     for (int i = 0; i < nb; ++i) {
-      const uint32_t ki = sortable(b.tot[i]);
+      const uint32_t ki = sortable(final_value(i));
       const int li = b.len[i];
       rank += ki > kj || (ki == kj && (li < lj || (li == lj && i < tid)));
     }
@@ -785,7 +877,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     for (int f = L + tid; f < Tn; f += kBeamThreads) out[f] = -1;
     if (tid == 0) {
       hyp_len[(size_t)n * U + u] = L;
-      score[(size_t)n * U + u] = (j >= 0 && b.tot[j] > -1e29f) ? (float)(off + (double)b.tot[j]) : -INFINITY;
+      const bool alive = j >= 0 && b.tot[j] > -1e29f;
+      score[(size_t)n * U + u] = alive ? (float)(off + (double)final_value(j)) : -INFINITY;
+      if constexpr (LM)
+        if (am_score) am_score[(size_t)n * U + u] = alive ? (float)(off + (double)b.tot[j]) : -INFINITY;
     }
   }
   if (tid < top_paths && path[tid] >= 0) {  // back-trace through the parent links, labels land in forward order
@@ -1010,12 +1105,24 @@ const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths) {
   return nullptr;
 }
 
+int ctc_lm_contexts(int O, int order) {
+  int C = 1;
+  for (int n = 1; n < order; ++n) C *= O;
+  return C;
+}
+
 void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
-                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score) {
+                     int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score, const CtcLm* lm,
+                     float* am_score) {
   if (U <= 0) return;
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie, hyp,
-                     hyp_len, score);
+  if (lm)
+    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
+                       hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus, (int)lm->eos,
+                       am_score);
+  else
+    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
+                       hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, (float*)nullptr);
 }
 
 // scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]

@@ -32,6 +32,7 @@ class Engine(object):
         self.F, self.L, self.H, self.O = cfg.input_dim, cfg.num_layers, cfg.num_units, cfg.output_dim
         self.batch_norm = bool(cfg.batch_norm)
         self._h = c_void_p()
+        self._lm_table = None  # the NgramLM table tfk_ctc_lm_set holds (ctc_set_lm)
         self._state = None
         self._stream = None
         self._cb = None
@@ -353,17 +354,17 @@ class Engine(object):
                              % (what, label_lens.size, int(label_lens.sum()), utt_lens.size, labels.size))
         return utt_lens, labels, label_lens
 
-    def _decode(self, fn, frames, utt_lens, refs, outputs, result, extra=(), raw=None):
+    def _decode(self, fn, frames, utt_lens, refs, outputs, result, extra=(), raw=None, own_flags=0):
         """One call of a forward-only CTC entry `fn`: tfk_ctc_X on spliced frames [sum(utt_lens), F], or tfk_ctc_X_raw on
         unspliced ones with raw = (context_width, cmvn).  refs: (labels, label_lens) after _refs.  outputs(rows, U) makes
         the arrays the entry fills, in the order of its signature (None: a NULL pointer); with rows == 0 -- only zero-frame
-        utterances, the engine is not called -- it fills them itself.  extra: the entry's own integer arguments.
-        Returns result(utt_lens, *arrays)."""
+        utterances, the engine is not called -- it fills them itself.  extra: the entry's own arguments behind the common ones,
+        own_flags: its own flag bits.  Returns result(utt_lens, *arrays)."""
         def run(ptr, ld, rows, lens, raw_args, flags):
             outs = outputs(rows, lens.size)
             if rows:
                 check(fn(self._h, ptr, ld, rows, _ptr(lens), lens.size, *raw_args, *extra, _ptr(refs[0]), _ptr(refs[1]),
-                         *[_ptr(o) for o in outs], flags))
+                         *[_ptr(o) for o in outs], flags | own_flags))
             return result(lens, *outs)
         if raw is None:
             X = _f32(frames)
@@ -431,6 +432,60 @@ class Engine(object):
         tensor (TFK_RAW_DEVICE)"""
         return self._beam(self.lib.tfk_ctc_beam_raw, raw, utt_lens, beam_width, top_paths, labels, label_lens,
                           raw=(context_width, cmvn))
+
+    # ---- the same search ranked with a character n-gram language model (neuralNetworks/ctc_lm.NgramLM) ----
+    def ctc_set_lm(self, lm):
+        """Make `lm` (an NgramLM, or None to drop it) the engine's language model (tfk_ctc_lm_set: the table is copied to the
+        device).  Nothing is uploaded when the same table object is already set."""
+        if lm is None:
+            if self._lm_table is not None:
+                check(self.lib.tfk_ctc_lm_set(self._h, c_void_p(None), 0))
+                self._lm_table = None
+            return
+        lm.check(self.O)
+        if self._lm_table is lm.table:
+            return
+        self._lm_table = None
+        check(self.lib.tfk_ctc_lm_set(self._h, _ptr(lm.table), lm.order))
+        self._lm_table = lm.table
+
+    def _beam_lm(self, fn, frames, utt_lens, lm, beam_width, top_paths, labels, label_lens, raw=None):
+        beam_width, top_paths = int(beam_width), int(top_paths)
+        if not 1 <= top_paths <= beam_width:
+            raise ValueError("top_paths %d outside [1, beam_width = %d]" % (top_paths, beam_width))
+        utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, True, "references")
+        self.ctc_set_lm(lm)
+
+        def outputs(rows, U):  # (no frames: the empty hypothesis, acoustic score 0, combined 0 or the model's end term)
+            score = np.full((top_paths, U), -np.inf, dtype=np.float32)
+            am = score.copy()
+            am[0] = 0.0
+            score[0] = np.float32(lm.weight) * lm.table[-1, -1] if lm.end_of_sequence else 0.0
+            edits = None if labels is None else (np.empty(U, dtype=np.int32) if rows else label_lens.copy())
+            return np.empty((top_paths, rows), dtype=np.int32), np.zeros((top_paths, U), dtype=np.int32), score, am, edits
+
+        def result(lens, hyp, hyp_len, score, am, edits):
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
+            return hyps, np.ascontiguousarray(score.T), np.ascontiguousarray(am.T), edits
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result,
+                            (beam_width, top_paths, c_float(lm.weight), c_float(lm.label_bonus)), raw,
+                            _lib.CTC_LM_EOS if lm.end_of_sequence else 0)
+
+    def ctc_beam_lm(self, X, utt_lens, lm, beam_width=100, top_paths=1, labels=None, label_lens=None):
+        """ctc_beam with prefixes ranked by acoustic score + language-model score (tfk_ctc_beam_lm; the search is stated in
+        include/tfkaldi_hip.h).  lm: an NgramLM over this model's labels -- its table is set on the engine if it is not
+        already, its weight, label bonus and end-of-sequence switch go with the call.  Returns (hyps, scores, am_scores,
+        edits): as ctc_beam, scores the COMBINED values the paths are ordered by, am_scores float32 [U, top_paths] their
+        acoustic parts; edits of the best path by combined score."""
+        return self._beam_lm(self.lib.tfk_ctc_beam_lm, X, utt_lens, lm, beam_width, top_paths, labels, label_lens)
+
+    def ctc_beam_lm_raw(self, raw, utt_lens, context_width, lm, cmvn=None, beam_width=100, top_paths=1, labels=None,
+                        label_lens=None):
+        """ctc_beam_lm on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        return self._beam_lm(self.lib.tfk_ctc_beam_lm_raw, raw, utt_lens, lm, beam_width, top_paths, labels, label_lens,
+                             raw=(context_width, cmvn))
 
     # ---- CTC forced alignment: the Viterbi path of the known label sequence, per frame the label POSITION it emits ----
     def _align(self, fn, frames, utt_lens, labels, label_lens, raw=None):

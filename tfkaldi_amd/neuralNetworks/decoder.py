@@ -125,6 +125,18 @@ class Decoder(object):
             return [], np.zeros((0, top_paths), dtype=np.float32)
         return self._ctc("ctc_beam", utterances, beam_width=beam_width, top_paths=top_paths)[:2]
 
+    def ctc_beam_search_lm(self, utterances, lm, beam_width=100, top_paths=1):
+        """ctc_beam_search with a character n-gram language model (ctc_lm.NgramLM; tfk_ctc_beam_lm): prefixes are ranked by
+        acoustic score + lm.weight * model log-probability + lm.label_bonus per label.  Returns (hyps, scores, am_scores):
+        as ctc_beam_search, scores the combined values, am_scores float32 [U, top_paths] their acoustic parts."""
+        if len(utterances) == 0:
+            return [], np.zeros((0, top_paths), dtype=np.float32), np.zeros((0, top_paths), dtype=np.float32)
+        lens, raw, frames, context_width, cmvn = self._batch(utterances)
+        kw = dict(beam_width=beam_width, top_paths=top_paths)
+        if raw:
+            return self.engine.ctc_beam_lm_raw(frames, lens, context_width, lm, cmvn=cmvn, **kw)[:3]
+        return self.engine.ctc_beam_lm(frames, lens, lm, **kw)[:3]
+
     def ctc_align(self, utterances, targets):
         """Forced alignment of a CTC model (tfk_ctc_align; the algorithm is stated in include/tfkaldi_hip.h): every
         utterance in ONE forward pass, the Viterbi path of its known label sequence `targets[u]` (one int label array per

@@ -362,14 +362,18 @@ class CTCTrainer(Trainer):
     def compute_loss(self, targets, logits, logit_seq_length, target_seq_length):
         return "ctc"
 
-    def label_errors(self, inputs, targets, beam_width=None):
+    def label_errors(self, inputs, targets, beam_width=None, lm=None):
         """Label errors of the batch under best-path decoding -- tf.nn.ctc_greedy_decoder(merge_repeated=True) followed by
         tf.edit_distance(normalize=False), the reference framework's standard CTC evaluation -- in evaluation mode, on the
         device (tfk_ctc_greedy).  Returns (sum of the Levenshtein distances, sum of the reference lengths) over the batch as
         Python ints: a corpus label error rate is sum(edits) / sum(reference labels) over its batches.  None when there is
         no data (as evaluate).  COLLECTIVE under data parallelism: the micro-batches are dealt to the ranks as in evaluate
         and the two counts summed over them.  beam_width: an int decodes by prefix beam search of that width instead
-        (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path."""
+        (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path.  lm: a ctc_lm.NgramLM ranks
+        the beam's prefixes by acoustic + language-model score (tfk_ctc_beam_lm); it needs a beam_width."""
+        if lm is not None and beam_width is None:
+            raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
         if inputs is None or targets is None:
             return None
-        return self.dp.label_errors(self.engine, self._microbatches(inputs, targets), beam_width=beam_width)
+        kw = {} if lm is None else {"lm": lm}
+        return self.dp.label_errors(self.engine, self._microbatches(inputs, targets), beam_width=beam_width, **kw)

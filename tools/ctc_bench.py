@@ -6,7 +6,11 @@ hypotheses: the edit distance's worst case) and once with the blank biased so th
 length; then, on the same two workloads, the beam leg: prefix beam search on the device (tfk_ctc_beam) at W = 1, 10, 100 --
 ms per call, the engine profiler's time of the ctc_beam_search kernel, label error rate greedy vs beam, the largest
 |device - float64| of a best score, and the host alternative (the float64 numpy restatement the tests use, timed on ONE
-utterance of the same logits and scaled to the batch); then the align leg: forced alignment of every utterance to its
+utterance of the same logits and scaled to the batch); then the model leg: the same search ranked with a character n-gram
+language model (tfk_ctc_beam_lm; NgramLM.from_label_sequences over the reference labels at orders 1 and 3, weight 0.5, bonus
+1.0) at W = 1, 10, 100 -- ms per call, the profiler's time of the ctc_beam_search_lm kernel, that time per frame step and its
+ratio to the acoustic kernel's, label error rate greedy / beam / beam + model, |device - float64| of one best combined
+score; then the align leg: forced alignment of every utterance to its
 reference on the device (tfk_ctc_align) -- ms per call, the profiler's time of the ctc_align kernels and that time per frame
 step, and the host alternative (the float64 numpy restatement of the tests on the same logits, all utterances).
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone."""
@@ -24,6 +28,7 @@ from tfkaldi_amd.engine import Engine  # noqa: E402
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from test_ctc_align_host import viterbi_align  # noqa: E402
 from test_ctc_beam_host import prefix_beam_search  # noqa: E402
+from test_ctc_beam_lm_host import prefix_beam_search_lm  # noqa: E402
 
 
 def main():
@@ -142,12 +147,13 @@ def decode_leg(eng, X, utt, labels, lab, rng):
             print("    %-28s n=%4d %9.1f us/call" % (s["name"], s["launches"] // K, s["total_ms"] / K * 1e3))
         print("    eval forward device time %.1f us, decode kernels %.1f us (%.1f %% of the forward)" % (fwd * 1e3, dec * 1e3,
                                                                                                      100.0 * dec / fwd))
-        beam_leg(eng, X, utt, labels, lab, case, edits)
+        beam = beam_leg(eng, X, utt, labels, lab, case, edits)
+        lm_leg(eng, X, utt, labels, lab, case, edits, beam)
         align_leg(eng, X, utt, labels, lab, case)
 
 
 def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
-    K = 10
+    K, out = 10, {}
     logits = eng.posteriors(X, raw_logits=True)
     for W in (1, 10, 100):
         hyps, scores, edits = eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)
@@ -171,6 +177,39 @@ def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
               % (case, W, ms, kern, kern * 1e3 / max(utt), edits.sum() / np.sum(lab), greedy_edits.sum() / np.sum(lab),
                  scores[0, 0], s64[0, 0], abs(scores[0, 0] - s64[0, 0]), np.array_equal(hyps[0][0], h64[0][0]), host,
                  host * len(utt), len(utt)))
+        out[W] = (kern, edits.sum() / np.sum(lab))
+    return out
+
+
+def lm_leg(eng, X, utt, labels, lab, case, greedy_edits, beam):
+    """beam: {W: (acoustic kernel ms, acoustic label error rate)} of beam_leg on the same workload"""
+    from tfkaldi_amd.neuralNetworks.ctc_lm import NgramLM
+    K = 10
+    logits = eng.posteriors(X, raw_logits=True)
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    for order in (1, 3):
+        lm = NgramLM.from_label_sequences(refs, eng.O - 1, order, weight=0.5, label_bonus=1.0)
+        call = lambda W: eng.ctc_beam_lm(X, utt, lm, beam_width=W, labels=labels, label_lens=lab)
+        for W in (1, 10, 100):
+            hyps, scores, am, edits = call(W)
+            for _ in range(2):
+                call(W)
+            t0 = time.perf_counter()
+            for _ in range(K):
+                call(W)
+            ms = (time.perf_counter() - t0) / K * 1e3
+            eng.profile_begin()
+            for _ in range(K):
+                call(W)
+            stats = {s["name"]: s for s in eng.profile_end()}
+            kern = stats["ctc_beam_search_lm"]["total_ms"] / K
+            h64, s64, _ = prefix_beam_search_lm(logits[:utt[0]], utt[:1], W, 1, lm)
+            print("  beam + model (%s) order %d W=%3d: tfk_ctc_beam_lm %8.3f ms/call, ctc_beam_search_lm kernel %8.3f ms (%.2f us "
+                  "per frame step, %.3f x the acoustic kernel); label error rate greedy %.3f beam %.3f beam + model %.3f; best "
+                  "combined score of utterance 0: device %.5f float64 %.5f (|diff| %.1e, same labels: %s)"
+                  % (case, order, W, ms, kern, kern * 1e3 / max(utt), kern / beam[W][0], greedy_edits.sum() / np.sum(lab),
+                     beam[W][1], edits.sum() / np.sum(lab), scores[0, 0], s64[0, 0], abs(scores[0, 0] - s64[0, 0]),
+                     np.array_equal(hyps[0][0], h64[0][0])))
 
 
 def align_leg(eng, X, utt, labels, lab, case):
