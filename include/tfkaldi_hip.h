@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 12
+#define TFK_ABI_VERSION 13
 
 typedef struct tfk_engine tfk_engine;
 
@@ -141,7 +141,8 @@ enum { /* flags */
   TFK_RAW_DEVICE = 16,     /* the *_raw entry points: `raw` is a device pointer -- features that never left HBM, e.g. the output
                             * of tfk_feat_compute; everything else (y, utt_len, cmvn, out) stays a host pointer.  The producer's
                             * work must be complete, or ordered before the engine's stream (tfk_stream), when the call is made. */
-  TFK_CTC_LM_EOS = 32      /* tfk_ctc_beam_lm*: the final ranking and score add the model's end-of-sequence term */
+  TFK_CTC_LM_EOS = 32,     /* tfk_ctc_beam_lm*: the final ranking and score add the model's end-of-sequence term */
+  TFK_CTC_LM = 64          /* tfk_ctc_beam_topk*: the engine's language model ranks the prefixes */
 };
 
 /* Replaces `update_gradients_op.run(feed_dict)` (trainer.py:160-169, 325-332) for ONE micro-batch,
@@ -309,8 +310,10 @@ int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O
  *   single row 0; ctx(p + c) = (ctx(p) * O + c) mod C.  table[ctx][c], c < O - 1: the natural-log probability of label c
  *   after that context.  Column O - 1: the log-probability that the sequence ENDS after it (read only under TFK_CTC_LM_EOS).
  * `table` is a HOST pointer to O^order floats; the call copies them to the device (64 MB at O = 64, order 4) and replaces any
- * model the engine holds; table == NULL drops it.  An order outside [1, 4] or a non-finite entry (tfk_last_error names its
- * index) is rejected and the engine keeps the model it had.  Parameters, accumulators and statistics are not touched;
+ * model the engine holds; table == NULL drops it.  (ABI 13) output_dim <= 65536 and O^order <= 2^26 entries (256 MB: O = 8192
+ * at order 2, O = 400 at order 3); a larger table is refused with the limit in the message, before anything is read or
+ * allocated.  An order outside [1, 4] or a non-finite entry (tfk_last_error names its index) is rejected too; in every such
+ * case the engine keeps the model it had.  A model over more than 64 outputs serves tfk_ctc_beam_topk only.  Parameters, accumulators and statistics are not touched;
  * tfk_ctc_beam / tfk_ctc_beam_raw ignore the model. */
 int tfk_ctc_lm_set(tfk_engine* e, const float* table, int32_t order);
 /* (ABI 12) CTC prefix beam search with that model (Hannun et al. 2014: prefixes ranked by p_ctc * p_lm^alpha * |prefix|^beta;
@@ -346,6 +349,48 @@ int tfk_ctc_beam_lm_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t 
 int tfk_ctc_beam_lm_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                            int32_t beam_width, int32_t top_paths, const float* lm_dev, int32_t order, float lm_weight,
                            float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score);
+/* (ABI 13) CTC prefix beam search with PER-FRAME LABEL PRUNING, for any output_dim up to 65536: per frame only the label_topk
+ * most probable labels may start a new label (`cutoff_top_n` elsewhere), which bounds a frame's candidates by
+ * beam_width * (K + 1) whatever output_dim is.  Everything of tfk_ctc_beam and tfk_ctc_beam_lm holds unless stated otherwise:
+ * the states (pb, pnb), stay and extend, merging by logaddexp in the fixed order, the rank key logaddexp(pb', pnb') + g, ties
+ * (the shorter prefix, then the lower candidate index), re-centring on the acoustic part with the offset kept in double, the
+ * final ranking, TFK_CTC_LM_EOS, and the layout of hyp, hyp_len, score, am_score, edits.  The differences (this comment is the
+ * contract):
+ *   K = min(label_topk, O - 1), 1 <= label_topk <= 63.
+ *   keep(t), for frame t, is the set of the K labels (never the blank) with the largest logits in row t; among equal logits
+ *   the lower class wins.
+ *   Extend sees only kept labels: for c not in keep(t) there is no candidate (p, c), and its term does not merge into a beam
+ *   prefix that equals p + c either -- the extension behaves as if lp[c] = -inf.
+ *   Stay is unchanged: it uses the true lp[blank] and the true lp[last(p)], whether or not last(p) is in keep(t).
+ *   Candidates of beam slot i are its kept labels in ascending class order, then the stay candidate; the candidate index (the
+ *   last tie-break) is i * (K + 1) + q.  With K = O - 1 this is tfk_ctc_beam's order.
+ *   So the search sums exactly the alignments in which every frame that BEGINS a label occurrence -- its class is a label and
+ *   differs from the previous frame's class -- has that label in its keep(t); `score` (am_score with a model) stays a lower
+ *   bound of the hypothesis' full CTC probability.
+ * flags: TFK_CTC_LM -- the engine's model (tfk_ctc_lm_set) ranks the prefixes with lm_weight and label_bonus, as
+ * tfk_ctc_beam_lm; non-zero return if none is set.  Without it the search is acoustic, lm_weight / label_bonus are ignored
+ * and am_score (may be NULL) equals score.  TFK_CTC_LM_EOS requires TFK_CTC_LM; alone it returns non-zero.
+ * Limits: 2 <= output_dim <= 65536, 1 <= top_paths <= beam_width <= 128, T <= 524286, 1 <= label_topk <= 63; a shape outside
+ * them returns non-zero and tfk_last_error names the limit.
+ * With output_dim <= 64 and label_topk >= output_dim - 1, hyp, hyp_len, score and am_score equal tfk_ctc_beam's /
+ * tfk_ctc_beam_lm's bit for bit: the row's log-sum-exp is formed as there (lp = z - (mx + logf(se)), se summed by the same
+ * wave butterfly), and the extension by a label and the stay on it use the same fp32 value z - (mx + logf(se)). */
+int tfk_ctc_beam_topk(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t beam_width, int32_t top_paths, int32_t label_topk, float lm_weight, float label_bonus,
+                      const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score,
+                      float* am_score, int32_t* edits, int flags);
+/* The same on UNSPLICED frames (as tfk_ctc_beam_raw; flags: those and TFK_RAW_DEVICE). */
+int tfk_ctc_beam_topk_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                          int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths, int32_t label_topk,
+                          float lm_weight, float label_bonus, const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp,
+                          int32_t* hyp_len, float* score, float* am_score, int32_t* edits, int flags);
+/* (ABI 13) Tests / tools: that search alone on logits, as tfk_ctc_beam_lm_logits; DEVICE pointers.  lm_dev == NULL: no model
+ * (order, lm_weight, label_bonus ignored, flags must be 0); else lm_dev [O^order <= 2^26]; flags: 0 or TFK_CTC_LM_EOS.
+ * am_score may be NULL.  The scratch of the call comes from the stream's memory pool. */
+int tfk_ctc_beam_topk_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                             int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* lm_dev, int32_t order,
+                             float lm_weight, float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score,
+                             float* am_score);
 /* (ABI 11) CTC forced alignment: the most probable alignment of every utterance's KNOWN label sequence -- which frames emit
  * which label, and with what probability (time stamps and segments, corpus cleaning by alignment score, frame-level targets).
  * Eval-mode forward of the flat utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); labels / label_len as

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -48,7 +48,7 @@ WEIGHTS, BIASES, BN_BETA, BN_MOVING_MEAN, BN_MOVING_VAR = range(5)
 SLOT_PARAM, SLOT_GRAD, SLOT_ADAM_M, SLOT_ADAM_V = range(4)
 (GLOBAL_STEP, LEARNING_RATE_FACT, INITIALISED_LAYERS, ADAM_STEPS, BATCH_LOSS, NUM_FRAMES,
  LEARNING_RATE) = range(7)
-DEVICE_PTRS, LAST_MICROBATCH, LOG_DIV_PRIOR, RAW_LOGITS, RAW_DEVICE, CTC_LM_EOS = 1, 2, 4, 8, 16, 32
+DEVICE_PTRS, LAST_MICROBATCH, LOG_DIV_PRIOR, RAW_LOGITS, RAW_DEVICE, CTC_LM_EOS, CTC_LM = 1, 2, 4, 8, 16, 32, 64
 DBG_LOGITS, DBG_HIDDEN, DBG_DROPOUT_MASK, DBG_PREACT, DBG_BN_MEAN, DBG_BN_RSTD = range(6)
 GEMM_NN, GEMM_NT, GEMM_TN = range(3)
 EPI_BIAS, EPI_ACCUM, EPI_RELU = 1, 2, 4
@@ -149,6 +149,14 @@ SYMBOLS = {
                                     c_int]),
     "tfk_ctc_beam_lm_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                        c_void_p, c_int32, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tfk_ctc_beam_topk": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "tfk_ctc_beam_topk_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                      c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int]),
+    "tfk_ctc_beam_topk_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32,
+                                         c_int32, c_void_p, c_int32, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "tfk_ctc_align": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "tfk_ctc_align_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int]),

@@ -83,6 +83,27 @@ const char* ctc_beam_limits(int O, int T, int U, int W, int top_paths);
 void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
                      int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score,
                      const CtcLm* lm = nullptr, float* am_score = nullptr);
+// The same search with PER-FRAME LABEL PRUNING, for any O up to kCtcTopkMaxClasses (the contract is the comment at
+// tfk_ctc_beam_topk in tfkaldi_hip.h): at frame t only the K = min(label_topk, O - 1) labels with the largest logits of row t
+// (ties: the lower class) may extend a prefix; a stay still uses the true lp[last(p)].  Candidates of slot i are its kept
+// labels in ascending class order, then the stay, so with K == O - 1 (O <= 64) every output equals ctc_beam_search's bit for
+// bit.  ctc_beam_topk_rows is the row pre-pass (one wave per row, off the sequential chain): row t of `pre`
+// (kCtcTopkRowWords words) = [64 kept labels ascending, 0x7fffffff beyond K | 64 values z - lsum | lsum = mx + logf(se) |
+// z[blank] - lsum]; ctc_beam_topk_search is the search on those rows.  pre: ctc_beam_topk_scratch_words(T) 32-bit words,
+// trie: ctc_beam_scratch_words(T, U, W) 64-bit words.  lm / am_score as ctc_beam_search, except that am_score (if not NULL) is
+// also written without a model, where it equals score; the table has at most kCtcLmMaxEntries entries (ctc_lm_entries:
+// O^order, or a value above the limit when it would exceed it).
+constexpr int kCtcTopkMaxClasses = 65536;
+constexpr int kCtcTopkMaxLabels = 63;
+constexpr int kCtcTopkRowWords = 2 * 64 + 2;
+constexpr size_t kCtcLmMaxEntries = (size_t)1 << 26;
+size_t ctc_lm_entries(int O, int order);
+size_t ctc_beam_topk_scratch_words(int T);
+const char* ctc_beam_topk_limits(int O, int T, int U, int W, int top_paths, int label_topk);
+void ctc_beam_topk_rows(hipStream_t s, const float* logits, int ld, int O, int T, int label_topk, uint32_t* pre);
+void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
+                          int top_paths, int label_topk, unsigned long long* trie, const uint32_t* pre, int32_t* hyp,
+                          int32_t* hyp_len, float* score, const CtcLm* lm = nullptr, float* am_score = nullptr);
 // Forced alignment: the most probable path through the CTC lattice of every utterance's KNOWN label sequence (the contract
 // is the comment at tfk_ctc_align in tfkaldi_hip.h).  States as the loss: n = 2S + 1, blank, l_0, blank, ..., blank;
 // transitions as ctc_alpha_beta (stay, +1, +2 into a label that differs from the label two states back); start in state

@@ -895,6 +895,429 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   }
 }
 
+// ---- prefix beam search with per-frame label pruning (tfk_ctc_beam_topk; any output_dim up to kCtcTopkMaxClasses) ----
+//
+// Two launches.  ctc_row_topk_kernel, parallel over the frames and off the sequential chain, turns every row into what the
+// search needs of it (kCtcTopkRowWords words): the K kept labels in ascending class order, their log-probabilities
+// z - lsum, lsum = mx + logf(se) itself and the blank's log-probability.  ctc_beam_topk_kernel is the frame step of
+// ctc_beam_kernel over nb * (K + 1) candidates: slot i's candidate q < K extends by the frame's q-th kept label, q == K stays.
+// It is a sibling, not a third instantiation of that body: a class there is a 6-bit column of lp[] / childmask / the trie key,
+// here a label is a position q in the frame's list plus a 16-bit class, and the existing code objects stay what they were.
+
+// ONE WAVE PER ROW (a block is one wave, so __syncthreads is a wave barrier).  The row is read from HBM once; the later
+// passes (sum, the radix passes, the compaction) find it in the cache.  For O <= 64 lane c holds class c and mx / se are formed
+// by the butterflies of ctc_beam_kernel's phase A: the same bits.  The K largest label logits by an 8-bit radix select over
+// order-preserving keys (integer LDS atomics: the counts do not depend on scheduling); of the keys EQUAL to the K-th the
+// lowest classes are taken, counted in class order during the compaction, which also leaves the labels ascending.
+__global__ void __launch_bounds__(64)
+ctc_row_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, uint32_t* __restrict__ pre) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ int sel[4];
+  const int lane = threadIdx.x;
+  const float* z = logits + (size_t)blockIdx.x * ld;
+  uint32_t* out = pre + (size_t)blockIdx.x * kCtcTopkRowWords;
+  const int blank = O - 1;
+  float mx = -INFINITY;
+  for (int c = lane; c < O; c += 64) mx = fmaxf(mx, z[c]);
+  mx = wave_max(mx);
+  float se = 0.f;
+  for (int c = lane; c < O; c += 64) se += expf(z[c] - mx);
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+  const float lsum = mx + logf(se);
+  for (int i = lane; i < 256; i += 64) hist[i] = 0u;
+  __syncthreads();
+  // the K-th largest key among the labels [0, blank): prefix; `need` of the keys equal to it belong to the K
+  uint32_t prefix = 0;
+  int need = K;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int c = lane; c < blank; c += 64) {
+      const uint32_t key = sortable(z[c]);
+      if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    {
+      const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
+      const int s = (int)(h.x + h.y + h.z + h.w);
+      int incl = s;  // this lane's bins and every higher one
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_down(incl, o);
+        if (lane + o < 64) incl += v;
+      }
+      int above = incl - s;
+      const uint32_t hv[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+      for (int q = 3; q >= 0; --q) {
+        const int c = (int)hv[q];
+        if (need > above && need <= above + c) {
+          sel[0] = 4 * lane + q;
+          sel[1] = need - above;
+        }
+        above += c;
+      }
+      reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    prefix |= (uint32_t)sel[0] << shift;
+    need = sel[1];  // (the next pass writes sel behind its own barrier)
+  }
+  // compaction in class order: a label is kept if its key is above the K-th, or equals it and fewer than `need` such labels
+  // lie below it
+  int n = 0, ties = 0;  // kept so far, keys equal to the K-th seen so far (uniform)
+  for (int c0 = 0; c0 < blank && n < K; c0 += 64) {
+    const int c = c0 + lane;
+    const float v = c < blank ? z[c] : 0.f;
+    const uint32_t key = c < blank ? sortable(v) : 0u;
+    const bool eq = key == prefix;
+    const uint64_t me = __ballot(eq);
+    const int eq_below = __builtin_amdgcn_mbcnt_hi((uint32_t)(me >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)me, 0u));
+    const bool keep = key > prefix || (eq && ties + eq_below < need);
+    const uint64_t mk = __ballot(keep);
+    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+    if (keep && n + below < K) {  // (n + below < K always holds for finite rows; the guard keeps a NaN row in bounds)
+      out[n + below] = (uint32_t)c;
+      out[64 + n + below] = __builtin_bit_cast(uint32_t, v - lsum);
+    }
+    n += __popcll(mk);
+    ties += __popcll(me);
+  }
+  n = min(n, K);
+  if (lane >= n) {  // the unused tail (and whatever a NaN row left open): no label, log-probability -inf
+    out[lane] = 0x7fffffffu;
+    out[64 + lane] = __builtin_bit_cast(uint32_t, NEG);
+  }
+  if (lane == 0) {
+    out[128] = __builtin_bit_cast(uint32_t, lsum);
+    out[129] = __builtin_bit_cast(uint32_t, z[blank] - lsum);
+  }
+}
+
+// (pb', pnb') of the pruned search's candidates: beam_candidate's expressions with the log-probabilities handed in.
+// stay: lpb = lp[blank], lpl = lp[last(i)] (the TRUE value, kept or not), merge = last(i) is kept at this frame, so its
+// parent's extension exists and is collected
+__device__ __forceinline__ void beam_topk_stay(const BeamSide& b, int i, float lpb, float lpl, bool merge, float* pbn,
+                                               float* pnbn) {
+  const int l = b.last[i];
+  *pbn = fmaxf(b.tot[i] + lpb, NEG);
+  float v = l >= 0 ? fmaxf(b.pnb[i] + lpl, NEG) : NEG;
+  const int s = b.src[i];
+  if (s >= 0 && merge) v = lae(v, fmaxf((b.last[s] == l ? b.pb[s] : b.tot[s]) + lpl, NEG));
+  *pnbn = v;
+}
+__device__ __forceinline__ void beam_topk_extend(const BeamSide& b, int i, int c, float lpc, float* pbn, float* pnbn) {
+  *pbn = NEG;
+  *pnbn = fmaxf((c == b.last[i] ? b.pb[i] : b.tot[i]) + lpc, NEG);
+}
+
+// The frame step of ctc_beam_kernel (phases A to E as stated there) with these differences:
+//   A  the frame's kept labels flab[K] / their log-probabilities fval[K] / lp[blank] were put into LDS by wave 0 in phase E of
+//      the frame before, from registers it loaded from the pre-pass rows a whole step earlier; beam slot j gathers its own
+//      z[t, last[j]] (issued at the top of the step, beside the model gathers) and subtracts lsum[t] -- the expression the
+//      pre-pass evaluated for a kept label, so a stay and an extension by the same label use the same bits -- and looks
+//      last[j] up in flab by binary search: lpos[j] = its position or -1.  The child mask is over POSITIONS.  The dead
+//      candidates are counted here, not in phase E: a child kills its parent's extension only where lpos >= 0, and phase C
+//      must run whenever the LIVE candidates exceed W
+//   B-D  candidate k = i * (K + 1) + q: q < K extends by flab[q], q == K stays; a stay collects its parent's extension only if
+//      lpos >= 0.  With K == O - 1 flab is 0 .. O - 2 and k, the keys, the tie-breaks and every value are ctc_beam_kernel's
+//   the trie key holds a 16-bit label
+template <bool LM>
+__global__ void __launch_bounds__(kBeamThreads)
+ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, const uint32_t* __restrict__ pre,
+                     const int32_t* __restrict__ seg, int U, int T, int W, int top_paths,
+                     unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp, int32_t* __restrict__ hyp_len,
+                     float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w, float lm_bonus, int eos,
+                     float* __restrict__ am_score) {
+  typedef typename BeamSideOf<LM>::type Side;
+  __shared__ Side beam[2];
+  __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ unsigned long long childmask[kCtcBeamMaxWidth];
+  __shared__ int flab[64];
+  __shared__ float fval[64];
+  __shared__ float lpl[kCtcBeamMaxWidth];
+  __shared__ int lpos[kCtcBeamMaxWidth];
+  __shared__ float s_lpb;
+  __shared__ float wmax[4];
+  __shared__ int wsum[4];
+  __shared__ int sel[4];
+  __shared__ int s_nb, s_ndead;
+  __shared__ int path[kCtcBeamMaxWidth];
+
+  const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int blank = O - 1, K1 = K + 1;
+  const uint32_t cap = 2u * (uint32_t)Tn * (uint32_t)W + 64u;  // this utterance's share of the table: load <= 1/2
+  unsigned long long* tab = trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
+  const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)K1 - 1u) / (unsigned)K1);  // k / K1 for k < 2^13
+  const uint32_t* prow = pre + (size_t)r0 * kCtcTopkRowWords;
+
+  hist[tid] = 0u;
+  if (tid < kCtcBeamMaxWidth) {
+    childmask[tid] = 0ull;
+    path[tid] = -1;
+  }
+  if (tid == 0) {  // the beam starts as {(): (0, -inf)}
+    Side& b = beam[0];
+    b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
+    b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
+    if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
+    s_nb = 1;
+    s_ndead = 0;
+  }
+  int cur = 0;
+  double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
+  // wave 0: the next frame's list, in registers until phase E; every thread: the next frame's lsum
+  uint32_t lab_next = 0x7fffffffu, val_next = 0u, lpb_next = 0u;
+  float lsum_next = 0.f;
+  if (Tn > 0) {
+    lsum_next = __builtin_bit_cast(float, prow[128]);
+    if (wave == 0) {
+      flab[lane] = min((int)prow[lane], blank - 1);  // (the list's unused tail is no label: kept inside the alphabet)
+      fval[lane] = __builtin_bit_cast(float, prow[64 + lane]);
+      if (lane == 0) s_lpb = __builtin_bit_cast(float, prow[129]);
+    }
+  }
+  __syncthreads();
+
+  for (int t = 0; t < Tn; ++t) {
+    const Side& b = beam[cur];
+    Side& nx = beam[cur ^ 1];
+    const int nb = s_nb;
+    const int N = nb * K1;
+    const int cpt = ((N + kBeamThreads - 1) / kBeamThreads) | 1;  // an odd run per thread: conflict-free LDS strides
+    const int k0 = min(tid * cpt, N), k1 = min(k0 + cpt, N);
+    float lmv[kBeamRun];
+    if constexpr (LM) {  // this frame's table values: in flight under phase A
+      beam_for_run(__builtin_amdgcn_readfirstlane(cpt), [&](int q) {
+        const int k = k0 + q;
+        lmv[q] = 0.f;
+        if (k < k1) {
+          const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
+          if (p != K) lmv[q] = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)flab[p]];
+        }
+      });
+    }
+    const float lsum = lsum_next;
+    float zl = 0.f;
+    int mylast = -1;
+    if (wave != 0 && tid - 64 < nb) {
+      mylast = b.last[tid - 64];
+      if (mylast >= 0) zl = logits[(size_t)(r0 + t) * ld + mylast];
+    }
+    if (t + 1 < Tn) {
+      const uint32_t* pn = prow + (size_t)(t + 1) * kCtcTopkRowWords;
+      lsum_next = __builtin_bit_cast(float, pn[128]);
+      if (wave == 0) {
+        lab_next = pn[lane];
+        val_next = pn[64 + lane];
+        lpb_next = pn[129];
+      }
+    }
+    // A
+    bool kills = false;  // this slot's label is kept at this frame, so its parent's extension by it is dead
+    if (wave != 0 && tid - 64 < nb) {
+      const int j = tid - 64;
+      int pos = -1;
+      if (mylast >= 0) {
+        int lo = 0, hi = K;  // the first position whose label is >= mylast
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (flab[mid] < mylast) lo = mid + 1; else hi = mid;
+        }
+        if (lo < K && flab[lo] == mylast) pos = lo;
+      }
+      lpl[j] = zl - lsum;
+      lpos[j] = pos;
+      const int s = b.src[j];
+      kills = s >= 0 && pos >= 0;
+      if (kills) atomicOr(&childmask[s], 1ull << pos);
+    }
+    if (wave != 0) {  // the dead candidates, counted exactly: a child whose label is pruned here kills nothing
+      const int dead = __popcll(__ballot(kills));
+      if (lane == 0 && dead) atomicAdd(&s_ndead, dead);
+    }
+    __syncthreads();
+    const int ndead = s_ndead;
+    // B
+    const float lpb = s_lpb;
+    if constexpr (LM)
+      beam_for_run(__builtin_amdgcn_readfirstlane(cpt), [&](int q) {
+        if (k0 + q < k1) keys[k0 + q] = __builtin_bit_cast(uint32_t, lmv[q]);
+      });
+    auto candidate = [&](int i, int p, float* pbn, float* pnbn) {
+      if (p == K) beam_topk_stay(b, i, lpb, lpl[i], lpos[i] >= 0, pbn, pnbn);
+      else beam_topk_extend(b, i, flab[p], fval[p], pbn, pnbn);
+    };
+    float lmax = NEG;
+    for (int k = k0; k < k1; ++k) {
+      const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
+      float pbn, pnbn;
+      candidate(i, p, &pbn, &pnbn);
+      const bool live = p == K || !((childmask[i] >> p) & 1ull);
+      const float tot = lae(pbn, pnbn);
+      float rank = tot;  // what the beam is cut by; the re-centring (lmax) stays on the acoustic part
+      if constexpr (LM) {
+        const float g = b.g[i];
+        rank = tot + (p == K ? g : beam_lm_extend(g, lm_w, __builtin_bit_cast(float, keys[k]), lm_bonus));
+      }
+      keys[k] = live ? sortable(rank) : 0u;
+      if (live) lmax = fmaxf(lmax, tot);
+    }
+    lmax = wave_max(lmax);
+    if (lane == 0) wmax[wave] = lmax;
+    __syncthreads();
+    float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (!(m > -1e29f)) m = 0.f;
+    // C
+    uint32_t Kk = 0u, K2 = 0xffffffffu;  // select: key > Kk, or key == Kk and tie-break key >= K2
+    if (N - ndead > W) {
+      int take, have;
+      Kk = beam_radix_select([&](int k) { return keys[k]; }, k0, k1, W, hist, sel, &take, &have);
+      K2 = 0u;
+      if (take < have) {
+        int t2, h2;
+        K2 = beam_radix_select(
+            [&](int k) {
+              const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
+              return keys[k] == Kk ? beam_tiebreak(b.len[i] + (p != K), k) : 0u;
+            },
+            k0, k1, take, hist, sel, &t2, &h2);
+      }
+    }
+    // D
+    int cnt = 0;
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t key = keys[k];
+      if (key > Kk) { ++cnt; continue; }
+      if (key == Kk && K2 != 0xffffffffu) {
+        const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
+        cnt += beam_tiebreak(b.len[i] + (p != K), k) >= K2;
+      }
+    }
+    int incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int slot = incl - cnt;
+    for (int w = 0; w < wave; ++w) slot += wsum[w];
+    const int nb_new = min(wsum[0] + wsum[1] + wsum[2] + wsum[3], W);
+    for (int k = k0; k < k1; ++k) {
+      const uint32_t key = keys[k];
+      const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
+      const bool chosen = key > Kk || (key == Kk && K2 != 0xffffffffu && beam_tiebreak(b.len[i] + (p != K), k) >= K2);
+      if (!chosen) continue;
+      if (slot < W) {
+        float pbn, pnbn;
+        candidate(i, p, &pbn, &pnbn);
+        pbn = fmaxf(pbn - m, NEG);
+        pnbn = fmaxf(pnbn - m, NEG);
+        nx.pb[slot] = pbn;
+        nx.pnb[slot] = pnbn;
+        nx.tot[slot] = lae(pbn, pnbn);
+        if (p == K) {
+          nx.node[slot] = b.node[i]; nx.parent[slot] = b.parent[i]; nx.last[slot] = b.last[i]; nx.len[slot] = b.len[i];
+          if constexpr (LM) { nx.g[slot] = b.g[i]; nx.ctx[slot] = b.ctx[i]; }
+        } else {
+          const int c = flab[p];
+          float lv = 0.f;
+          if constexpr (LM) lv = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)c];  // issued ahead of the trie probe
+          // find or insert (parent node, label): the slot is the node's id
+          const unsigned long long nk = ((unsigned long long)(uint32_t)b.node[i] << 16) | (unsigned long long)c;
+          uint32_t pos = __umulhi((uint32_t)((nk * 0x9E3779B97F4A7C15ull) >> 32), cap);
+          int id = 0;
+          for (uint32_t n = 0; n < cap; ++n) {
+            const unsigned long long old = atomicCAS(&tab[pos], kTrieEmpty, nk);
+            if (old == kTrieEmpty || old == nk) { id = (int)pos; break; }
+            pos = pos + 1u == cap ? 0u : pos + 1u;
+          }
+          nx.node[slot] = id; nx.parent[slot] = b.node[i]; nx.last[slot] = c; nx.len[slot] = b.len[i] + 1;
+          if constexpr (LM) {
+            nx.g[slot] = beam_lm_extend(b.g[i], lm_w, lv, lm_bonus);
+            nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
+          }
+        }
+      }
+      ++slot;
+    }
+    if (tid == 0) {
+      s_nb = nb_new;
+      s_ndead = 0;
+    }
+    off += (double)m;
+    __syncthreads();
+    // E
+    if (tid < kCtcBeamMaxWidth) childmask[tid] = 0ull;
+    if (wave == 0) {  // the next frame's list (nobody reads this frame's any more)
+      flab[lane] = min((int)lab_next, blank - 1);
+      fval[lane] = __builtin_bit_cast(float, val_next);
+      if (lane == 0) s_lpb = __builtin_bit_cast(float, lpb_next);
+    }
+    {
+      int s = -1;
+      if (tid < nb_new) {
+        const int p = nx.parent[tid];
+        for (int i = 0; i < nb_new; ++i)
+          if (nx.node[i] == p) s = i;
+        nx.src[tid] = s;
+      }
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+
+  // the top_paths best of the final beam, as ctc_beam_kernel
+  const Side& b = beam[cur];
+  const int nb = s_nb;
+  if constexpr (LM) {  // the combined values, parked in keys[] as floats
+    if (tid < nb) {
+      float v = b.tot[tid] + b.g[tid];
+      if (eos) v = beam_lm_end(v, lm_w, lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank]);
+      keys[tid] = __builtin_bit_cast(uint32_t, v);
+    }
+    __syncthreads();
+  }
+  auto final_value = [&](int i) -> float {
+    if constexpr (LM) return __builtin_bit_cast(float, keys[i]);
+    else return b.tot[i];
+  };
+  if (tid < nb) {
+    const uint32_t kj = sortable(final_value(tid));
+    const int lj = b.len[tid];
+    int rank = 0;
+    for (int i = 0; i < nb; ++i) {
+      const uint32_t ki = sortable(final_value(i));
+      const int li = b.len[i];
+      rank += ki > kj || (ki == kj && (li < lj || (li == lj && i < tid)));
+    }
+    path[rank] = tid;
+  }
+  __syncthreads();
+  for (int n = 0; n < top_paths; ++n) {
+    const int j = path[n];
+    const int L = j >= 0 ? min(b.len[j], Tn) : 0;
+    int32_t* out = hyp + (size_t)n * T + r0;
+    for (int f = L + tid; f < Tn; f += kBeamThreads) out[f] = -1;
+    if (tid == 0) {
+      hyp_len[(size_t)n * U + u] = L;
+      const bool alive = j >= 0 && b.tot[j] > -1e29f;
+      score[(size_t)n * U + u] = alive ? (float)(off + (double)final_value(j)) : -INFINITY;
+      if (am_score) am_score[(size_t)n * U + u] = alive ? (float)(off + (double)b.tot[j]) : -INFINITY;
+    }
+  }
+  if (tid < top_paths && path[tid] >= 0) {  // back-trace through the parent links, labels land in forward order
+    const int j = path[tid];
+    int32_t* out = hyp + (size_t)tid * T + r0;
+    uint32_t node = (uint32_t)b.node[j];
+    for (int pos = min(b.len[j], Tn) - 1; pos >= 0 && node < cap; --pos) {
+      const unsigned long long nk = __hip_atomic_load(&tab[node], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[pos] = (int32_t)(nk & 0xffffull);
+      node = (uint32_t)(nk >> 16);
+    }
+  }
+}
+
 // ---- forced alignment (the Viterbi path of the CTC lattice; the contract is stated in ctc.h) ----
 
 // one wave per row: lse[t] = log-sum-exp of logits row t (what the alignment score subtracts per frame)
@@ -1123,6 +1546,44 @@ void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, c
   else
     hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
                        hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, (float*)nullptr);
+}
+
+size_t ctc_beam_topk_scratch_words(int T) { return (size_t)(T > 0 ? T : 0) * kCtcTopkRowWords; }
+
+const char* ctc_beam_topk_limits(int O, int T, int U, int W, int top_paths, int label_topk) {
+  if (W < 1 || W > kCtcBeamMaxWidth) return "beam_width outside [1, 128]";
+  if (O < 2 || O > kCtcTopkMaxClasses) return "output_dim outside [2, 65536]";
+  if (label_topk < 1 || label_topk > kCtcTopkMaxLabels) return "label_topk outside [1, 63]";
+  if (top_paths < 1 || top_paths > W) return "top_paths outside [1, beam_width]";
+  if (T < 0 || T > kCtcBeamMaxFrames) return "more than 524286 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  return nullptr;
+}
+
+size_t ctc_lm_entries(int O, int order) {
+  size_t n = 1;
+  for (int i = 0; i < order && n <= kCtcLmMaxEntries; ++i) n *= (size_t)O;
+  return n;
+}
+
+void ctc_beam_topk_rows(hipStream_t s, const float* logits, int ld, int O, int T, int label_topk, uint32_t* pre) {
+  if (T <= 0) return;
+  hipLaunchKernelGGL(ctc_row_topk_kernel, dim3((unsigned)T), dim3(64), 0, s, logits, ld, O, min(label_topk, O - 1), pre);
+}
+
+void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
+                          int top_paths, int label_topk, unsigned long long* trie, const uint32_t* pre, int32_t* hyp,
+                          int32_t* hyp_len, float* score, const CtcLm* lm, float* am_score) {
+  if (U <= 0) return;
+  const int K = min(label_topk, O - 1);
+  (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
+  if (lm)
+    hipLaunchKernelGGL(ctc_beam_topk_kernel<true>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
+                       top_paths, trie, hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus,
+                       (int)lm->eos, am_score);
+  else
+    hipLaunchKernelGGL(ctc_beam_topk_kernel<false>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
+                       top_paths, trie, hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, am_score);
 }
 
 // scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]

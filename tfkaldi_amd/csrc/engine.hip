@@ -66,14 +66,16 @@ struct LayerLayout {
 
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
-  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM, KF_COUNT
+  KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
+  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
                                      "act_forward",             "hidden_backward",  "colsum",          "softmax_xent",
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
                                      "misc",                    "ctc_best_path",    "edit_distance",
-                                     "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm"};
+                                     "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm",
+                                     "ctc_beam_search_topk",    "ctc_topk_rows"};
 
 struct ProfRec {
   int family;
@@ -188,6 +190,9 @@ struct tfk_engine {
   // prefix beam search (tfk_ctc_beam): the trie table of ctc_beam_search
   unsigned long long* ctc_trie = nullptr;
   size_t ctc_cap_trie = 0;
+  // pruned beam search (tfk_ctc_beam_topk): the rows of ctc_beam_topk_rows
+  uint32_t* ctc_pre = nullptr;
+  size_t ctc_cap_pre = 0;
   // the character n-gram table of tfk_ctc_lm_set, [O^(order - 1), O]; order 0: no model
   float* ctc_lm = nullptr;
   int ctc_lm_order = 0;
@@ -1690,8 +1695,10 @@ int train_or_eval(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, 
 int decode_args(const tfk_engine* e, const char* who, const float* X, int T, int flags, const RawSpec* raw, int own = 0) {
   if (!e) return fail(-1, "engine is NULL");
   if (flags & ~own & ~(raw ? TFK_RAW_DEVICE : 0))
-    return own ? fail(-1, "flags %d: %s takes 0 or TFK_CTC_LM_EOS, %s_raw those and TFK_RAW_DEVICE", flags, who, who)
-               : fail(-1, "flags %d: %s takes 0, %s_raw 0 or TFK_RAW_DEVICE", flags, who, who);
+    return (own & TFK_CTC_LM) ? fail(-1, "flags %d: %s takes TFK_CTC_LM and TFK_CTC_LM_EOS, %s_raw those and TFK_RAW_DEVICE", flags,
+                                     who, who)
+           : own ? fail(-1, "flags %d: %s takes 0 or TFK_CTC_LM_EOS, %s_raw those and TFK_RAW_DEVICE", flags, who, who)
+                 : fail(-1, "flags %d: %s takes 0, %s_raw 0 or TFK_RAW_DEVICE", flags, who, who);
   if (T <= 0) return fail(-1, "empty batch (T = %d)", T);
   if (!X) return fail(-1, "X is NULL");
   return 0;
@@ -1847,7 +1854,8 @@ int tfk_destroy(tfk_engine* e) {
   if (e->ws_splitk) hipFree(e->ws_splitk);
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
-                  (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm})
+                  (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
+                  (void*)e->ctc_pre})
     if (p) hipFree(p);
   if (e->h_dec) hipHostFree(e->h_dec);
   for (hipEvent_t ev : e->post_ev) hipEventDestroy(ev);
@@ -2449,6 +2457,8 @@ int tfk_ctc_greedy_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T
 // of the best path: evaluation-mode forward as tfk_posteriors, then ctc_beam_search (and label_edit_distance on plane 0)
 // on the logits in HBM; top_paths * (T + 2U) + U words go back to the host.  lm (tfk_ctc_beam_lm): rank by the engine's
 // n-gram table with that weight and label bonus; top_paths * U acoustic scores more come back, behind the distances.
+// label_topk > 0 (tfk_ctc_beam_topk): the search with per-frame label pruning, any output_dim; the model ranks under
+// TFK_CTC_LM, and the acoustic scores come back either way.
 struct BeamLmArgs {
   float weight, bonus;
   float* am_score;  // host, may be NULL
@@ -2456,35 +2466,64 @@ struct BeamLmArgs {
 static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
                          int32_t beam_width, int32_t top_paths, const int32_t* ref_labels, const int32_t* ref_len,
                          int32_t* hyp, int32_t* hyp_len, float* score, int32_t* edits, int flags, const RawSpec* raw,
-                         const BeamLmArgs* lm = nullptr) {
-  CHK(decode_args(e, lm ? "tfk_ctc_beam_lm" : "tfk_ctc_beam", X, T, flags, raw, lm ? TFK_CTC_LM_EOS : 0));
-  if (lm && !e->ctc_lm_order) return fail(-1, "tfk_ctc_beam_lm: no language model is set (tfk_ctc_lm_set)");
+                         const BeamLmArgs* lm = nullptr, int label_topk = 0) {
+  const BeamLmArgs* const args = lm;  // (topk: always given; lm below = whether the model ranks)
+  const char* who = label_topk ? "tfk_ctc_beam_topk" : lm ? "tfk_ctc_beam_lm" : "tfk_ctc_beam";
+  CHK(decode_args(e, who, X, T, flags, raw, label_topk ? TFK_CTC_LM | TFK_CTC_LM_EOS : lm ? TFK_CTC_LM_EOS : 0));
+  if (label_topk) {
+    if ((flags & TFK_CTC_LM_EOS) && !(flags & TFK_CTC_LM))
+      return fail(-1, "tfk_ctc_beam_topk: TFK_CTC_LM_EOS without TFK_CTC_LM (the end term is the model's)");
+    if (!(flags & TFK_CTC_LM)) lm = nullptr;
+    flags &= ~TFK_CTC_LM;
+  }
+  if (lm && !e->ctc_lm_order) return fail(-1, "%s: no language model is set (tfk_ctc_lm_set)", who);
   const CtcLm model = {e->ctc_lm, e->ctc_lm_order, lm ? lm->weight : 0.f, lm ? lm->bonus : 0.f,
                        (flags & TFK_CTC_LM_EOS) != 0};
   flags &= ~TFK_CTC_LM_EOS;
   if (!hyp || !hyp_len || !score) return fail(-1, "hyp / hyp_len / score is NULL");
   if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
-  if (const char* why = ctc_beam_limits(e->O, T, U, beam_width, top_paths))
+  if (label_topk) {
+    if (const char* why = ctc_beam_topk_limits(e->O, T, U, beam_width, top_paths, label_topk))
+      return fail(-1, "CTC beam search (beam_width %d, top_paths %d, label_topk %d, output_dim %d, T %d): %s", beam_width,
+                  top_paths, label_topk, e->O, T, why);
+  } else if (const char* why = ctc_beam_limits(e->O, T, U, beam_width, top_paths)) {
     return fail(-1, "CTC beam search (beam_width %d, top_paths %d, output_dim %d, T %d): %s", beam_width, top_paths, e->O, T,
                 why);
+  }
+  const bool am = lm || label_topk;  // the acoustic scores come back
   const size_t P = (size_t)top_paths;
-  // [hypotheses | lengths | scores | distances | acoustic scores (model only)]
-  const size_t back = P * (size_t)T + 2 * P * (size_t)U + (size_t)U, am_words = lm ? P * (size_t)U : 0;
+  // [hypotheses | lengths | scores | distances | acoustic scores (with a model, and from the pruned search)]
+  const size_t back = P * (size_t)T + 2 * P * (size_t)U + (size_t)U, am_words = am ? P * (size_t)U : 0;
   const size_t trie_words = ctc_beam_scratch_words(T, U, beam_width);
   int max_ref = 0;
   // (with a model the acoustic scores lie behind the U distance words, so those travel back even when edits == NULL and
   // nothing has written them; the host does not read them then)
   CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, ref_labels, ref_len}, edits != nullptr, back + am_words, 0,
-                  lm ? back + am_words : (edits ? back : back - U), &max_ref,
-                  [&] { return grow(e, &e->ctc_trie, &e->ctc_cap_trie, trie_words); }, [&] {
+                  am ? back + am_words : (edits ? back : back - U), &max_ref,
+                  [&] {
+                    if (label_topk) CHK(grow(e, &e->ctc_pre, &e->ctc_cap_pre, ctc_beam_topk_scratch_words(T)));
+                    return grow(e, &e->ctc_trie, &e->ctc_cap_trie, trie_words);
+                  },
+                  [&] {
     int32_t* d_hyp = e->ctc_dec;
     int32_t* d_len = d_hyp + P * T;
+    if (label_topk) {  // the row pre-pass: one read of the logits, kCtcTopkRowWords words out per frame
+      ProfScope ps(e, KF_CTC_TOPK_ROWS, 0, 4.0 * T * e->O + 4.0 * T * kCtcTopkRowWords);
+      ctc_beam_topk_rows(e->stream, e->logits, e->ldO, e->O, T, label_topk, e->ctc_pre);
+    }
     {
       // (8 bytes per trie word: the memset, the call's largest traffic)
-      ProfScope ps(e, lm ? KF_CTC_BEAM_LM : KF_CTC_BEAM, 0, 4.0 * T * e->O + 4.0 * P * T + 8.0 * trie_words);
-      ctc_beam_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, e->ctc_trie, d_hyp, d_len,
-                      reinterpret_cast<float*>(d_len + P * U), lm ? &model : nullptr,
-                      lm ? reinterpret_cast<float*>(d_len + 2 * P * U + U) : nullptr);
+      ProfScope ps(e, label_topk ? KF_CTC_BEAM_TOPK : lm ? KF_CTC_BEAM_LM : KF_CTC_BEAM, 0,
+                   (label_topk ? 4.0 * T * kCtcTopkRowWords + 4.0 * T * beam_width : 4.0 * T * e->O) + 4.0 * P * T +
+                       8.0 * trie_words);
+      float* d_score = reinterpret_cast<float*>(d_len + P * U);
+      float* d_am = am ? reinterpret_cast<float*>(d_len + 2 * P * U + U) : nullptr;
+      if (label_topk)
+        ctc_beam_topk_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, label_topk,
+                             e->ctc_trie, e->ctc_pre, d_hyp, d_len, d_score, lm ? &model : nullptr, d_am);
+      else
+        ctc_beam_search(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, beam_width, top_paths, e->ctc_trie, d_hyp, d_len,
+                        d_score, lm ? &model : nullptr, d_am);
     }
     if (edits) {
       ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * T + 4.0 * U);
@@ -2495,7 +2534,7 @@ static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, 
   memcpy(hyp_len, e->h_dec + P * T, P * U * sizeof(int32_t));
   memcpy(score, e->h_dec + P * T + P * U, P * U * sizeof(float));
   if (edits) memcpy(edits, e->h_dec + P * T + 2 * P * U, (size_t)U * sizeof(int32_t));
-  if (lm && lm->am_score) memcpy(lm->am_score, e->h_dec + back, P * U * sizeof(float));
+  if (am && args->am_score) memcpy(args->am_score, e->h_dec + back, P * U * sizeof(float));
   return 0;
 }
 
@@ -2504,10 +2543,13 @@ int tfk_ctc_lm_set(tfk_engine* e, const float* table, int32_t order) {
   HIPCHK(hipSetDevice(e->cfg.device));
   if (table) {
     if (order < 1 || order > kCtcLmMaxOrder) return fail(-1, "tfk_ctc_lm_set: order %d outside [1, %d]", order, kCtcLmMaxOrder);
-    if (e->O < 2 || e->O > kCtcBeamMaxClasses)
-      return fail(-1, "tfk_ctc_lm_set: output_dim %d outside [2, %d] (the beam search's limit)", e->O, kCtcBeamMaxClasses);
+    if (e->O < 2 || e->O > kCtcTopkMaxClasses)
+      return fail(-1, "tfk_ctc_lm_set: output_dim %d outside [2, %d] (the beam search's limit)", e->O, kCtcTopkMaxClasses);
+    if (ctc_lm_entries(e->O, order) > kCtcLmMaxEntries)
+      return fail(-1, "tfk_ctc_lm_set: a table of order %d over %d outputs has more than %zu entries", order, e->O,
+                  kCtcLmMaxEntries);
   }
-  const size_t n = table ? (size_t)ctc_lm_contexts(e->O, order) * (size_t)e->O : 0;
+  const size_t n = table ? ctc_lm_entries(e->O, order) : 0;
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(table[i])) return fail(-1, "tfk_ctc_lm_set: entry %zu of the table is not finite", i);
   HIPCHK(hipStreamSynchronize(e->stream));  // a search may still be reading the model this one replaces
@@ -2554,24 +2596,84 @@ int tfk_ctc_beam_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
   return ctc_beam_impl(e, raw, ldraw, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
                        flags, &r);
 }
+int tfk_ctc_beam_topk(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t beam_width, int32_t top_paths, int32_t label_topk, float lm_weight, float label_bonus,
+                      const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp, int32_t* hyp_len, float* score,
+                      float* am_score, int32_t* edits, int flags) {
+  if (label_topk < 1) return fail(-1, "tfk_ctc_beam_topk: label_topk outside [1, 63]");
+  const BeamLmArgs lm = {lm_weight, label_bonus, am_score};
+  return ctc_beam_impl(e, X, ldx, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
+                       flags, nullptr, &lm, label_topk);
+}
+int tfk_ctc_beam_topk_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                          int32_t context_width, const float* cmvn, int32_t beam_width, int32_t top_paths, int32_t label_topk,
+                          float lm_weight, float label_bonus, const int32_t* ref_labels, const int32_t* ref_len, int32_t* hyp,
+                          int32_t* hyp_len, float* score, float* am_score, int32_t* edits, int flags) {
+  if (label_topk < 1) return fail(-1, "tfk_ctc_beam_topk_raw: label_topk outside [1, 63]");
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  const BeamLmArgs lm = {lm_weight, label_bonus, am_score};
+  return ctc_beam_impl(e, raw, ldraw, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
+                       flags, &r, &lm, label_topk);
+}
 static int ctc_beam_logits_impl(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
                                 int32_t U, int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len,
-                                float* score, const CtcLm* lm, float* am_score) {
-  if (const char* why = ctc_beam_limits(O, T, U, beam_width, top_paths))
+                                float* score, const CtcLm* lm, float* am_score, int label_topk = 0) {
+  if (label_topk) {
+    if (const char* why = ctc_beam_topk_limits(O, T, U, beam_width, top_paths, label_topk))
+      return fail(-1, "CTC beam search (beam_width %d, top_paths %d, label_topk %d, O %d, T %d, U %d): %s", beam_width,
+                  top_paths, label_topk, O, T, U, why);
+  } else if (const char* why = ctc_beam_limits(O, T, U, beam_width, top_paths)) {
     return fail(-1, "CTC beam search (beam_width %d, top_paths %d, O %d, T %d, U %d): %s", beam_width, top_paths, O, T, U, why);
+  }
   if (U == 0) return 0;
   if (!seg || !hyp_len || !score || (T > 0 && (!logits || !hyp))) return fail(-1, "logits / seg / hyp / hyp_len / score is NULL");
   if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
   unsigned long long* trie = nullptr;  // the call's own scratch, released in stream order
   HIPCHK(hipMallocAsync((void**)&trie, ctc_beam_scratch_words(T, U, beam_width) * sizeof(unsigned long long),
                         (hipStream_t)stream));
-  ctc_beam_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, trie, hyp, hyp_len, score, lm,
-                  am_score);
+  uint32_t* pre = nullptr;
+  if (label_topk && T > 0) {
+    const hipError_t got = hipMallocAsync((void**)&pre, ctc_beam_topk_scratch_words(T) * sizeof(uint32_t), (hipStream_t)stream);
+    if (got != hipSuccess) {
+      (void)hipFreeAsync(trie, (hipStream_t)stream);
+      HIPCHK(got);
+    }
+  }
+  if (label_topk) ctc_beam_topk_rows((hipStream_t)stream, logits, (int)ld, O, T, label_topk, pre);
+  if (label_topk)
+    ctc_beam_topk_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, label_topk, trie, pre, hyp,
+                         hyp_len, score, lm, am_score);
+  else
+    ctc_beam_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, trie, hyp, hyp_len, score, lm,
+                    am_score);
   const hipError_t launched = hipGetLastError();
   const hipError_t freed = hipFreeAsync(trie, (hipStream_t)stream);  // also when the launch failed
+  const hipError_t freed_pre = pre ? hipFreeAsync(pre, (hipStream_t)stream) : hipSuccess;
   HIPCHK(launched);
   HIPCHK(freed);
+  HIPCHK(freed_pre);
   return 0;
+}
+int tfk_ctc_beam_topk_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                             int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* lm_dev, int32_t order,
+                             float lm_weight, float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score,
+                             float* am_score) {
+  if (label_topk < 1) return fail(-1, "tfk_ctc_beam_topk_logits: label_topk outside [1, 63]");
+  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "tfk_ctc_beam_topk_logits: flags %d, it takes 0 or TFK_CTC_LM_EOS", flags);
+  if (!lm_dev) {
+    if (flags) return fail(-1, "tfk_ctc_beam_topk_logits: TFK_CTC_LM_EOS without a table");
+    return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, nullptr, am_score,
+                                label_topk);
+  }
+  if (order < 1 || order > kCtcLmMaxOrder)
+    return fail(-1, "tfk_ctc_beam_topk_logits: order %d outside [1, %d]", order, kCtcLmMaxOrder);
+  if (O >= 2 && O <= kCtcTopkMaxClasses && ctc_lm_entries(O, order) > kCtcLmMaxEntries)
+    return fail(-1, "tfk_ctc_beam_topk_logits: a table of order %d over %d outputs has more than %zu entries", order, O,
+                kCtcLmMaxEntries);
+  const CtcLm lm = {lm_dev, order, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0};
+  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score,
+                              label_topk);
 }
 int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                         int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score) {

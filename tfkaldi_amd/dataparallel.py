@@ -161,16 +161,21 @@ def _eval_accumulate_all(engine, mine):
         _eval_accumulate(engine, mb)
 
 
-def _label_errors(engine, mb, beam_width=None, lm=None):
+def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None):
     """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
-    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM)"""
+    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM; label_topk:
+    pruned to the frame's label_topk most probable labels)"""
     if lm is not None and beam_width is None:
         raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
+    if label_topk is not None and beam_width is None:
+        raise ValueError("label_topk prunes a beam search: give beam_width with label_topk")
     if not isinstance(mb, CtcMicroBatch):
         raise TypeError("label errors need CTC micro-batches (label sequences), not %s" % type(mb).__name__)
     entry, kw = ("ctc_greedy", {}) if beam_width is None else ("ctc_beam", {"beam_width": beam_width})
     if lm is not None:
         entry, kw = "ctc_beam_lm", dict(kw, lm=lm)
+    if label_topk is not None:  # (forwarded only when given: an engine without the keyword keeps serving the other calls)
+        kw = dict(kw, label_topk=label_topk)
     if mb.context_width is not None:  # unspliced frames: CMVN + splice on the device
         entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
     edits = getattr(engine, entry)(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens, **kw)[-1]
@@ -1290,10 +1295,11 @@ class DataParallel(object):
         start, end = partition(len(microbatches), self.world)[self.rank]
         return self.eval_own(engine, microbatches[start:end])
 
-    def label_errors(self, engine, microbatches, beam_width=None, lm=None):
+    def label_errors(self, engine, microbatches, beam_width=None, lm=None, label_topk=None):
         """(edits, reference labels): label errors summed over the CTC micro-batches of the WHOLE batch (identical on every
         rank) under best-path decoding (beam_width None) or the best path of a prefix beam search of that width (lm: an
-        NgramLM the search ranks its prefixes with; every rank passes the same one).
+        NgramLM the search ranks its prefixes with; label_topk: an int prunes the search to the frame's label_topk most
+        probable labels, for models of any output size; every rank passes the same ones).
         COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and the two counts
         are SUM all-reduced as one int64 tensor over self.group (on the device for an NCCL / RCCL group)."""
         mine = microbatches
@@ -1302,7 +1308,7 @@ class DataParallel(object):
             mine = microbatches[start:end]
         edits = labels = 0
         for mb in mine:
-            e, n = _label_errors(engine, mb, beam_width, lm)
+            e, n = _label_errors(engine, mb, beam_width, lm, label_topk)
             edits += e
             labels += n
         if not self.enabled:

@@ -400,7 +400,7 @@ class Engine(object):
         return self._greedy(self.lib.tfk_ctc_greedy_raw, raw, utt_lens, labels, label_lens, raw=(context_width, cmvn))
 
     # ---- CTC prefix beam search: tf.nn.ctc_beam_search_decoder(merge_repeated=False), N best with log-probabilities ----
-    def _beam(self, fn, frames, utt_lens, beam_width, top_paths, labels, label_lens, raw=None):
+    def _beam(self, fn, frames, utt_lens, beam_width, top_paths, labels, label_lens, raw=None, label_topk=None):
         beam_width, top_paths = int(beam_width), int(top_paths)
         if not 1 <= top_paths <= beam_width:
             raise ValueError("top_paths %d outside [1, beam_width = %d]" % (top_paths, beam_width))
@@ -416,22 +416,36 @@ class Engine(object):
             starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
             hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
             return hyps, np.ascontiguousarray(score.T), edits
+        if label_topk is not None:  # the pruned entry without a model: its acoustic-score output is not asked for (NULL)
+            def outputs_topk(rows, U):
+                hyp, hyp_len, score, edits = outputs(rows, U)
+                return hyp, hyp_len, score, None, edits
+
+            def result_topk(lens, hyp, hyp_len, score, _, edits):
+                return result(lens, hyp, hyp_len, score, edits)
+            fn = self.lib.tfk_ctc_beam_topk if raw is None else self.lib.tfk_ctc_beam_topk_raw
+            return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs_topk, result_topk,
+                                (beam_width, top_paths, int(label_topk), c_float(0.0), c_float(0.0)), raw)
         return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, (beam_width, top_paths), raw)
 
-    def ctc_beam(self, X, utt_lens, beam_width=100, top_paths=1, labels=None, label_lens=None):
+    def ctc_beam(self, X, utt_lens, beam_width=100, top_paths=1, labels=None, label_lens=None, label_topk=None):
         """Prefix beam search over the utterances X [sum(utt_lens), F] (tfk_ctc_beam; the algorithm is stated in
         include/tfkaldi_hip.h): the `top_paths` most probable label sequences of every utterance among those that stay in a
         beam of `beam_width`, best first, with their natural-log probabilities.  Returns (hyps, scores, edits): hyps[u][n]
         int32 label arrays, scores float32 [U, top_paths] (-inf where fewer prefixes survived), edits int32 [U] = Levenshtein
-        distance of the BEST path to the reference (labels back to back, label_lens per utterance) or None."""
-        return self._beam(self.lib.tfk_ctc_beam, X, utt_lens, beam_width, top_paths, labels, label_lens)
+        distance of the BEST path to the reference (labels back to back, label_lens per utterance) or None.
+        label_topk: None is that search (at most 64 outputs); an int in [1, 63] is the search with per-frame label pruning
+        (tfk_ctc_beam_topk), where only the frame's label_topk most probable labels may start a new label: any output_dim up
+        to 65536, and less work per frame below 64."""
+        return self._beam(self.lib.tfk_ctc_beam, X, utt_lens, beam_width, top_paths, labels, label_lens,
+                          label_topk=label_topk)
 
     def ctc_beam_raw(self, raw, utt_lens, context_width, cmvn=None, beam_width=100, top_paths=1, labels=None,
-                     label_lens=None):
+                     label_lens=None, label_topk=None):
         """ctc_beam on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
         return self._beam(self.lib.tfk_ctc_beam_raw, raw, utt_lens, beam_width, top_paths, labels, label_lens,
-                          raw=(context_width, cmvn))
+                          raw=(context_width, cmvn), label_topk=label_topk)
 
     # ---- the same search ranked with a character n-gram language model (neuralNetworks/ctc_lm.NgramLM) ----
     def ctc_set_lm(self, lm):
@@ -449,7 +463,7 @@ class Engine(object):
         check(self.lib.tfk_ctc_lm_set(self._h, _ptr(lm.table), lm.order))
         self._lm_table = lm.table
 
-    def _beam_lm(self, fn, frames, utt_lens, lm, beam_width, top_paths, labels, label_lens, raw=None):
+    def _beam_lm(self, fn, frames, utt_lens, lm, beam_width, top_paths, labels, label_lens, raw=None, label_topk=None):
         beam_width, top_paths = int(beam_width), int(top_paths)
         if not 1 <= top_paths <= beam_width:
             raise ValueError("top_paths %d outside [1, beam_width = %d]" % (top_paths, beam_width))
@@ -468,24 +482,30 @@ class Engine(object):
             starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
             hyps = [[hyp[n, s:s + hyp_len[n, u]].copy() for n in range(top_paths)] for u, s in enumerate(starts)]
             return hyps, np.ascontiguousarray(score.T), np.ascontiguousarray(am.T), edits
+        own = _lib.CTC_LM_EOS if lm.end_of_sequence else 0
+        if label_topk is not None:  # the pruned entry, ranked by the model
+            fn = self.lib.tfk_ctc_beam_topk if raw is None else self.lib.tfk_ctc_beam_topk_raw
+            return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result,
+                                (beam_width, top_paths, int(label_topk), c_float(lm.weight), c_float(lm.label_bonus)), raw,
+                                own | _lib.CTC_LM)
         return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result,
-                            (beam_width, top_paths, c_float(lm.weight), c_float(lm.label_bonus)), raw,
-                            _lib.CTC_LM_EOS if lm.end_of_sequence else 0)
+                            (beam_width, top_paths, c_float(lm.weight), c_float(lm.label_bonus)), raw, own)
 
-    def ctc_beam_lm(self, X, utt_lens, lm, beam_width=100, top_paths=1, labels=None, label_lens=None):
+    def ctc_beam_lm(self, X, utt_lens, lm, beam_width=100, top_paths=1, labels=None, label_lens=None, label_topk=None):
         """ctc_beam with prefixes ranked by acoustic score + language-model score (tfk_ctc_beam_lm; the search is stated in
         include/tfkaldi_hip.h).  lm: an NgramLM over this model's labels -- its table is set on the engine if it is not
         already, its weight, label bonus and end-of-sequence switch go with the call.  Returns (hyps, scores, am_scores,
         edits): as ctc_beam, scores the COMBINED values the paths are ordered by, am_scores float32 [U, top_paths] their
-        acoustic parts; edits of the best path by combined score."""
-        return self._beam_lm(self.lib.tfk_ctc_beam_lm, X, utt_lens, lm, beam_width, top_paths, labels, label_lens)
+        acoustic parts; edits of the best path by combined score.  label_topk: as ctc_beam."""
+        return self._beam_lm(self.lib.tfk_ctc_beam_lm, X, utt_lens, lm, beam_width, top_paths, labels, label_lens,
+                             label_topk=label_topk)
 
     def ctc_beam_lm_raw(self, raw, utt_lens, context_width, lm, cmvn=None, beam_width=100, top_paths=1, labels=None,
-                        label_lens=None):
+                        label_lens=None, label_topk=None):
         """ctc_beam_lm on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
         return self._beam_lm(self.lib.tfk_ctc_beam_lm_raw, raw, utt_lens, lm, beam_width, top_paths, labels, label_lens,
-                             raw=(context_width, cmvn))
+                             raw=(context_width, cmvn), label_topk=label_topk)
 
     # ---- CTC forced alignment: the Viterbi path of the known label sequence, per frame the label POSITION it emits ----
     def _align(self, fn, frames, utt_lens, labels, label_lens, raw=None):

@@ -3,6 +3,7 @@ and the search are stated in include/tfkaldi_hip.h): a DENSE table over the labe
 import numpy as np
 
 MAX_ORDER = 4
+MAX_ENTRIES = 1 << 26  # of a table on the device (tfk_ctc_lm_set): 256 MB
 
 
 class NgramLM(object):
@@ -34,7 +35,10 @@ class NgramLM(object):
         return self.num_classes - 1
 
     def check(self, num_classes):
-        """raise unless the table fits a model of num_classes outputs (labels + blank)"""
+        """raise unless the table fits a model of num_classes outputs (labels + blank) and the device's size limit"""
+        if self.num_classes ** self.order > MAX_ENTRIES:
+            raise ValueError("an order-%d table over %d outputs has %d entries, more than the device takes (%d)"
+                             % (self.order, self.num_classes, self.num_classes ** self.order, MAX_ENTRIES))
         if self.num_classes != int(num_classes):
             raise ValueError("the language model has %d labels + blank, the acoustic model %d outputs"
                              % (self.num_labels, num_classes))

@@ -116,23 +116,29 @@ class Decoder(object):
             return []
         return self._ctc("ctc_greedy", utterances)[0]
 
-    def ctc_beam_search(self, utterances, beam_width=100, top_paths=1):
+    def ctc_beam_search(self, utterances, beam_width=100, top_paths=1, label_topk=None):
         """Prefix beam search decoding of a CTC model (tf.nn.ctc_beam_search_decoder with merge_repeated=False, its default
         beam_width): every utterance in ONE forward pass, the search on the device (tfk_ctc_beam).  Returns (hyps, scores):
         hyps[u][n] the n-th best int32 label array of utterance u, scores float32 [U, top_paths] their natural-log
-        probabilities.  All `Unspliced` -> device-side splice, as decode_batch."""
+        probabilities.  All `Unspliced` -> device-side splice, as decode_batch.  label_topk: an int prunes the search to the
+        frame's label_topk (1 to 63) most probable labels (tfk_ctc_beam_topk) -- the way to search a model of more than 64
+        outputs, and a cheaper search below that; None is the unpruned search."""
         if len(utterances) == 0:
             return [], np.zeros((0, top_paths), dtype=np.float32)
-        return self._ctc("ctc_beam", utterances, beam_width=beam_width, top_paths=top_paths)[:2]
+        kw = {} if label_topk is None else {"label_topk": label_topk}
+        return self._ctc("ctc_beam", utterances, beam_width=beam_width, top_paths=top_paths, **kw)[:2]
 
-    def ctc_beam_search_lm(self, utterances, lm, beam_width=100, top_paths=1):
+    def ctc_beam_search_lm(self, utterances, lm, beam_width=100, top_paths=1, label_topk=None):
         """ctc_beam_search with a character n-gram language model (ctc_lm.NgramLM; tfk_ctc_beam_lm): prefixes are ranked by
         acoustic score + lm.weight * model log-probability + lm.label_bonus per label.  Returns (hyps, scores, am_scores):
-        as ctc_beam_search, scores the combined values, am_scores float32 [U, top_paths] their acoustic parts."""
+        as ctc_beam_search, scores the combined values, am_scores float32 [U, top_paths] their acoustic parts.  label_topk:
+        as ctc_beam_search."""
         if len(utterances) == 0:
             return [], np.zeros((0, top_paths), dtype=np.float32), np.zeros((0, top_paths), dtype=np.float32)
         lens, raw, frames, context_width, cmvn = self._batch(utterances)
         kw = dict(beam_width=beam_width, top_paths=top_paths)
+        if label_topk is not None:
+            kw["label_topk"] = label_topk
         if raw:
             return self.engine.ctc_beam_lm_raw(frames, lens, context_width, lm, cmvn=cmvn, **kw)[:3]
         return self.engine.ctc_beam_lm(frames, lens, lm, **kw)[:3]

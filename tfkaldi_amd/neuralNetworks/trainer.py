@@ -362,7 +362,7 @@ class CTCTrainer(Trainer):
     def compute_loss(self, targets, logits, logit_seq_length, target_seq_length):
         return "ctc"
 
-    def label_errors(self, inputs, targets, beam_width=None, lm=None):
+    def label_errors(self, inputs, targets, beam_width=None, lm=None, label_topk=None):
         """Label errors of the batch under best-path decoding -- tf.nn.ctc_greedy_decoder(merge_repeated=True) followed by
         tf.edit_distance(normalize=False), the reference framework's standard CTC evaluation -- in evaluation mode, on the
         device (tfk_ctc_greedy).  Returns (sum of the Levenshtein distances, sum of the reference lengths) over the batch as
@@ -370,10 +370,16 @@ class CTCTrainer(Trainer):
         no data (as evaluate).  COLLECTIVE under data parallelism: the micro-batches are dealt to the ranks as in evaluate
         and the two counts summed over them.  beam_width: an int decodes by prefix beam search of that width instead
         (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path.  lm: a ctc_lm.NgramLM ranks
-        the beam's prefixes by acoustic + language-model score (tfk_ctc_beam_lm); it needs a beam_width."""
+        the beam's prefixes by acoustic + language-model score (tfk_ctc_beam_lm); it needs a beam_width.  label_topk: an int
+        prunes the search to the frame's label_topk most probable labels (tfk_ctc_beam_topk), which is what lets a model of
+        more than 64 outputs be searched; it needs a beam_width too."""
         if lm is not None and beam_width is None:
             raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
+        if label_topk is not None and beam_width is None:
+            raise ValueError("label_topk prunes a beam search: give beam_width with label_topk")
         if inputs is None or targets is None:
             return None
         kw = {} if lm is None else {"lm": lm}
+        if label_topk is not None:
+            kw["label_topk"] = label_topk
         return self.dp.label_errors(self.engine, self._microbatches(inputs, targets), beam_width=beam_width, **kw)

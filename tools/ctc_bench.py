@@ -12,8 +12,14 @@ language model (tfk_ctc_beam_lm; NgramLM.from_label_sequences over the reference
 ratio to the acoustic kernel's, label error rate greedy / beam / beam + model, |device - float64| of one best combined
 score; then the align leg: forced alignment of every utterance to its
 reference on the device (tfk_ctc_align) -- ms per call, the profiler's time of the ctc_align kernels and that time per frame
-step, and the host alternative (the float64 numpy restatement of the tests on the same logits, all utterances).
-`--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone."""
+step, and the host alternative (the float64 numpy restatement of the tests on the same logits, all utterances); then the
+pruned leg: the search with per-frame label pruning (tfk_ctc_beam_topk) at label_topk = 8 and 16 beside the unpruned search on
+the same workload, and at label_topk = 63 (nothing pruned at 36 outputs: the pruned kernel against the existing one on the
+same logits) -- the profiler's time of the ctc_beam_search_topk kernel and of the row pre-pass on its own, label error rates;
+and the wide leg: a model of 1000 outputs (which the unpruned search refuses) at label_topk = 1 .. 63 and W = 10, 100, the
+kernel's time per frame step against K + 1.
+`--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
+pruned and the wide leg alone."""
 import os
 import sys
 import time
@@ -48,10 +54,20 @@ def main():
         align_leg(eng, X, utt, labels, np.asarray(lab), "random output weights")
         eng.close()
         return
+    if "--topk-only" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        bias = np.zeros(O, np.float32)
+        bias[O - 1] = 2.0
+        eng.set(_lib.BIASES, eng.L, bias)
+        topk_leg(eng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
+        eng.close()
+        wide_leg(rng, X, utt, cfg)
+        return
     if "--decode-only" not in sys.argv:
         train_leg(eng, X, raw, utt, labels, lab, T)
     decode_leg(eng, X, utt, labels, lab, rng)
     eng.close()
+    wide_leg(rng, X, utt, cfg)
 
 
 def train_leg(eng, X, raw, utt, labels, lab, T):
@@ -150,6 +166,7 @@ def decode_leg(eng, X, utt, labels, lab, rng):
         beam = beam_leg(eng, X, utt, labels, lab, case, edits)
         lm_leg(eng, X, utt, labels, lab, case, edits, beam)
         align_leg(eng, X, utt, labels, lab, case)
+        topk_leg(eng, X, utt, labels, lab, case)
 
 
 def beam_leg(eng, X, utt, labels, lab, case, greedy_edits):
@@ -210,6 +227,75 @@ def lm_leg(eng, X, utt, labels, lab, case, greedy_edits, beam):
                   % (case, order, W, ms, kern, kern * 1e3 / max(utt), kern / beam[W][0], greedy_edits.sum() / np.sum(lab),
                      beam[W][1], edits.sum() / np.sum(lab), scores[0, 0], s64[0, 0], abs(scores[0, 0] - s64[0, 0]),
                      np.array_equal(hyps[0][0], h64[0][0])))
+
+
+def _kernel_ms(eng, call, names, K=10):
+    for _ in range(2):
+        call()
+    t0 = time.perf_counter()
+    for _ in range(K):
+        call()
+    ms = (time.perf_counter() - t0) / K * 1e3
+    eng.profile_begin()
+    for _ in range(K):
+        call()
+    stats = {s["name"]: s for s in eng.profile_end()}
+    return (ms,) + tuple(stats[n]["total_ms"] / K for n in names)
+
+
+def topk_leg(eng, X, utt, labels, lab, case):
+    """the existing workload (O <= 64): label_topk = 8, 16 and 63 (= unpruned) beside the existing kernel, with and without a
+    model, each with its label error rate"""
+    from tfkaldi_amd.neuralNetworks.ctc_lm import NgramLM
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    lm = NgramLM.from_label_sequences(refs, eng.O - 1, 3, weight=0.5, label_bonus=1.0)
+    for W in (1, 10, 100):
+        for model in (None, lm):
+            old = (lambda: eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab)) if model is None else (
+                lambda: eng.ctc_beam_lm(X, utt, model, beam_width=W, labels=labels, label_lens=lab))
+            ref = old()
+            ms, kern = _kernel_ms(eng, old, ("ctc_beam_search" if model is None else "ctc_beam_search_lm",))
+            what = "acoustic" if model is None else "order-3 model"
+            print("  pruned (%s) W=%3d %s: unpruned entry %8.3f ms/call, kernel %8.3f ms (%.2f us per frame step), label error "
+                  "rate %.3f" % (case, W, what, ms, kern, kern * 1e3 / max(utt), ref[-1].sum() / np.sum(lab)))
+            for K in (8, 16, 63):
+                new = (lambda: eng.ctc_beam(X, utt, beam_width=W, labels=labels, label_lens=lab, label_topk=K)) \
+                    if model is None else (lambda: eng.ctc_beam_lm(X, utt, model, beam_width=W, labels=labels, label_lens=lab,
+                                                                   label_topk=K))
+                got = new()
+                ms, kt, rows = _kernel_ms(eng, new, ("ctc_beam_search_topk", "ctc_topk_rows"))
+                same = all(np.array_equal(a[0], b[0]) for a, b in zip(got[0], ref[0]))
+                print("      label_topk %2d: %8.3f ms/call, ctc_beam_search_topk kernel %8.3f ms (%.2f us per frame step, %.3f x "
+                      "the unpruned kernel), row pre-pass %7.3f ms; label error rate %.3f; best paths equal the unpruned "
+                      "search's: %s%s"
+                      % (K, ms, kt, kt * 1e3 / max(utt), kt / kern, rows, got[-1].sum() / np.sum(lab), same,
+                         ", scores bit for bit: %s" % (got[1].tobytes() == ref[1].tobytes()) if K == 63 else ""))
+
+
+def wide_leg(rng, X, utt, cfg):
+    """a model of 1000 outputs on the same frames: the pruned search at label_topk = 1 .. 63"""
+    O = 1000
+    wide = _lib.make_config(cfg.input_dim, cfg.num_layers, cfg.num_units, O, nonlin="relu", batch_norm=True,
+                            max_frames=X.shape[0], num_steps=1000, compute_dtype=os.environ.get("TFK_QB_DTYPE", "float32"))
+    eng = Engine(wide)
+    eng.init_hidden_weights(rng)
+    eng.set(_lib.WEIGHTS, eng.L, 3.0 * rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+    bias = np.zeros(O, np.float32)
+    bias[O - 1] = 6.0
+    eng.set(_lib.BIASES, eng.L, bias)
+    hyps, _ = eng.ctc_greedy(X, utt)
+    print("wide (O = %d, %d utterances x %d frames): best-path hypothesis length mean %.1f"
+          % (O, len(utt), max(utt), np.mean([h.size for h in hyps])))
+    for W in (10, 100):
+        for K in (1, 4, 8, 16, 32, 63):
+            call = lambda: eng.ctc_beam(X, utt, beam_width=W, label_topk=K)
+            got = call()
+            ms, kt, rows = _kernel_ms(eng, call, ("ctc_beam_search_topk", "ctc_topk_rows"), K=5)
+            print("  wide W=%3d label_topk %2d: tfk_ctc_beam_topk %8.3f ms/call, kernel %8.3f ms = %.2f us per frame step "
+                  "(%.4f us per frame step and candidate column K + 1), row pre-pass %7.3f ms; mean length %.1f, mean best "
+                  "score %.3f" % (W, K, ms, kt, kt * 1e3 / max(utt), kt * 1e3 / max(utt) / (K + 1), rows,
+                                  np.mean([h[0].size for h in got[0]]), float(np.mean(got[1][:, 0]))))
+    eng.close()
 
 
 def align_leg(eng, X, utt, labels, lab, case):
