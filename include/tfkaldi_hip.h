@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 13
+#define TFK_ABI_VERSION 14
 
 typedef struct tfk_engine tfk_engine;
 
@@ -429,6 +429,41 @@ int tfk_ctc_align_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T,
  * (a value outside [0, O) is clamped). */
 int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                          const int32_t* labels, const int32_t* lab_off, int32_t* ali, float* score);
+/* (ABI 14) CTC N-best rescoring: the EXACT log-probability log p(labels | x) of label sequences the caller names -- the
+ * hypotheses of a beam search (whose own scores are lower bounds: only the alignments that survived pruning), or any other
+ * list -- and their label errors against a reference.  Eval-mode forward of the flat utterance-major frames X [T, ldx] of U
+ * utterances (utt_len[U], sum = T).  hyp_count[U] = the number of hypotheses of utterance u, >= 0 (0 is allowed anywhere);
+ * P = their sum, at most 2^20 = 1048576.  The (utterance, hypothesis) pairs are ordered by utterance, then by hypothesis;
+ * label_len[P] and labels lie back to back in pair order, values in [0, output_dim - 1), at most 511 per hypothesis; blank =
+ * the LAST class; pairs are independent.
+ * score[P]: the natural log of the sum, over ALL valid CTC alignments of the pair's label sequence on its utterance's frames,
+ * of prod_t softmax(z[t, :])[class(s_t)]: states and transitions are the loss's (n = 2S + 1 states blank, l_0, blank, ...,
+ * blank; start in state 0 or 1, end in n - 1 or n - 2; a step stays, advances by 1, or advances by 2 into a label that
+ * differs from the label two states back), so score = -(the utterance's CTC loss with those labels).  A pair too short for
+ * its labels: -inf.  A zero-frame utterance: 0 if S == 0, else -inf.  The emission is z[t, class] - logsumexp(z[t, :]) in
+ * fp32; the state values are fp32 relative to a running offset kept in double, and the result is rounded to float once.
+ * edits[P] (may be NULL; needs ref_len, and ref_labels where a reference is not empty -- per UTTERANCE, as tfk_ctc_greedy
+ * takes them, at most 511 labels each): the Levenshtein distance (unit costs) of every hypothesis to its utterance's reference.
+ * P == 0 is valid and writes nothing.  Errors (non-zero, tfk_last_error names the cause; the engine stays usable): NULL
+ * pointers, T <= 0, a negative count or length, a hypothesis of more than 511 labels (utterance and hypothesis are named), a
+ * label outside [0, output_dim - 1) (named), P > 1048576, edits without ref_len.  Host pointers.  Evaluation mode;
+ * parameters, accumulators, moments and statistics are not touched (same rules as tfk_ctc_greedy).  flags: 0. */
+int tfk_ctc_score(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                  const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const int32_t* ref_labels,
+                  const int32_t* ref_len, float* score, int32_t* edits, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_score_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t context_width, const float* cmvn, const int32_t* hyp_count, const int32_t* labels,
+                      const int32_t* label_len, const int32_t* ref_labels, const int32_t* ref_len, float* score,
+                      int32_t* edits, int flags);
+/* (ABI 14) Tests / tools: the scores alone on logits [T, ld] of O classes, DEVICE pointers: seg[U + 1] = first row of every
+ * utterance, pair_utt[P] = the utterance of pair p (in [0, U); pairs of one utterance should be adjacent), lab_off[P + 1] =
+ * first label of every pair in labels; score [P] as above.  Rows outside [seg[0], seg[U]) do not matter.  The three small
+ * tables are read back first (the longest hypothesis selects the kernel: one synchronisation of `stream`); the kernels and
+ * the call's own scratch (T floats, from the stream's memory pool) are stream-ordered.  Labels are not validated (a value
+ * outside [0, O) is clamped). */
+int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                         const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off, float* score);
 /* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
  * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */

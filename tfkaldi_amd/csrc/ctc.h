@@ -121,6 +121,20 @@ const char* ctc_align_limits(int O, int T, int U, int max_labels);
 void ctc_viterbi_align(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
                        const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch, int32_t* ali,
                        float* score);
+// N-best rescoring: score[p] = log p(labels_p | x_u), the natural log of the sum over ALL valid CTC alignments of pair p's
+// label sequence labels[lab_off[p], lab_off[p + 1]) on the frames of utterance u = pair_utt[p] (the contract is the comment
+// at tfk_ctc_score in tfkaldi_hip.h).  States and transitions as the loss, so score = -(that utterance's CTC loss with those
+// labels); -inf for a pair too short for its labels, for a zero-frame utterance 0 if S == 0 else -inf.  The pairs of one
+// utterance should be adjacent (they share the rows they read); any order is correct.  fp32 state values relative to a
+// running offset kept in double, as the loss.  scratch: ctc_score_scratch_bytes(T) bytes (the rows' log-sum-exps: T floats
+// whatever P is); max_labels >= every label count (it selects the register tile).  ctc_score_limits: NULL, or the limit a
+// shape breaks.
+constexpr int kCtcScoreMaxPairs = 1 << 20;
+size_t ctc_score_scratch_bytes(int T);
+const char* ctc_score_limits(int O, int T, int U, int P, int max_labels);
+void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+               const int32_t* pair_utt, int P, const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch,
+               float* score);
 // tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
 // ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
 // length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,

@@ -12,6 +12,8 @@
 //   ctc_viterbi      forced alignment, ONE WAVE PER UTTERANCE: the max-plus twin of the forward sweep on the raw logits
 //                    with 2-bit back-pointers, then the backtrace over back-pointer rows staged 64 frames at a time in LDS
 //                    (ctc_row_lse supplies the rows' log-sum-exps for the score)
+//   ctc_score        N-best rescoring, ONE WAVE PER (utterance, hypothesis) PAIR: the forward sweep again, gathering the
+//                    logits itself as ctc_viterbi does and storing nothing per frame; out: log p(labels | x) per pair
 // Log space, fp32, with a large finite "minus infinity" so that no inf - inf can arise.
 #include "ctc.h"
 
@@ -1486,6 +1488,113 @@ ctc_viterbi_kernel(const float* __restrict__ logits, int ld, int O, const int32_
   }
 }
 
+// ---- N-best rescoring (the exact log p(labels | x) of named label sequences; the contract is stated in ctc.h) ----
+
+// ONE WAVE PER (utterance, hypothesis) PAIR: the forward sweep of ctc_alpha_beta_kernel in the sum-product semiring -- lse3,
+// lane-owned states, DPP neighbour shifts, PFD rows in flight with clamped row indices, the state vector re-centred on its
+// maximum every PFD steps with the sum of the shifts in double, the end reduction over n - 1 and n - 2 -- fed as
+// ctc_viterbi_kernel is: the lane gathers the logits of its states' classes itself and nothing is stored per frame.  The
+// emission is lp = z[t, cls] - lse[t] in fp32, the expression ctc_gather_kernel evaluates; lse[t] (ctc_row_lse_kernel, one
+// value per frame whatever the number of pairs) rides in the ring beside the row.  The pairs of one utterance are adjacent
+// in the grid and read the same rows: the first wave brings a row into the cache, its neighbours find it there.
+template <int R>
+__global__ void __launch_bounds__(64)
+ctc_score_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U,
+                 const int32_t* __restrict__ pair_utt, const int32_t* __restrict__ labels,
+                 const int32_t* __restrict__ lab_off, const float* __restrict__ lse, float* __restrict__ score) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int u = min(max(pair_utt[p], 0), U - 1);  // (clamped: a bad index must not become a bad address)
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int l0 = lab_off[p], S = lab_off[p + 1] - l0, n = 2 * S + 1;
+  if (Tn <= 0) {  // an utterance without frames: only the empty labelling is possible
+    if (lane == 0) score[p] = S == 0 ? 0.f : -INFINITY;
+    return;
+  }
+  if (S < 0 || n > 64 * R) {  // not this launch's register tile (the launcher's max_labels rules it out)
+    if (lane == 0) score[p] = __builtin_nanf("");
+    return;
+  }
+  const int s0 = lane * R;
+  int cls[R];
+  bool skip_in[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int s = s0 + r, j = s >> 1;
+    const bool lab = (s & 1) && s < n;
+    cls[r] = lab ? min(max(labels[l0 + j], 0), O - 1) : O - 1;
+    skip_in[r] = lab && j >= 1 && labels[l0 + j] != labels[l0 + j - 1];
+  }
+  const float* zu = logits + (size_t)r0 * ld;
+  const float* lu = lse + r0;
+  constexpr int PFD = 8;
+  float pre[PFD][R], prl[PFD];
+  double off = 0.0;
+  float a[R];
+  {
+    const float l = lu[0];
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = (s0 + r < 2 && s0 + r < n) ? zu[cls[r]] - l : NEG;
+  }
+#pragma unroll
+  for (int j = 0; j < PFD; ++j) {
+    const int row = min(1 + j, Tn - 1);
+    prl[j] = lu[row];
+#pragma unroll
+    for (int r = 0; r < R; ++r) pre[j][r] = zu[(size_t)row * ld + cls[r]];
+  }
+  for (int t0 = 1; t0 < Tn; t0 += PFD) {
+#pragma unroll
+    for (int j = 0; j < PFD; ++j) {
+      const int t = t0 + j;
+      const bool live = t < Tn;
+      const int nrow = min(t + PFD, Tn - 1);
+      float cur[R];
+      const float curl = prl[j];
+      prl[j] = lu[nrow];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        cur[r] = pre[j][r] - curl;
+        pre[j][r] = zu[(size_t)nrow * ld + cls[r]];
+      }
+      const float up1 = lane_prev(a[R - 1], NEG, lane), up2 = lane_prev(a[R - 2], NEG, lane);
+      float na[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float p1 = r >= 1 ? a[r - 1] : up1;
+        const float p2 = r >= 2 ? a[r - 2] : (r == 1 ? up1 : up2);
+        const float v = (s0 + r < n) ? lse3(a[r], p1, skip_in[r] ? p2 : NEG) + cur[r] : NEG;
+        na[r] = live ? v : a[r];
+      }
+      if (j == PFD - 1) {  // compile-time: re-centre the state vector on its maximum
+        float m = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) m = fmaxf(m, na[r]);
+        m = wave_max(m);
+        if (live && m > -1e29f) {
+          off += (double)m;
+#pragma unroll
+          for (int r = 0; r < R; ++r) na[r] = fmaxf(na[r] - m, NEG);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) a[r] = na[r];
+    }
+  }
+  // log p(labels) = alpha_T(n-1) (+) alpha_T(n-2)
+  float m = NEG;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (s0 + r == n - 1 || s0 + r == n - 2) m = fmaxf(m, a[r]);
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float se = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (s0 + r == n - 1 || s0 + r == n - 2) se += expf(a[r] - m);
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+  const float log_z_rel = m + logf(se);  // relative to the final offset
+  if (lane == 0) score[p] = log_z_rel > -1e29f ? (float)(off + (double)log_z_rel) : -INFINITY;
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -1613,6 +1722,32 @@ void ctc_viterbi_align(hipStream_t s, const float* logits, int ld, int O, int T,
     case 4: hipLaunchKernelGGL(ctc_viterbi_kernel<4>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
     case 8: hipLaunchKernelGGL(ctc_viterbi_kernel<8>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
     default: hipLaunchKernelGGL(ctc_viterbi_kernel<16>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, lse, bp, ali, score); break;
+  }
+}
+
+size_t ctc_score_scratch_bytes(int T) { return (size_t)(T > 0 ? T : 0) * sizeof(float); }
+
+const char* ctc_score_limits(int O, int T, int U, int P, int max_labels) {
+  if (O < 2) return "output_dim < 2 (one label + blank)";
+  if (max_labels < 0) return "a negative length";
+  if (max_labels > kCtcMaxLabels) return "more than 511 labels in one hypothesis";
+  if (T < 0 || T > kCtcAlignMaxFrames) return "more than 8388607 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  if (P < 0 || P > kCtcScoreMaxPairs) return "more than 1048576 (utterance, hypothesis) pairs";
+  return nullptr;
+}
+
+void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+               const int32_t* pair_utt, int P, const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch,
+               float* score) {
+  if (P <= 0 || U <= 0) return;
+  float* lse = static_cast<float*>(scratch);
+  if (T > 0) hipLaunchKernelGGL(ctc_row_lse_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, lse);
+  switch (regs_for(max_labels)) {
+    case 2: hipLaunchKernelGGL(ctc_score_kernel<2>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
+    case 4: hipLaunchKernelGGL(ctc_score_kernel<4>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
+    case 8: hipLaunchKernelGGL(ctc_score_kernel<8>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
+    default: hipLaunchKernelGGL(ctc_score_kernel<16>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
   }
 }
 

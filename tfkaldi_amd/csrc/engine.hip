@@ -67,7 +67,7 @@ struct LayerLayout {
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
   KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
-  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_COUNT
+  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
@@ -75,7 +75,7 @@ const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
                                      "misc",                    "ctc_best_path",    "edit_distance",
                                      "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm",
-                                     "ctc_beam_search_topk",    "ctc_topk_rows"};
+                                     "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score"};
 
 struct ProfRec {
   int family;
@@ -199,6 +199,15 @@ struct tfk_engine {
   // forced alignment (tfk_ctc_align): the back-pointer rows and row log-sum-exps of ctc_viterbi_align
   unsigned char* ctc_bp = nullptr;
   size_t ctc_cap_bp = 0;
+  // N-best rescoring (tfk_ctc_score): the row log-sum-exps of ctc_score, and the pair tables
+  // [pair_utt P | lab_off P + 1 | reference start P | reference length P | labels] with their pinned staging
+  unsigned char* ctc_sc = nullptr;
+  size_t ctc_cap_sc = 0;
+  int32_t* ctc_pair = nullptr;
+  size_t ctc_cap_pair = 0;
+  int32_t* h_pair = nullptr;
+  size_t h_pair_cap = 0;
+  hipEvent_t ctc_pair_staged = nullptr;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1855,8 +1864,10 @@ int tfk_destroy(tfk_engine* e) {
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
                   (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
-                  (void*)e->ctc_pre})
+                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair})
     if (p) hipFree(p);
+  if (e->h_pair) hipHostFree(e->h_pair);
+  if (e->ctc_pair_staged) hipEventDestroy(e->ctc_pair_staged);
   if (e->h_dec) hipHostFree(e->h_dec);
   for (hipEvent_t ev : e->post_ev) hipEventDestroy(ev);
   for (int k = 0; k < 2; ++k) {
@@ -2761,6 +2772,157 @@ int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t 
   const size_t bytes = ctc_align_scratch_bytes(T, max_labels);
   HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
   ctc_viterbi_align((hipStream_t)stream, logits, (int)ld, O, T, seg, U, labels, lab_off, max_labels, scratch, ali, score);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+// N-best rescoring (the exact log p(labels | x) of the caller's hypotheses and their label errors; the contract: tfkaldi_hip.h):
+// evaluation-mode forward as tfk_posteriors, then ctc_score (and label_edit_distance) on the logits in HBM; P or 2P words go
+// back to the host.  The references travel through ctc_stage as tfk_ctc_greedy's do; the pair tables are staged behind them.
+static int ctc_score_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                          const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const int32_t* ref_labels,
+                          const int32_t* ref_len, float* score, int32_t* edits, int flags, const RawSpec* raw) {
+  CHK(decode_args(e, "tfk_ctc_score", X, T, flags, raw));
+  if (U <= 0 || !utt_len || !hyp_count) return fail(-1, "CTC score: utt_len / hyp_count is NULL or no utterances");
+  if (edits && !ref_len) return fail(-1, "CTC score: edits without references (ref_len is NULL)");
+  int64_t P64 = 0;
+  for (int u = 0; u < U; ++u) {
+    if (hyp_count[u] < 0) return fail(-1, "CTC score: utterance %d has a negative hypothesis count", u);
+    if (utt_len[u] < 0) return fail(-1, "CTC score: utterance %d has a negative length", u);
+    P64 += hyp_count[u];
+    if (P64 > kCtcScoreMaxPairs)
+      return fail(-1, "CTC score: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
+  }
+  const int P = (int)P64;
+  if (P > 0 && (!label_len || !score)) return fail(-1, "CTC score: label_len / score is NULL");
+  std::vector<int32_t> tab(4 * (size_t)P + 1);  // [pair_utt | lab_off | reference start | reference length]
+  int32_t* pair_utt = tab.data();
+  int32_t* lab_off = pair_utt + P;
+  int32_t* ref_at = lab_off + P + 1;
+  int32_t* ref_cnt = ref_at + P;
+  int max_hyp = 0;
+  {
+    int p = 0;
+    int64_t first = 0, ref_first = 0;
+    lab_off[0] = 0;
+    for (int u = 0; u < U; ++u) {
+      const int32_t rn = edits ? ref_len[u] : 0;
+      for (int h = 0; h < hyp_count[u]; ++h, ++p) {
+        const int32_t n = label_len[p];
+        if (n < 0) return fail(-1, "CTC score: utterance %d, hypothesis %d has a negative length", u, h);
+        if (n > kCtcMaxLabels)
+          return fail(-1, "CTC score: utterance %d, hypothesis %d has %d labels (limit %d)", u, h, n, kCtcMaxLabels);
+        if (n > 0 && !labels) return fail(-1, "CTC score: labels is NULL");
+        for (int32_t i = 0; i < n; ++i)
+          if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
+            return fail(-1, "CTC score: utterance %d, hypothesis %d: label %d outside [0, %d)", u, h, labels[first + i],
+                        e->O - 1);
+        first += n;
+        if (first > 0x7fffffff) return fail(-1, "CTC score: more than 2^31 - 1 labels in one call");
+        pair_utt[p] = u;
+        lab_off[p + 1] = (int32_t)first;
+        ref_at[p] = (int32_t)ref_first;
+        ref_cnt[p] = rn;
+        max_hyp = n > max_hyp ? n : max_hyp;
+      }
+      if (rn > 0) ref_first += rn;  // (a negative reference length is ctc_stage's to refuse)
+    }
+  }
+  if (const char* why = ctc_score_limits(e->O, T, U, P, max_hyp)) return fail(-1, "CTC score (T %d, U %d, P %d): %s", T, U, P, why);
+  if (P == 0) return 0;
+  const size_t total = (size_t)lab_off[P], tab_words = 4 * (size_t)P + 1;
+  const size_t back = edits ? 2 * (size_t)P : (size_t)P;  // [score | distances]
+  int max_ref = 0;
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, ref_labels, edits ? ref_len : nullptr}, edits != nullptr,
+                  2 * (size_t)P, 0, back, &max_ref, [&]() -> int {
+    CHK(grow(e, &e->ctc_sc, &e->ctc_cap_sc, ctc_score_scratch_bytes(T)));
+    CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, tab_words + (total > 0 ? total : 1)));
+    // pinned staging, guarded by its own event (a call that failed midway may have left a copy in flight)
+    if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
+    CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, tab_words + total, /*slack=*/true, /*sync=*/false));
+    memcpy(e->h_pair, tab.data(), tab_words * sizeof(int32_t));
+    if (total > 0) memcpy(e->h_pair + tab_words, labels, total * sizeof(int32_t));
+    HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, (tab_words + total) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
+    return 0;
+  }, [&] {
+    const int32_t* d_utt = e->ctc_pair;
+    const int32_t* d_off = d_utt + P;
+    const int32_t* d_ref_at = d_off + P + 1;
+    const int32_t* d_ref_cnt = d_ref_at + P;
+    const int32_t* d_lab = e->ctc_pair + tab_words;
+    {
+      // (the rows are read once per pair, mostly from the cache: P / U waves of an utterance share them)
+      ProfScope ps(e, KF_CTC_SCORE, 0, 4.0 * T * e->O + 8.0 * T + 4.0 * (double)total + 4.0 * P);
+      ctc_score(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, d_utt, P, d_lab, d_off, max_hyp, e->ctc_sc,
+                reinterpret_cast<float*>(e->ctc_dec));
+    }
+    if (edits) {
+      // the distance is symmetric: the references are the kernel's `hyp` operand (start and length per pair), the pairs'
+      // labels its `ref` operand (the one that selects the register tile)
+      ProfScope ps(e, KF_EDIT_DISTANCE, 0, 4.0 * (double)total + 4.0 * P);
+      label_edit_distance(e->stream, e->ctc_lab, d_ref_at, d_ref_cnt, d_lab, d_off, P, max_hyp, e->ctc_dec + P);
+    }
+  }));
+  memcpy(score, e->h_dec, (size_t)P * sizeof(float));
+  if (edits) memcpy(edits, e->h_dec + P, (size_t)P * sizeof(int32_t));
+  return 0;
+}
+
+int tfk_ctc_score(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                  const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const int32_t* ref_labels,
+                  const int32_t* ref_len, float* score, int32_t* edits, int flags) {
+  return ctc_score_impl(e, X, ldx, T, utt_len, U, hyp_count, labels, label_len, ref_labels, ref_len, score, edits, flags,
+                        nullptr);
+}
+int tfk_ctc_score_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                      int32_t context_width, const float* cmvn, const int32_t* hyp_count, const int32_t* labels,
+                      const int32_t* label_len, const int32_t* ref_labels, const int32_t* ref_len, float* score,
+                      int32_t* edits, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_score_impl(e, raw, ldraw, T, utt_len, U, hyp_count, labels, label_len, ref_labels, ref_len, score, edits, flags,
+                        &r);
+}
+int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                         const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off, float* score) {
+  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
+  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC score: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
+  if (P == 0) return 0;
+  if (U == 0) return fail(-1, "CTC score: %d pairs and no utterance", P);
+  if (!seg || !pair_utt || !lab_off || !score || (T > 0 && !logits))
+    return fail(-1, "logits / seg / pair_utt / lab_off / score is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  // The register tile follows the longest hypothesis, which only the device knows: the three small tables come back first
+  // (U + 2P + 2 words, one synchronisation); everything after that is stream-ordered.
+  std::vector<int32_t> h((size_t)U + 1 + 2 * (size_t)P + 1);
+  int32_t* h_utt = h.data() + U + 1;
+  int32_t* h_off = h_utt + P;
+  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int u = 0; u < U; ++u)
+    if (h[u + 1] < h[u]) return fail(-1, "CTC score: utterance %d has a negative length", u);
+  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC score: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
+  int max_labels = 0;
+  for (int p = 0; p < P; ++p) {
+    const int32_t n = h_off[p + 1] - h_off[p];
+    if (n < 0) return fail(-1, "CTC score: pair %d has a negative length", p);
+    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC score: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
+    max_labels = n > max_labels ? n : max_labels;
+  }
+  if (h_off[0] < 0) return fail(-1, "CTC score: lab_off[0] = %d < 0", h_off[0]);
+  if (const char* why = ctc_score_limits(O, T, U, P, max_labels))
+    return fail(-1, "CTC score (O %d, T %d, U %d, P %d): %s", O, T, U, P, why);
+  if (h_off[P] > h_off[0] && !labels) return fail(-1, "CTC score: labels is NULL");
+  void* scratch = nullptr;  // the call's own scratch, released in stream order
+  const size_t bytes = ctc_score_scratch_bytes(T);
+  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
+  ctc_score((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, max_labels, scratch, score);
   const hipError_t launched = hipGetLastError();
   const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
   HIPCHK(launched);

@@ -161,10 +161,13 @@ def _eval_accumulate_all(engine, mine):
         _eval_accumulate(engine, mb)
 
 
-def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None):
+def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
     """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
     (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM; label_topk:
-    pruned to the frame's label_topk most probable labels)"""
+    pruned to the frame's label_topk most probable labels).  rescore_paths: an int N takes the search's N best, scores them
+    exactly with their label errors (ctc_score) and counts the hypothesis that is best after decoder.ctc_rerank."""
+    if rescore_paths is not None and beam_width is None:
+        raise ValueError("rescoring re-ranks the N best of a beam search: give beam_width with rescore_paths")
     if lm is not None and beam_width is None:
         raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
     if label_topk is not None and beam_width is None:
@@ -178,8 +181,22 @@ def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None):
         kw = dict(kw, label_topk=label_topk)
     if mb.context_width is not None:  # unspliced frames: CMVN + splice on the device
         entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
-    edits = getattr(engine, entry)(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens, **kw)[-1]
     import numpy as np
+    if rescore_paths is not None:
+        from .neuralNetworks.decoder import ctc_rerank
+        found, beam = getattr(engine, entry)(mb.X, mb.utt_lens, top_paths=int(rescore_paths), **kw)[:2]
+        # (padding paths -- beam score -inf -- are not pairs; the search's own ranking value is what marks them)
+        kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+        flat = [h for hs in kept for h in hs]
+        labels = np.concatenate(flat) if flat else np.zeros(0, dtype=np.int32)
+        raw = mb.context_width is not None
+        scores, dists = getattr(engine, "ctc_score_raw" if raw else "ctc_score")(
+            mb.X, mb.utt_lens, *((mb.context_width,) if raw else ()), [len(hs) for hs in kept], labels,
+            [h.size for h in flat], ref_labels=mb.labels, ref_lens=mb.label_lens, **({"cmvn": mb.cmvn} if raw else {}))
+        edits = [int(d[ctc_rerank(hs, sc, lm)[0][0]]) if len(hs) else int(n)
+                 for hs, sc, d, n in zip(kept, scores, dists, mb.label_lens)]
+        return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
+    edits = getattr(engine, entry)(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens, **kw)[-1]
     return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
 
 
@@ -1295,11 +1312,12 @@ class DataParallel(object):
         start, end = partition(len(microbatches), self.world)[self.rank]
         return self.eval_own(engine, microbatches[start:end])
 
-    def label_errors(self, engine, microbatches, beam_width=None, lm=None, label_topk=None):
+    def label_errors(self, engine, microbatches, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
         """(edits, reference labels): label errors summed over the CTC micro-batches of the WHOLE batch (identical on every
         rank) under best-path decoding (beam_width None) or the best path of a prefix beam search of that width (lm: an
         NgramLM the search ranks its prefixes with; label_topk: an int prunes the search to the frame's label_topk most
-        probable labels, for models of any output size; every rank passes the same ones).
+        probable labels, for models of any output size; rescore_paths: an int N re-ranks the search's N best by their exact
+        scores (ctc_score + ctc_rerank, lm honoured) and counts the new best; every rank passes the same ones).
         COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and the two counts
         are SUM all-reduced as one int64 tensor over self.group (on the device for an NCCL / RCCL group)."""
         mine = microbatches
@@ -1308,7 +1326,7 @@ class DataParallel(object):
             mine = microbatches[start:end]
         edits = labels = 0
         for mb in mine:
-            e, n = _label_errors(engine, mb, beam_width, lm, label_topk)
+            e, n = _label_errors(engine, mb, beam_width, lm, label_topk, rescore_paths)
             edits += e
             labels += n
         if not self.enabled:

@@ -22,6 +22,18 @@ def _ptr(a):
     return c_void_p(None) if a is None else a.ctypes.data_as(c_void_p)
 
 
+def _levenshtein(a, b):
+    """Levenshtein distance (unit costs) of two int sequences: what the entries report when the engine is not called"""
+    row = np.arange(len(b) + 1)
+    for i, x in enumerate(a):
+        new = np.empty_like(row)
+        new[0] = i + 1
+        for j, y in enumerate(b):
+            new[j + 1] = min(row[j + 1] + 1, new[j] + 1, row[j] + (x != y))
+        row = new
+    return int(row[-1])
+
+
 class Engine(object):
     """One engine per GPU.  `torch_state=True` keeps the persistent state in a torch CUDA tensor and
     runs on a torch stream so torch.distributed (RCCL) can all-reduce views of the gradient region."""
@@ -532,6 +544,55 @@ class Engine(object):
         """ctc_align on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
         tensor (TFK_RAW_DEVICE)"""
         return self._align(self.lib.tfk_ctc_align_raw, raw, utt_lens, labels, label_lens, raw=(context_width, cmvn))
+
+    # ---- CTC N-best rescoring: the exact log p(labels | x) of named hypotheses, and their label errors ----
+    def _score(self, fn, frames, utt_lens, hyp_counts, labels, label_lens, ref_labels, ref_lens, raw=None):
+        utt_lens, ref_labels, ref_lens = self._refs(utt_lens, ref_labels, ref_lens, True, "references")
+        hyp_counts = np.ascontiguousarray(hyp_counts, dtype=np.int32).reshape(-1)
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
+        if hyp_counts.size != utt_lens.size or np.any(hyp_counts < 0):
+            raise ValueError("hypotheses: %d counts (smallest %d) for %d utterances"
+                             % (hyp_counts.size, int(hyp_counts.min()) if hyp_counts.size else 0, utt_lens.size))
+        P = int(hyp_counts.sum(dtype=np.int64))
+        if label_lens.size != P or np.any(label_lens < 0) or int(label_lens.sum(dtype=np.int64)) != labels.size:
+            raise ValueError("hypotheses: %d label counts (sum %d) for %d hypotheses and %d labels"
+                             % (label_lens.size, int(label_lens.sum(dtype=np.int64)), P, labels.size))
+        cuts = np.cumsum(hyp_counts, dtype=np.int64)[:-1]
+
+        def outputs(rows, U):  # (no frames: only the empty labelling has an alignment, the empty one)
+            if rows:
+                return np.empty(P, dtype=np.float32), None if ref_labels is None else np.empty(P, dtype=np.int32)
+            score = np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32)
+            if ref_labels is None:
+                return score, None
+            hyps = np.split(labels, np.cumsum(label_lens, dtype=np.int64)[:-1]) if P else []
+            refs = np.split(ref_labels, np.cumsum(ref_lens, dtype=np.int64)[:-1])
+            utt = np.repeat(np.arange(U), hyp_counts)
+            return score, np.array([_levenshtein(h, refs[u]) for h, u in zip(hyps, utt)], dtype=np.int32)
+
+        def result(lens, score, edits):
+            return np.split(score, cuts), None if edits is None else np.split(edits, cuts)
+        return self._decode(fn, frames, utt_lens, (ref_labels, ref_lens), outputs, result, (_ptr(hyp_counts), _ptr(labels),
+                                                                                           _ptr(label_lens)), raw)
+
+    def ctc_score(self, X, utt_lens, hyp_counts, labels, label_lens, ref_labels=None, ref_lens=None):
+        """N-best rescoring over the utterances X [sum(utt_lens), F] (tfk_ctc_score; the contract is stated in
+        include/tfkaldi_hip.h): for every (utterance, hypothesis) pair the EXACT natural-log probability log p(labels | x) --
+        the sum over all CTC alignments, minus the utterance's CTC loss with those labels -- where a beam search reports only
+        the alignments that survived its pruning.  hyp_counts[u] hypotheses per utterance (0 is allowed); labels back to back
+        in pair order (by utterance, then by hypothesis), label_lens per pair, at most 511 labels each.  With references
+        (ref_labels back to back, ref_lens per UTTERANCE) also the Levenshtein distance of every hypothesis to its
+        utterance's reference.  Returns (scores, edits): per utterance a float32 array of its hypotheses' scores (-inf for
+        one its utterance is too short for) and an int32 array of their distances (edits None without references)."""
+        return self._score(self.lib.tfk_ctc_score, X, utt_lens, hyp_counts, labels, label_lens, ref_labels, ref_lens)
+
+    def ctc_score_raw(self, raw, utt_lens, context_width, hyp_counts, labels, label_lens, ref_labels=None, ref_lens=None,
+                      cmvn=None):
+        """ctc_score on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        return self._score(self.lib.tfk_ctc_score_raw, raw, utt_lens, hyp_counts, labels, label_lens, ref_labels, ref_lens,
+                           raw=(context_width, cmvn))
 
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):

@@ -30,6 +30,30 @@ def ctc_segments(ali, labels):
     return [(int(k), int(frames[a]), int(frames[b - 1]) + 1) for k, a, b in zip(labels, first, last)]
 
 
+def ctc_rerank(hyps, exact_scores, lm=None):
+    """Second-pass ranking of ONE utterance's N-best list: `hyps` int label arrays in the first pass's order,
+    `exact_scores` their exact log-probabilities log p(labels | x) (Decoder.ctc_score).  The combined score of a hypothesis
+    is its exact score plus lm.score(h) (a ctc_lm.NgramLM: weight, label bonus and end term as the search uses them), in
+    float64.  Returns (order, scores, posteriors): `order` the indices into hyps by descending combined score -- a stable
+    sort, so a tie keeps the first pass's order -- `scores` float64 the combined scores in that order, `posteriors` float64
+    their softmax over the list (a -inf hypothesis sorts last with posterior 0; a list without a finite score gets zeros)."""
+    am = np.asarray(exact_scores, dtype=np.float64).reshape(-1)
+    if am.size != len(hyps):
+        raise ValueError("%d hypotheses, %d scores" % (len(hyps), am.size))
+    if np.any(np.isnan(am)) or np.any(am == np.inf):
+        raise ValueError("exact scores are log-probabilities: finite or -inf")
+    total = am.copy()
+    if lm is not None:
+        total += np.array([lm.score(h) for h in hyps], dtype=np.float64).reshape(am.shape)
+    order = np.argsort(-total, kind="stable")
+    scores = total[order]
+    post = np.zeros_like(scores)
+    if scores.size and scores[0] > -np.inf:
+        post = np.exp(scores - scores[0])
+        post /= post.sum()
+    return order, scores, post
+
+
 class _Graph(object):
     def finalize(self):
         pass
@@ -156,6 +180,48 @@ class Decoder(object):
             return [], np.zeros(0, dtype=np.float32)
         targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
         return self._ctc("ctc_align", utterances, np.concatenate(targets), [t.size for t in targets])
+
+    def ctc_score(self, utterances, hyps, refs=None):
+        """N-best rescoring of a CTC model (tfk_ctc_score; the contract is stated in include/tfkaldi_hip.h): every utterance
+        in ONE forward pass, then for every hypothesis hyps[u][n] (a list of int label arrays per utterance, possibly empty)
+        the EXACT log-probability log p(labels | x), the sum over all its CTC alignments, on the device.  refs: one int
+        label array per utterance, for the label errors.  Returns (scores, edits): scores[u] float32 [len(hyps[u])], edits[u]
+        int32 Levenshtein distances to refs[u] (edits None without refs).  All `Unspliced` -> device-side splice."""
+        if len(utterances) != len(hyps) or (refs is not None and len(refs) != len(utterances)):
+            raise ValueError("%d utterances, %d hypothesis lists, %s references"
+                             % (len(utterances), len(hyps), "no" if refs is None else len(refs)))
+        if len(utterances) == 0:
+            return [], None if refs is None else []
+        flat = [np.asarray(h, dtype=np.int32).reshape(-1) for hs in hyps for h in hs]
+        labels = np.concatenate(flat) if flat else np.zeros(0, dtype=np.int32)
+        kw = {}
+        if refs is not None:
+            refs = [np.asarray(r, dtype=np.int32).reshape(-1) for r in refs]
+            kw = {"ref_labels": np.concatenate(refs), "ref_lens": [r.size for r in refs]}
+        return self._ctc("ctc_score", utterances, [len(hs) for hs in hyps], labels, [h.size for h in flat], **kw)
+
+    def ctc_rescore(self, utterances, beam_width=100, top_paths=10, lm=None, label_topk=None):
+        """Two-pass decoding of a CTC model: the prefix beam search (ctc_beam_search, or ctc_beam_search_lm with `lm`;
+        label_topk as there), then ONE ctc_score pass over the paths whose beam score is finite (padding paths are not
+        scored), then ctc_rerank per utterance: the beam's scores count only the alignments that survived its pruning, the
+        second pass ranks by what the model really assigns (plus lm.score).  Returns (hyps, scores, am_scores, beam_rank,
+        posteriors), per utterance in the new order: hyps[u] the int32 label arrays, scores[u] float64 the combined scores,
+        am_scores[u] float32 the exact log-probabilities, beam_rank[u] the position each hypothesis had in the beam's
+        list, posteriors[u] float64 the softmax of the combined scores over the list."""
+        if len(utterances) == 0:
+            return [], [], [], [], []
+        if lm is None:
+            found, beam = self.ctc_beam_search(utterances, beam_width, top_paths, label_topk)
+        else:
+            found, _, beam = self.ctc_beam_search_lm(utterances, lm, beam_width, top_paths, label_topk)
+        kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+        exact = self.ctc_score(utterances, kept)[0]
+        out = ([], [], [], [], [])
+        for hs, am in zip(kept, exact):
+            order, scores, post = ctc_rerank(hs, am, lm)
+            for dst, v in zip(out, ([hs[i] for i in order], scores, am[order], order.astype(np.int32), post)):
+                dst.append(v)
+        return out
 
     def set_prior(self, prior):
         self.engine.set_prior(prior)

@@ -362,7 +362,7 @@ class CTCTrainer(Trainer):
     def compute_loss(self, targets, logits, logit_seq_length, target_seq_length):
         return "ctc"
 
-    def label_errors(self, inputs, targets, beam_width=None, lm=None, label_topk=None):
+    def label_errors(self, inputs, targets, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
         """Label errors of the batch under best-path decoding -- tf.nn.ctc_greedy_decoder(merge_repeated=True) followed by
         tf.edit_distance(normalize=False), the reference framework's standard CTC evaluation -- in evaluation mode, on the
         device (tfk_ctc_greedy).  Returns (sum of the Levenshtein distances, sum of the reference lengths) over the batch as
@@ -372,7 +372,11 @@ class CTCTrainer(Trainer):
         (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path.  lm: a ctc_lm.NgramLM ranks
         the beam's prefixes by acoustic + language-model score (tfk_ctc_beam_lm); it needs a beam_width.  label_topk: an int
         prunes the search to the frame's label_topk most probable labels (tfk_ctc_beam_topk), which is what lets a model of
-        more than 64 outputs be searched; it needs a beam_width too."""
+        more than 64 outputs be searched; it needs a beam_width too.  rescore_paths: an int N decodes the N best, scores
+        them exactly on the device with their label errors (tfk_ctc_score) and counts the hypothesis that is best after
+        re-ranking by exact score (+ lm.score with lm: decoder.ctc_rerank); it needs a beam_width as well."""
+        if rescore_paths is not None and beam_width is None:
+            raise ValueError("rescoring re-ranks the N best of a beam search: give beam_width with rescore_paths")
         if lm is not None and beam_width is None:
             raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
         if label_topk is not None and beam_width is None:
@@ -382,4 +386,6 @@ class CTCTrainer(Trainer):
         kw = {} if lm is None else {"lm": lm}
         if label_topk is not None:
             kw["label_topk"] = label_topk
+        if rescore_paths is not None:
+            kw["rescore_paths"] = rescore_paths
         return self.dp.label_errors(self.engine, self._microbatches(inputs, targets), beam_width=beam_width, **kw)

@@ -18,6 +18,11 @@ the same workload, and at label_topk = 63 (nothing pruned at 36 outputs: the pru
 same logits) -- the profiler's time of the ctc_beam_search_topk kernel and of the row pre-pass on its own, label error rates;
 and the wide leg: a model of 1000 outputs (which the unpruned search refuses) at label_topk = 1 .. 63 and W = 10, 100, the
 kernel's time per frame step against K + 1.
+`--score-only` runs the rescoring leg alone: the N-best of the search at W = 10 and 100 (top_paths = W, so 160 and 1600
+(utterance, hypothesis) pairs) scored exactly on the device with their label errors (tfk_ctc_score) -- ms per call, the
+profiler's time of the ctc_score kernels and that time per frame step, the loss's forward family (tfk_eval_accumulate_ctc) on
+the same batch as the yardstick, the host alternative (the float64 numpy restatement of the tests, timed on utterance 0's
+pairs and scaled), how many utterances change their best hypothesis, and the best-path / rescored / oracle label error rates.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -35,6 +40,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from test_ctc_align_host import viterbi_align  # noqa: E402
 from test_ctc_beam_host import prefix_beam_search  # noqa: E402
 from test_ctc_beam_lm_host import prefix_beam_search_lm  # noqa: E402
+from test_ctc_score_host import ctc_score_restated  # noqa: E402
 
 
 def main():
@@ -52,6 +58,14 @@ def main():
     if "--align-only" in sys.argv:
         eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
         align_leg(eng, X, utt, labels, np.asarray(lab), "random output weights")
+        eng.close()
+        return
+    if "--score-only" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        bias = np.zeros(O, np.float32)
+        bias[O - 1] = 2.0
+        eng.set(_lib.BIASES, eng.L, bias)
+        score_leg(eng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
         eng.close()
         return
     if "--topk-only" in sys.argv:
@@ -296,6 +310,44 @@ def wide_leg(rng, X, utt, cfg):
                   "score %.3f" % (W, K, ms, kt, kt * 1e3 / max(utt), kt * 1e3 / max(utt) / (K + 1), rows,
                                   np.mean([h[0].size for h in got[0]]), float(np.mean(got[1][:, 0]))))
     eng.close()
+
+
+def score_leg(eng, X, utt, labels, lab, case):
+    from tfkaldi_amd.neuralNetworks.decoder import ctc_rerank
+    zs = np.split(eng.posteriors(X, raw_logits=True), np.cumsum(utt)[:-1])
+    total = float(np.sum(lab))
+
+    def loss():
+        eng.eval_accumulate_ctc(X, utt, labels, lab)
+        eng.eval_finish()
+    loss_ms, loss_kern = _kernel_ms(eng, loss, ("softmax_xent",))
+    print("  score (%s): yardstick, the loss's forward on the same batch (%d utterances, %d labels each): "
+          "tfk_eval_accumulate_ctc %8.3f ms/call, softmax_xent family (softmax, gather, forward sweep) %8.3f ms "
+          "(%.3f us per frame step)" % (case, len(utt), int(np.mean(lab)), loss_ms, loss_kern, loss_kern * 1e3 / max(utt)))
+    for W in (10, 100):
+        found, beam, best_edits = eng.ctc_beam(X, utt, beam_width=W, top_paths=W, labels=labels, label_lens=lab)
+        kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+        flat = [h for hs in kept for h in hs]
+        counts, hl, hn = [len(hs) for hs in kept], np.concatenate(flat), [h.size for h in flat]
+        call = lambda: eng.ctc_score(X, utt, counts, hl, hn, labels, lab)
+        scores, dists = call()
+        ms, kern, ed = _kernel_ms(eng, call, ("ctc_score", "edit_distance"))
+        t0 = time.perf_counter()
+        s64 = np.array([ctc_score_restated(zs[0], h) for h in kept[0]])
+        host = (time.perf_counter() - t0) * 1e3
+        order = [ctc_rerank(hs, sc)[0] for hs, sc in zip(kept, scores)]
+        moved = sum(int(o[0] != 0) for o in order)
+        rescored = sum(int(d[o[0]]) for d, o in zip(dists, order))
+        oracle = sum(int(d.min()) for d in dists)
+        gap = max(float(np.max(sc - bm[:len(sc)])) for sc, bm in zip(scores, beam))
+        print("  score (%s) W=%3d: %d pairs, longest hypothesis %d labels; tfk_ctc_score %8.3f ms/call, ctc_score kernels "
+              "%8.3f ms (%.3f us per frame step, %.2f x the loss's forward family), edit_distance %7.3f ms; host alternative "
+              "(numpy float64 restatement) %.0f ms for utterance 0's %d pairs = %.0f ms scaled to %d; %d of %d utterances "
+              "change their best hypothesis, largest exact minus beam score %.3f nats; label error rate best path %.4f "
+              "rescored %.4f oracle %.4f; largest |device - float64| on utterance 0 %.1e"
+              % (case, W, len(flat), max(hn), ms, kern, kern * 1e3 / max(utt), kern / loss_kern, ed, host, len(kept[0]),
+                 host * len(flat) / len(kept[0]), len(flat), moved, len(utt), gap, best_edits.sum() / total, rescored / total,
+                 oracle / total, float(np.max(np.abs(scores[0] - s64)))))
 
 
 def align_leg(eng, X, utt, labels, lab, case):
