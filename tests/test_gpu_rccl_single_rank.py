@@ -83,8 +83,10 @@ def test_single_rank_rccl_is_identity(gpu, tmp_path, mode, comm, dtype):
         for i, (X, y) in enumerate(mbs):
             eng.accumulate(X, y, last=(i == len(mbs) - 1))
         want.append(eng.apply())
-    for X, y in _data(num_mb, 9):
-        eng.eval_accumulate(X, y)
+    # the validation pass as DataParallel.eval_step runs it (plain micro-batches as ONE stacked pass: the frames' losses are
+    # summed in one reduction, which rounds differently from three sums added up -- bit-for-bit needs the same order)
+    from tfkaldi_amd.dataparallel import _eval_accumulate_all
+    _eval_accumulate_all(eng, _data(num_mb, 9))
     want.append(eng.eval_finish())
     ref = _collect(eng, want)
     eng.close()

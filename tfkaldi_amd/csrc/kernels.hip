@@ -236,8 +236,10 @@ bn_stats_partial_kernel(const float* __restrict__ z, int T, int ld, int rows_per
   s = reduce_rows(s, sm);
   const int n = max(t.r1 - t.r0, 0);
   if (threadIdx.y == 0) {
-    const float inv = n > 0 ? 1.f / (float)n : 0.f;
-    sm_mean[threadIdx.x] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+    // a true division, not a product with 1 / n: the mean of a CONSTANT column must be that constant bit for bit (n * c is
+    // exact, n * c * fl(1 / n) can be an ulp off, and rstd = 1 / sqrt(eps) makes 6e-5 of the output out of an ulp of 30)
+    const float fn = n > 0 ? (float)n : 1.f;
+    sm_mean[threadIdx.x] = make_float4(__fdiv_rn(s.x, fn), __fdiv_rn(s.y, fn), __fdiv_rn(s.z, fn), __fdiv_rn(s.w, fn));
   }
   __syncthreads();
   const float4 mu = sm_mean[threadIdx.x];
@@ -436,8 +438,9 @@ bn_act_forward_kernel(ActDesc d, const float* __restrict__ z, float* __restrict_
     }
   tot = reduce_rows(tot, sm);
   if (threadIdx.y == 0) {
-    const float inv = 1.f / (float)T;
-    smm[threadIdx.x] = make_float4(tot.x * inv, tot.y * inv, tot.z * inv, tot.w * inv);
+    // (a true division, as in bn_stats_partial_kernel: a constant column's mean is that constant bit for bit)
+    const float fT = (float)T;
+    smm[threadIdx.x] = make_float4(__fdiv_rn(tot.x, fT), __fdiv_rn(tot.y, fT), __fdiv_rn(tot.z, fT), __fdiv_rn(tot.w, fT));
   }
   __syncthreads();
   const float4 mu = smm[threadIdx.x];
