@@ -155,7 +155,8 @@ int tfk_accumulate(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y,
 /* The step BEFORE the path, moved onto the device: per-speaker mean/variance normalisation and the
  * +-context splice of processing/feature_reader.py:91-156 (apply_cmvn :109-115, splice :117-156).
  * raw [T, ldraw] = the UNSPLICED frames (raw_dim columns, input_dim = raw_dim * (2*context_width + 1)) of U
- * utterances back to back, utt_len[U] their frame counts (sum = T).
+ * utterances back to back, utt_len[U] their frame counts (sum = T; 0 is allowed anywhere, also for more utterances
+ * than there are frames: an empty utterance contributes no row and its cmvn rows are not read).
  * cmvn = NULL: raw is already normalised.  cmvn = [U, 2, raw_dim] fp32: row 0 of utterance u is its speaker's
  * mean, row 1 the standard deviation sqrt(E[x^2] - mean^2); the device computes (raw - mean) / std with the same
  * IEEE roundings as numpy's float32 subtract and divide, so the result is bit-identical to the host path.
@@ -233,7 +234,12 @@ int tfk_apply_enqueue(tfk_engine* e);
 
 /* Replaces `update_valid_loss.run(feed_dict)` (trainer.py:188-195, 433): eval-mode forward + loss. */
 int tfk_eval_accumulate(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int32_t T, int flags);
-/* Replaces `average_loss.eval()` + re-initialisation (trainer.py:436-441). */
+/* Replaces `average_loss.eval()` + re-initialisation (trainer.py:436-441).
+ * Evaluation INSIDE a training step (between the tfk_accumulate* calls of a step and its tfk_apply): the reference keeps one
+ * batch_loss / num_frames pair for both, so its validation would cost the step its loss and its gradient scale.  Here the
+ * step's sums are set aside when the first tfk_eval_accumulate* of such an evaluation runs and tfk_eval_finish, after
+ * reporting the evaluation's own average, puts them back: the step finishes as if nothing had been evaluated.  (Without an
+ * evaluation pass in front of it tfk_eval_finish re-initialises whatever the sums hold, as before.) */
 int tfk_eval_finish(tfk_engine* e, float* average_loss);
 
 int tfk_halve_learning_rate(tfk_engine* e); /* trainer.py:141-142 */

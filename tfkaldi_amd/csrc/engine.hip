@@ -159,6 +159,13 @@ struct tfk_engine {
   bool apply_open = false, apply_direct = false;  // between tfk_apply_begin and tfk_apply_end
   float cur_lr_t = 0.f;
   bool scalars_fresh = true;     // batch_loss / num_frames / #mb are logically zero (next loss_reduce overwrites)
+  // An evaluation pass in the middle of a training step (micro-batches accumulated, optimiser not yet run): the reference's
+  // update_valid_loss adds to the SAME batch_loss / num_frames as training and average_loss re-initialises them, which would
+  // cost the step its loss and -- G / num_frames -- its gradient scale.  The step's sums are set aside before the first such
+  // evaluation pass (stash_scalars) and put back by tfk_eval_finish, which then reports the evaluation's own sums.
+  bool step_open = false;        // a training micro-batch has been accumulated since the last optimiser step / reset
+  bool stash_live = false;       // scalar_stash holds the open step's (loss, frames, #mb)
+  float* scalar_stash = nullptr;
   bool colsum_done = false;      // the output layer's bias-gradient partial sums of THIS micro-batch are in the workspace already
                                  // (colsum_loss, launched with the loss sum right behind softmax_xent)
   bool fuse_hb_enabled = true;   // env TFK_FUSE_HB=0: separate statistics pass (experiments)
@@ -620,15 +627,20 @@ void free_activations(tfk_engine* e, bool async = false) {
   e->cap = 0;
 }
 
-// synchronous allocations of create (small, once)
+// synchronous allocations of create and of a first use (small, once).  hipMemset of device memory only ENQUEUES the fill on the
+// null stream, and the engine's streams are non-blocking: without the wait the zeros could land after a kernel enqueued later
+// had written the buffer -- the per-segment batch-norm statistics of an engine's FIRST stacked pass (seg_stats) were zeroed
+// under its backward pass now and then, which then saw rstd = 0 and returned zero gradients for the layers below.
 int alloc_zero(float** p, size_t floats) {
   HIPCHK(hipMalloc((void**)p, floats * sizeof(float)));
   HIPCHK(hipMemset(*p, 0, floats * sizeof(float)));
+  HIPCHK(hipStreamSynchronize(nullptr));
   return 0;
 }
 int alloc_zero_b(bf16_t** p, size_t elems) {
   HIPCHK(hipMalloc((void**)p, elems * sizeof(bf16_t)));
   HIPCHK(hipMemset(*p, 0, elems * sizeof(bf16_t)));
+  HIPCHK(hipStreamSynchronize(nullptr));
   return 0;
 }
 // stream-ordered, zero-filled
@@ -658,7 +670,7 @@ int reserve(tfk_engine* e, int T) {
     //  hold a NaN bit pattern would poison dW = X^T dZ although its dZ row is zero -- pinned pages are not cleared by the driver)
     memset(e->hX[s], 0, (size_t)cap * e->F * sizeof(float));
     HIPCHK(hipHostMalloc((void**)&e->hY[s], (size_t)cap * sizeof(int32_t), hipHostMallocDefault));
-    // raw frames: at most F columns (context 0); one utterance per frame at worst
+    // raw frames: at most F columns (context 0); at most `cap` utterances (stage_pass reserves for max(rows, utterances))
     CHK(grow_zero(e, &e->dRaw[s], (size_t)cap * e->ldF));
     // utterance offsets [U + 1]; stacked passes add the utterances' output rows [U] and the row_vend table [cap / 64 + 1]
     CHK(dev_alloc(e, (void**)&e->dSeg[s], seg_ints(cap) * sizeof(int32_t), false));
@@ -775,7 +787,6 @@ int stage_raw(tfk_engine* e, const float* raw, int64_t ldraw, const int32_t* y, 
   const int D = e->F / win;
   if (ldraw < D) return fail(-1, "ldraw %lld < raw dimension %d", (long long)ldraw, D);
   if (U <= 0 || !utt_len) return fail(-1, "no utterances");
-  if (U > T) return fail(-1, "more utterances (%d) than frames (%d)", U, T);
   long total = 0;
   for (int u = 0; u < U; ++u) {
     if (utt_len[u] < 0) return fail(-1, "negative utterance length");
@@ -1183,9 +1194,27 @@ int settle_scalars(tfk_engine* e) {
 int read_scalars(tfk_engine* e) {
   CHK(settle_scalars(e));
   HIPCHK(hipMemcpyAsync(e->h_scalars, e->p_scalars(), 4 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (e->stash_live) {
+    // the evaluation ran inside a training step: the step's own sums come back (stream order: behind the read above)
+    HIPCHK(hipMemcpyAsync(e->p_scalars(), e->scalar_stash, 4 * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  }
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->scalars_fresh = true;  // init_loss / init_num_frames
+  if (e->stash_live) {
+    e->stash_live = false;
+    e->scalars_fresh = false;
+  } else {
+    e->scalars_fresh = true;  // init_loss / init_num_frames
+    e->step_open = false;
+  }
   return check_kernel_errors(e);
+}
+// before the loss of an evaluation pass is added: set the sums of an open training step aside (see step_open)
+int stash_scalars(tfk_engine* e) {
+  if (!e->step_open || e->scalars_fresh || e->stash_live) return 0;
+  HIPCHK(hipMemcpyAsync(e->scalar_stash, e->p_scalars(), 4 * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  e->stash_live = true;
+  e->scalars_fresh = true;  // the evaluation's first loss sum overwrites
+  return 0;
 }
 
 struct TensorRef {
@@ -1322,7 +1351,7 @@ int create_impl(const tfk_config* cfg, void* state, size_t state_bytes, void* st
   for (int l = 0; l < e->L; ++l) {
     if (alloc_zero(&e->mean[l], (size_t)e->ldH) || alloc_zero(&e->rstd[l], (size_t)e->ldH)) return bail(-1);
   }
-  if (alloc_zero(&e->prior, (size_t)e->ldO)) return bail(-1);
+  if (alloc_zero(&e->prior, (size_t)e->ldO) || alloc_zero(&e->scalar_stash, 4)) return bail(-1);
   if (e->bf16) {
     // shadow: mirrors the fp32 arena element for element inside the state arena when every leading dimension is a
     // multiple of 8 (the optimiser then writes it with the update and the sharded exchange gathers it), else packed
@@ -1474,6 +1503,7 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   }
   {
     ProfScope ps(e, KF_LOSS_REDUCE, 0, 4.0 * c.U);
+    if (!train) CHK(stash_scalars(e));
     ctc_loss_reduce(e->stream, e->ctc_utt_loss, e->ctc_lab_off, c.U, e->p_scalars(), e->scalars_fresh);
     e->scalars_fresh = false;
   }
@@ -1607,7 +1637,8 @@ int stage_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int
                Stack* st = nullptr, const int32_t* seg_utts = nullptr, Tables tables = Tables()) {
   HIPCHK(hipSetDevice(e->cfg.device));
   p->T = st ? st->T_pad : T;
-  CHK(reserve(e, p->T));
+  // (raw: the utterance tables of the input slots are sized by the rows -- empty utterances can outnumber the frames)
+  CHK(reserve(e, raw ? std::max(p->T, (int)raw->U) : p->T));
   CHK(tables());
   p->slot_before = e->slot;
   if (raw) CHK(stage_raw(e, X, ldx, y, T, raw->utt_len, raw->U, raw->context, raw->cmvn, &p->Xd, &p->ld, &p->yd,
@@ -1635,6 +1666,7 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
   // (a call that failed between the fused loss / column-sum launch and its backward pass must not leave the flag behind for a
   // later micro-batch -- a CTC one has no fused column sums: round-5 advisor finding)
   e->colsum_done = false;
+  if (train) e->step_open = true;
   T = p.T;
   // train mode evaluates every hidden layer when BN is on: the UPDATE_OPS of all batch-norm layers are
   // fetched by update_gradients_op (trainer.py:164-169) even for layers the tf.case does not select.
@@ -1659,6 +1691,7 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
                     e->scalars_fresh, st ? st->T_valid : -1, st ? st->k : 1);
         e->colsum_done = true;
       } else {
+        CHK(stash_scalars(e));  // (as late as this: a call that failed before its loss was added must leave the sums alone)
         loss_reduce(e->stream, e->row_loss, T, e->p_scalars(), e->scalars_fresh);
       }
       e->scalars_fresh = false;
@@ -1875,6 +1908,7 @@ int tfk_destroy(tfk_engine* e) {
     if (e->ctc_staged[k]) hipEventDestroy(e->ctc_staged[k]);
   }
   if (e->h_scalars) hipHostFree(e->h_scalars);
+  if (e->scalar_stash) hipFree(e->scalar_stash);
   if (e->h_post) hipHostFree(e->h_post);
   if (e->own_state && e->state) hipFree(e->state);
   for (int s = 0; s < 2; ++s) {
@@ -2203,6 +2237,7 @@ int apply_end(tfk_engine* e, float* average_loss) {
   e->steps_seen = e->steps_begun;  // (step_finish runs behind every micro-batch of the step: their input slots are free)
   e->grads_fresh = true;
   e->scalars_fresh = true;  // init_loss / init_num_frames (trainer.py:350-352) without a memset
+  e->step_open = e->stash_live = false;
   if (check_kernel_errors(e)) {
     if (average_loss) *average_loss = NAN;
     return -1;
@@ -2986,6 +3021,7 @@ int tfk_zero_accumulators(tfk_engine* e) {
   HIPCHK(hipMemsetAsync(e->p_grad(), 0, e->reduce_floats * sizeof(float), e->stream));
   e->grads_fresh = false;  // physically zero now
   e->scalars_fresh = false;
+  e->step_open = e->stash_live = false;
   return 0;
 }
 int tfk_set_bucket_callback(tfk_engine* e, tfk_bucket_fn fn, void* user) {
