@@ -150,16 +150,3 @@ def test_random_significands_and_adversarial_operands(gpu):
     for T, d_in, d_out in [(1024, 2048, 2048), (1000, 2050, 2010)]:
         _check_pair(gpu, bits(T, d_out), bits(d_in, d_out), bits(T, d_in), label="random significands")
         _check_pair(gpu, spread(T, d_out), spread(d_in, d_out), spread(T, d_in), label="wide exponents")
-
-
-@pytest.mark.parametrize("waves", ["4", "44"])
-def test_the_other_block_forms(gpu, waves):
-    """TFK_BF16X3_WAVES = 4 (four waves of 64x64: chained lists like the default) and 44 (four multiplying + four loader waves: one
-    tile per block) go through the same dma_tile: the shape and accumulate cases again, each form in a process of its own (the
-    switch is read once)"""
-    import subprocess
-    env = dict(os.environ, TFK_BF16X3_WAVES=waves)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-k", "tile_lists or twice"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-1500:]
-    assert " passed" in r.stdout and "failed" not in r.stdout

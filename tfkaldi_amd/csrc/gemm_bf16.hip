@@ -463,39 +463,6 @@ struct Frag3 {
   }
 };
 
-// The same for the 16x16x32 MFMA shape (TFK_X3_M16, x3_layout.h): plane q of NF16 fragments of 16 rows (columns), all 32 k of a slot.
-// k-contiguous: one offset register; k-strided: four (parity of X = 3 * unit + plane, parity of the fragment inside its unit).
-template <bool KC, int EXT, int NF16>
-struct Frag3M {
-  int off[KC ? 1 : 4];
-  __device__ __forceinline__ void init(int lane, int frag0) {
-    if constexpr (KC) {
-      off[0] = x3::kc16_lane_off(lane, frag0);
-    } else {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) off[v] = x3::ks16_lane_off<EXT>(lane, frag0, v & 1, v >> 1);
-    }
-  }
-  __device__ __forceinline__ Frag3M at(int bytes) const {
-    Frag3M r;
-#pragma unroll
-    for (int v = 0; v < (KC ? 1 : 4); ++v) r.off[v] = off[v] + bytes;
-    return r;
-  }
-  __device__ __forceinline__ bf16x8 read(const char* img, int f, int pl) const {
-    if constexpr (KC) {
-      return *reinterpret_cast<const bf16x8*>(img + off[0] + x3::kc16_imm(f, pl));
-    } else {
-      typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-      const int X = 3 * (f >> 1) + pl;
-      const char* q = img + off[(X & 1) + 2 * (f & 1)];
-      const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(q + x3::ks16_imm<EXT>(X, 0)));
-      const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(q + x3::ks16_imm<EXT>(X, 1)));
-      return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-  }
-};
-
 // TFKB_ABL (tools/gemm_bf16_ablate.hip only): timing-only variants of the DMA kernel with pieces of the K loop removed
 // -- 1 MFMAs, 2 LDS-DMA pieces, 4 fragment reads.  Results are wrong by construction.
 #ifndef TFKB_ABL
@@ -520,24 +487,18 @@ struct Frag3M {
 // fp32 value exactly; a ring slot holds all six plane tiles of a 32-k step, and each 16-k MFMA step multiplies the six plane
 // pairs of order <= 2^-16 -- (3,1) (2,2) (1,3) (2,1) (1,2) (1,1), smallest first -- into the SAME fp32 accumulators.
 // KSPLIT = 2 (NPL == 3 only): two blocks per tile, each over half of K; see gemm_bf16x3_splitk_floats (gemm_bf16.h)
+// DUAL (NPL == 3, KSPLIT == 1): a block of the dual launch (gemm_bf16x3_dual_kernel) -- C goes through a buffer resource
+// (epilogue<>, CBUF); 1 = one tile, 2 = a LIST: `ntiles` consecutive tiles from position seq0 of the grouped tile sequence, see
+// the loop over `ti`
 constexpr int kSplitFlagWords = 4096;  // head of the split-K workspace: {ticket, ready} per tile, from word kSplitXccWord on the
                                       // {XCD + 1 of the block of K half 0, of K half 1} per tile; then the partial sums
 constexpr int kSplitXccWord = 2048;
-// LOADERS (NPL == 3 only; 0 or WAVES_M * WAVES_N): that many EXTRA waves behind the multiplying ones do nothing but issue the
-// LDS-DMA pieces ("wave specialisation").  A wave issues in order, and `buffer_load ... lds` sits in the vector-memory issue
-// queue for as long as the fill path is busy (it is: the fill of a slot takes about as long as its MFMAs) -- in a wave that also
-// multiplies, every one of the twelve pieces per slot is a bubble in the matrix pipe: MFMAs + fragment reads alone 34 us, with
-// the pieces 47 (profiles/r04_gemm_f32x3_ablation.txt), i.e. fill and MFMA time ADD UP although neither saturates the CU.  With
-// a loader wave next to every multiplying wave on its SIMD the stalls hit a wave that has nothing else to do; the multiplying
-// waves' stream is fragment reads and MFMAs only.  Loaders and multipliers meet at the per-slot barrier (the loader arrives
-// once its own pieces of the NEXT tile have landed); after the K loop the loaders end -- a barrier counts surviving waves only,
-// so the epilogue's barriers are the multipliers' own.
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
-          int NPL = 1, int KSPLIT = 1, int LOADERS = 0, bool LIST = false, bool CBUF = false>
+          int NPL = 1, int KSPLIT = 1, int DUAL = 0>
 __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int tiles_n, int group_rows, int bid, char* smem,
                                          int seq0 = 0, int ntiles = 1) {
-  static_assert(LOADERS == 0 || (NPL == 3 && LOADERS == WAVES_M * WAVES_N), "loader waves: one per multiplying wave, x3 only");
-  static_assert(!LIST || (NPL == 3 && KSPLIT == 1 && LOADERS == 0), "tile lists: the unsplit fp32-emulating contraction, no loader waves");
+  static_assert(DUAL == 0 || (NPL == 3 && KSPLIT == 1), "the dual launch: the unsplit fp32-emulating contraction");
+  constexpr bool LIST = DUAL == 2, CBUF = DUAL != 0;
   constexpr int NTH = WAVES_M * WAVES_N * 64;
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
   // (NPL == 3: one image per operand holds its three planes, x3_layout.h)
@@ -591,44 +552,10 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   const int a_klim = min(A_KC ? K8 : p.K, k_end), b_klim = min(B_KC ? K8 : p.K, k_end);
   // tiles [0, nk_full) of this block lie wholly below both operands' k limits
   const int nk_full = min(a_klim, b_klim) / BKT - kbase;
-  if constexpr (LOADERS > 0) {
-    if (wave >= WAVES_M * WAVES_N) {
-      // ---- a loader wave: tile t + NS - 1 goes out right behind barrier t - 1 (its slot's last reader has every fragment of
-      // tile t - 1 in registers by then), and barrier t is entered once this wave's pieces of tile t + 1 have landed ----
-      const int lwave = wave - WAVES_M * WAVES_N;
-      la.init(p.A, p.lda, A_KC ? p.M : p.K, m0, A_KC ? p.M : ((p.M + 7) & ~7), a_klim, tid - NTH);
-      lb.init(p.B, p.ldb, B_KC ? p.N : p.K, n0, B_KC ? p.N : ((p.N + 7) & ~7), b_klim, tid - NTH);
-      auto tile = [&](auto guard, int slot, int kt) {
-        if (TFKB_ABL & 2) return;
-#pragma unroll
-        for (int j = 0; j < NPA; ++j)
-          la.template issue<decltype(guard)::value>(j, lds0 + (unsigned)(slot * STAGE), (kt + kbase) * BKT, lwave);
-#pragma unroll
-        for (int j = 0; j < NPB; ++j)
-          lb.template issue<decltype(guard)::value>(j, lds0 + (unsigned)(slot * STAGE + NPL * A_BYTES), (kt + kbase) * BKT, lwave);
-      };
-#pragma unroll
-      for (int t = 0; t < NS - 1; ++t) tile(std::true_type(), t, t);
-      TFKB_WAIT_BARRIER((NS - 2) * NP);
-      int ws = NS - 1;
-      const int n_fast = max(0, min(nk, nk_full - (NS - 1)));
-#pragma unroll 1
-      for (int kt = 0; kt < nk; ++kt) {
-        if (kt < n_fast) tile(std::false_type(), ws, kt + NS - 1);
-        else tile(std::true_type(), ws, kt + NS - 1);
-        TFKB_WAIT_BARRIER((NS - 2) * NP);
-        ws = ws + 1 == NS ? 0 : ws + 1;
-      }
-      TFKB_WAIT_BARRIER(0);
-      return;
-    }
-  }
   // the loaders' per-lane offsets for the tile at (m0, n0)
   auto init_loaders = [&]() {
-    if constexpr (LOADERS == 0) {
-      la.init(p.A, p.lda, A_KC ? p.M : p.K, m0, A_KC ? p.M : ((p.M + 7) & ~7), a_klim, tid);
-      lb.init(p.B, p.ldb, B_KC ? p.N : p.K, n0, B_KC ? p.N : ((p.N + 7) & ~7), b_klim, tid);
-    }
+    la.init(p.A, p.lda, A_KC ? p.M : p.K, m0, A_KC ? p.M : ((p.M + 7) & ~7), a_klim, tid);
+    lb.init(p.B, p.ldb, B_KC ? p.N : p.K, n0, B_KC ? p.N : ((p.N + 7) & ~7), b_klim, tid);
   };
   init_loaders();
   typename std::conditional<NPL == 3, Frag3<A_KC, BM, FM>, Frag<A_KC, BM, FM, BKT>>::type qa;
@@ -659,9 +586,7 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   //  knows the tile lies inside it, see DmaOperand3::issue)
   auto piece_g = [&](auto guard, int j, int slot, int kt) {
     if (TFKB_ABL & 2) return;
-    if constexpr (LOADERS > 0) {
-      return;  // (the loader waves issue every piece)
-    } else if constexpr (NPL == 3) {
+    if constexpr (NPL == 3) {
       if (j < NPA)
         la.template issue<decltype(guard)::value>(j, lds0 + (unsigned)(slot * STAGE), (kt + kbase) * BKT, wave);
       else
@@ -770,7 +695,7 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
   // number of pieces is issued between any two barriers).  The tile's epilogue then runs with the next tile's pieces landing,
   // its stores are waited for no earlier than at the next tile's first barrier, and `red` lies behind the ring.  A tile of fewer
   // than NS ring tiles, or a block form without the chain, drains the ring and starts the next tile from its prologue.
-  constexpr bool CHAIN = LIST && NPL == 3 && TFK_X3_M16 == 0 && SCHED == 0;
+  constexpr bool CHAIN = LIST && NPL == 3 && SCHED == 0;
   const int nlist = LIST ? ntiles : 1;
   float* const red = reinterpret_cast<float*>(smem + (LIST ? NS * STAGE : 0));
   bool primed = false;  // the ring holds this tile's first ring tiles and fa[0] / fb[0] its first fragments
@@ -837,116 +762,6 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_barrier" : : : "memory");
         __builtin_amdgcn_sched_barrier(0);
-      }
-    } else if constexpr (NPL == 3 && TFK_X3_M16 != 0) {
-      // The 16x16x32 shape: a ring slot is ONE 32-k step of six plane products x FM16 x FN16 MFMAs.  The products run (0,0) (0,1)
-      // (0,2) | barrier | (1,0) (1,1) (2,0): every fragment register is read for the last time as early as possible, so one set of
-      // fragments (+ a second B plane 0) serves -- A1 and A2 of this slot are fetched under the first half, A0, B0, B2, B1 of the
-      // NEXT slot under the second, each into registers whose last use lies behind it.  The barrier sits where it sat (round 3):
-      // every read of this slot has been issued in front of it, the next slot's data is complete behind it.
-      static_assert(KSPT == 2, "fp32-emulating contraction: 32 k per ring slot");
-      constexpr int FM16 = 2 * FM, FN16 = 2 * FN;
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
-      Frag3M<A_KC, BM, FM16> ma;
-      Frag3M<B_KC, BN, FN16> mb;
-      ma.init(lane, wm * FM16);
-      mb.init(lane, wn * FN16);
-      f32x4 c1[FM16][FN16], c2[FM16][FN16];
-#pragma unroll
-      for (int a = 0; a < FM16; ++a)
-#pragma unroll
-        for (int b = 0; b < FN16; ++b) {
-          c1[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-          c2[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      bf16x8 ga[3][FM16], gb[3][FN16], gb0n[FN16];
-      auto rd_a = [&](const decltype(ma)& r, int pl) {
-#pragma unroll
-        for (int a = 0; a < FM16; ++a) ga[pl][a] = r.read(smem, a, pl);
-      };
-      auto rd_b = [&](const decltype(mb)& r, int pl, bf16x8 (&dst)[FN16]) {
-#pragma unroll
-        for (int b = 0; b < FN16; ++b) dst[b] = r.read(smem, b, pl);
-      };
-      auto mm = [&](int pa, int pb) {
-#pragma unroll
-        for (int a = 0; a < FM16; ++a)
-#pragma unroll
-          for (int b = 0; b < FN16; ++b) {
-            if (pa + pb == 0) c1[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[0][a], gb[0][b], c1[a][b], 0, 0, 0);
-            else c2[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ga[pa][a], gb[pb][b], c2[a][b], 0, 0, 0);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      // third `part` of the pieces [j0, j1) of tile `tile` into slot `slot`
-      auto pieces = [&](auto guard, int part, int j0, int j1, int slot, int tile) {
-#pragma unroll
-        for (int j = j0 + part * (j1 - j0) / 3; j < j0 + (part + 1) * (j1 - j0) / 3; ++j) piece_g(guard, j, slot, tile);
-      };
-      {
-        const auto r0a = ma.at(0);
-        const auto r0b = mb.at(NPL * A_BYTES);
-        rd_a(r0a, 0);
-        rd_b(r0b, 0, gb[0]);
-        rd_b(r0b, 1, gb[1]);
-        rd_b(r0b, 2, gb[2]);
-      }
-      const int n_fast = max(0, min(nk, nk_full - NS));
-      auto iteration = [&](auto guard, int kt) {
-        const auto ra = ma.at(rs * STAGE);
-        rd_a(ra, 1);
-        pieces(guard, 0, NPH, NP, ws, kt + NS - 1);
-        mm(0, 0);
-        rd_a(ra, 2);
-        pieces(guard, 1, NPH, NP, ws, kt + NS - 1);
-        mm(0, 1);
-        pieces(guard, 2, NPH, NP, ws, kt + NS - 1);
-        mm(0, 2);
-        TFKB_WAIT_BARRIER((NS - 2) * NP);
-        rs = rs + 1 == NS ? 0 : rs + 1;
-        ws = ws + 1 == NS ? 0 : ws + 1;
-        const bool fetch = kt + 1 < nk;
-        const auto na = ma.at(rs * STAGE);
-        const auto nb = mb.at(rs * STAGE + NPL * A_BYTES);
-        if (fetch) {
-          rd_a(na, 0);
-          rd_b(nb, 0, gb0n);
-        }
-        pieces(guard, 0, 0, NPH, ws, kt + NS);
-        mm(1, 0);
-        if (fetch) rd_b(nb, 2, gb[2]);
-        pieces(guard, 1, 0, NPH, ws, kt + NS);
-        mm(1, 1);
-        if (fetch) rd_b(nb, 1, gb[1]);
-        pieces(guard, 2, 0, NPH, ws, kt + NS);
-        mm(2, 0);
-        if (fetch) {
-#pragma unroll
-          for (int b = 0; b < FN16; ++b) gb[0][b] = gb0n[b];
-        }
-      };
-#pragma unroll 1
-      for (int kt = 0; kt < n_fast; ++kt) iteration(std::false_type(), kt);
-#pragma unroll 1
-      for (int kt = n_fast; kt < nk; ++kt) iteration(std::true_type(), kt);
-      // the 16x16 result tiles -> the 32x32 register layout the epilogues are written for: reg r of lane (i, h) is row
-      // 4 h + (r & 3) + 8 (r >> 2), column i of a 32x32 fragment; 16x16 tile (p, q) of it holds row 16 p + 4 (l >> 4) + s, column
-      // 16 q + (l & 15) in reg s of lane l.  One ds_bpermute per (register, column half), once per block.
-      {
-        const int src = (16 * h + (i & 15)) * 4;  // + 128 for the registers with (r >> 2) & 1
-#pragma unroll
-        for (int a = 0; a < FM; ++a)
-#pragma unroll
-          for (int b = 0; b < FN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int addr = src + (((r >> 2) & 1) ? 128 : 0);
-              const f32x4& t0 = c1[2 * a + (r >> 3)][2 * b], &u0 = c2[2 * a + (r >> 3)][2 * b];
-              const f32x4& t1 = c1[2 * a + (r >> 3)][2 * b + 1], &u1 = c2[2 * a + (r >> 3)][2 * b + 1];
-              const float v0 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t0[r & 3] + u0[r & 3])));
-              const float v1 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, t1[r & 3] + u1[r & 3])));
-              acc[a][b][r] = (i & 16) ? v1 : v0;
-            }
       }
     } else if constexpr (NPL == 3) {
       // One wave per SIMD, and per 16-k step 6 * FM * FN MFMAs for 3 * (FM + FN) fragment reads and a handful of LDS-DMA pieces:
@@ -1164,12 +979,11 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
 }
 
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
-          int NPL = 1, int KSPLIT = 1, int LOADERS = 0>
-__global__ void __launch_bounds__((WAVES_M * WAVES_N + LOADERS) * 64)
+          int NPL = 1, int KSPLIT = 1>
+__global__ void __launch_bounds__(WAVES_M * WAVES_N * 64)
 gemm_bf16_dma_kernel(GemmArgsB p, int tiles_m, int tiles_n, int group_rows) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  dma_tile<A_KC, B_KC, EPI, WAVES_M, WAVES_N, FM, FN, NS, BKT, SCHED, NPL, KSPLIT, LOADERS>(p, tiles_m, tiles_n, group_rows,
-                                                                                            blockIdx.x, smem);
+  dma_tile<A_KC, B_KC, EPI, WAVES_M, WAVES_N, FM, FN, NS, BKT, SCHED, NPL, KSPLIT>(p, tiles_m, tiles_n, group_rows, blockIdx.x, smem);
 }
 
 // Two INDEPENDENT contractions in one launch -- backward: dA = dZ . W^T (NT, optionally EPI_DACT) of a layer and the
@@ -1382,14 +1196,12 @@ gemm_bf16_kernel(GemmArgsB p, int tiles_m, int tiles_n, int group_rows) {
 // The dual launch of the fp32-emulating contraction: dA (NT) and dW (TN) of a layer on 128x128 blocks in ONE launch.  At 1024
 // frames dA alone has 128 tiles for 256 CUs (which is why gemm_bf16x3 splits its K in two) and dW 256; together every CU runs one
 // dA tile (64 ring tiles) or two dW tiles (32 each): no partial-sum exchange, one ramp and one tail instead of two.
-// WN: waves along n -- 2 (four waves of 64x64), 4 (EIGHT waves of 64x32, two per SIMD) or 0 (four waves of 64x64 + four loader
-// waves): see launch_x3
+// Every block is EIGHT waves of 64x32, two per SIMD (the form launch_x3 runs on 128x128 blocks).
 // per: tiles per block of the problem with the SHORTER K (x3_layout.h: dual_tiles_per_block) -- at 1024 frames 128 dA blocks of
 // 64 ring tiles and 128 blocks of two dW tiles (2 x 32), one block per CU, the ring running on from a block's first tile into
-// its second (dma_tile: LIST).  The form with loader waves keeps one tile per block (per = 1: its loader waves end with the K
-// loop).
-template <int EPI_NT, int EPI_TN, int WN>
-__global__ void __launch_bounds__(WN == 2 ? 256 : 512)
+// its second (dma_tile: LIST).
+template <int EPI_NT, int EPI_TN>
+__global__ void __launch_bounds__(512)
 gemm_bf16x3_dual_kernel(GemmArgsB p1, GemmArgsB p2, int tiles_m1, int tiles_n1, int group1, int tiles_m2, int tiles_n2, int group2,
                         int tn_first, int per) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1397,25 +1209,19 @@ gemm_bf16x3_dual_kernel(GemmArgsB p1, GemmArgsB p2, int tiles_m1, int tiles_n1, 
   // of 8192 rows): the short ones fill the tail
   const int n1 = tiles_m1 * tiles_n1, n2 = tiles_m2 * tiles_n2;
   const int b = blockIdx.x;
-  constexpr bool LIST = WN != 0;
-  constexpr int WNN = WN ? WN : 2, FNN = WN ? 4 / WN : 2, LD = WN ? 0 : 4;
   const int n_long = tn_first ? n2 : n1;
   if (b < n_long) {  // one tile of the long problem
-    if (tn_first) dma_tile<false, false, EPI_TN, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, false, true>(p2, tiles_m2, tiles_n2, group2, b, smem);
-    else dma_tile<true, true, EPI_NT, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, false, true>(p1, tiles_m1, tiles_n1, group1, b, smem);
+    if (tn_first) dma_tile<false, false, EPI_TN, 2, 4, 2, 1, 3, 32, 0, 3, 1, 1>(p2, tiles_m2, tiles_n2, group2, b, smem);
+    else dma_tile<true, true, EPI_NT, 2, 4, 2, 1, 3, 32, 0, 3, 1, 1>(p1, tiles_m1, tiles_n1, group1, b, smem);
     return;
   }
-  int seq0 = 0, count = 1;
-  if constexpr (LIST) {
-    x3::dual_block_tiles(tn_first ? n1 : n2, per, b - n_long, seq0, count);
-    if (count == 0) return;
-  }
+  int seq0, count;
+  x3::dual_block_tiles(tn_first ? n1 : n2, per, b - n_long, seq0, count);
+  if (count == 0) return;
   if (tn_first)
-    dma_tile<true, true, EPI_NT, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, LIST, true>(p1, tiles_m1, tiles_n1, group1, b - n_long, smem, seq0,
-                                                                                 count);
+    dma_tile<true, true, EPI_NT, 2, 4, 2, 1, 3, 32, 0, 3, 1, 2>(p1, tiles_m1, tiles_n1, group1, b - n_long, smem, seq0, count);
   else
-    dma_tile<false, false, EPI_TN, 2, WNN, 2, FNN, 3, 32, 0, 3, 1, LD, LIST, true>(p2, tiles_m2, tiles_n2, group2, b - n_long, smem, seq0,
-                                                                                  count);
+    dma_tile<false, false, EPI_TN, 2, 4, 2, 1, 3, 32, 0, 3, 1, 2>(p2, tiles_m2, tiles_n2, group2, b - n_long, smem, seq0, count);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -1427,17 +1233,8 @@ const CfgB kCfgB[kNumGemmBf16Configs] = {{64, 64}, {128, 64}, {128, 128}, {128, 
 int g_forced_b = -2;  // -2: env not read yet; -1: heuristic
 int g_group_rows = 0;  // env TFK_BF16_GROUP_ROWS (experiments): tile rows per XCD patch; 0 = balanced, large = column-major
 
-template <class Kern>
-int launch_grid(Kern kern, const GemmArgsB& p, int bm, int bn, int threads, size_t lds, hipStream_t stream, bool* attr_done,
-                int blocks_per_tile = 1) {
-  const int tiles_m = (p.M + bm - 1) / bm, tiles_n = (p.N + bn - 1) / bn;
-  if (!*attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    *attr_done = true;
-  }
-  // tile rows per XCD patch: ~sqrt(tiles per XCD * BN / BM) makes the patch square in bytes
+// tile rows per XCD patch: ~sqrt(tiles per XCD * BN / BM) makes the patch square in bytes
+int pick_group_rows(int tiles_m, int tiles_n, int bm, int bn) {
   int group_rows = g_group_rows;
   if (group_rows <= 0) {
     const double per_xcd = (double)tiles_m * tiles_n / NUM_XCD;
@@ -1445,30 +1242,91 @@ int launch_grid(Kern kern, const GemmArgsB& p, int bm, int bn, int threads, size
   }
   if (group_rows < 1) group_rows = 1;
   if (group_rows > tiles_m) group_rows = tiles_m;
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n * blocks_per_tile), dim3(threads), lds, stream, p, tiles_m, tiles_n, group_rows);
+  return group_rows;
+}
+
+// Every kernel here takes its LDS as dynamic shared memory beyond the 64 KB a launch may ask for unprepared: the limit of kernel
+// KERN is raised once, in front of its first launch.  Returns hipError_t as int.
+template <auto KERN>
+int allow_full_lds() {
+  static bool done = false;
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    done = true;
+  }
+  return 0;
+}
+
+template <auto KERN>
+int launch_grid(const GemmArgsB& p, int bm, int bn, int threads, size_t lds, hipStream_t stream, int blocks_per_tile = 1) {
+  const int tiles_m = (p.M + bm - 1) / bm, tiles_n = (p.N + bn - 1) / bn;
+  if (int e = allow_full_lds<KERN>()) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_m * tiles_n * blocks_per_tile), dim3(threads), lds, stream, p, tiles_m, tiles_n,
+                     pick_group_rows(tiles_m, tiles_n, bm, bn));
   return (int)hipGetLastError();
+}
+
+// The run-time (layout, epilogue) of a call as compile-time constants: f(A_KC, B_KC, EPI), each a std::integral_constant, for
+// the combinations the kernels are built for -- anything else is an invalid argument.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+int with_layout_epi(GemmLayout layout, int epi, F f) {
+  constexpr std::true_type kc;    // operand k-contiguous in memory
+  constexpr std::false_type ks;   // k-strided
+  switch (layout) {
+    case GEMM_NN:
+      switch (epi) {
+        case 0: return f(kc, ks, Int<0>());
+        case EPI_BIAS: return f(kc, ks, Int<EPI_BIAS>());
+        case EPI_BIAS | EPI_COLSTATS: return f(kc, ks, Int<EPI_BIAS | EPI_COLSTATS>());
+        case EPI_BIAS | EPI_EVAL_ACT: return f(kc, ks, Int<EPI_BIAS | EPI_EVAL_ACT>());
+      }
+      break;
+    case GEMM_NT:
+      if (epi == 0) return f(kc, kc, Int<0>());
+      if (epi == EPI_DACT) return f(kc, kc, Int<EPI_DACT>());
+      break;
+    case GEMM_TN:
+      if (epi == 0) return f(ks, ks, Int<0>());
+      if (epi == EPI_ACCUM) return f(ks, ks, Int<EPI_ACCUM>());
+      break;
+  }
+  return (int)hipErrorInvalidValue;
+}
+// The same for the pair of a dual launch: f(EPI_NT, EPI_TN); the callers have checked that nt.epi is 0 or EPI_DACT and tn.epi 0
+// or EPI_ACCUM.
+template <class F>
+int with_dual_epi(const GemmArgsB& nt, const GemmArgsB& tn, F f) {
+  const int key = (nt.epi == EPI_DACT ? 2 : 0) + (tn.epi == EPI_ACCUM ? 1 : 0);
+  switch (key) {
+    case 0: return f(Int<0>(), Int<0>());
+    case 1: return f(Int<0>(), Int<EPI_ACCUM>());
+    case 2: return f(Int<EPI_DACT>(), Int<0>());
+    default: return f(Int<EPI_DACT>(), Int<EPI_ACCUM>());
+  }
 }
 
 template <bool A_KC, bool B_KC, int EPI, int FM, int FN>
 int launch_reg(const GemmArgsB& p, hipStream_t stream) {
   constexpr int BM = 64 * FM, BN = 64 * FN;
   const size_t lds = (size_t)3 * (Operand<A_KC, BM>::SZ + Operand<B_KC, BN>::SZ) * sizeof(bf16_t);
-  static bool attr_done = false;
-  return launch_grid(&gemm_bf16_kernel<A_KC, B_KC, EPI, FM, FN>, p, BM, BN, NT, lds, stream, &attr_done);
+  return launch_grid<&gemm_bf16_kernel<A_KC, B_KC, EPI, FM, FN>>(p, BM, BN, NT, lds, stream);
 }
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
-          int NPL = 1, int KSPLIT = 1, int LOADERS = 0>
+          int NPL = 1, int KSPLIT = 1>
 int launch_dma(const GemmArgsB& p, hipStream_t stream) {
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
   const size_t lds = (size_t)NS * NPL * (BM + BN) * BKT * 2;
   static_assert((size_t)NS * NPL * (BM + BN) * BKT * 2 <= 160 * 1024, "LDS");
-  static bool attr_done = false;
-  return launch_grid(&gemm_bf16_dma_kernel<A_KC, B_KC, EPI, WAVES_M, WAVES_N, FM, FN, NS, BKT, SCHED, NPL, KSPLIT, LOADERS>, p,
-                     BM, BN, (WAVES_M * WAVES_N + LOADERS) * 64, lds, stream, &attr_done, KSPLIT);
+  return launch_grid<&gemm_bf16_dma_kernel<A_KC, B_KC, EPI, WAVES_M, WAVES_N, FM, FN, NS, BKT, SCHED, NPL, KSPLIT>>(
+      p, BM, BN, WAVES_M * WAVES_N * 64, lds, stream, KSPLIT);
 }
 
 // fp32-emulating contraction on three bf16 planes per operand: 128x128 blocks (three 48 KB slots) when the result has a
-// tile of it for nearly every CU, else 128x64 (four 36 KB slots); 32 k per slot, four waves
+// tile of it for nearly every CU -- eight waves of 64x32, two instruction streams per SIMD -- else 128x64 (four 36 KB slots,
+// four waves); 32 k per slot
 int g_x3_cfg = -2;  // env TFK_BF16X3_CFG (experiments): 0 = 128x64, 1 = 128x128, 2 = split-K where eligible, 3 = 64x64 (TN), -1 heuristic
 int x3_cfg() {
   if (g_x3_cfg == -2) {
@@ -1488,24 +1346,6 @@ bool x3_split_shape(bool tn, int M, int N, int K) {
 bool x3_split_shape_tn(int M, int N, int K) {
   const long m128 = (M + 127) / 128, tiles128 = m128 * ((N + 127) / 128), tiles64 = m128 * ((N + 63) / 64);
   return tiles128 < 100 && tiles64 >= 64 && tiles64 < 200 && tiles64 % NUM_XCD == 0 && 2 * tiles64 <= kSplitXccWord && K >= 512;
-}
-// Waves per 128x128 block (env TFK_BF16X3_WAVES = 8 | 4 | 44; profiles/r05_gemm_f32x3_power.txt):
-//    8  eight multiplying waves of 64x32, two instruction streams per SIMD (default);
-//    4  four multiplying waves of 64x64, one per SIMD: the fewest fragment bytes per MFMA, but every LDS-DMA piece the wave
-//       issues and every wait for a fragment is a bubble in its SIMD's matrix pipe;
-//   44  four multiplying waves + four loader waves (dma_tile: LOADERS).
-// Round 5 built all three expecting the schedule to be the limiter (MFMAs alone 36 us, fill alone 27, together 47 at
-// 1024 x 2048 x 2048) -- and they finish within 2 % of each other, because the contraction is POWER-bound: over operands of
-// zeros the same launches take 39.7 us (the pair of a layer 71 us instead of 99, 8192 frames 252 us instead of 372 = the time
-// of the MFMAs alone), i.e. fill and MFMAs DO overlap and what random significands cost is clock.  In the training step (half
-// of the activations are ReLU zeros) the eight-wave form is ahead: 1.11 ms against 1.14 (4) and 1.16 (44) at BASELINE cfg2.
-int x3_waves() {
-  static const int w = [] {
-    const char* q = getenv("TFK_BF16X3_WAVES");
-    const int v = q ? atoi(q) : 8;
-    return v == 4 || v == 44 ? v : 8;
-  }();
-  return w;
 }
 // split-K hand-over through the shared L2 when both blocks of a tile turn out to run on one XCD (env TFK_X3_HANDOVER = mem | l2).
 // Built in round 6 on the judge's suggestion (the partner IS on the same XCD for every tile of the forward contractions) and
@@ -1540,13 +1380,10 @@ int launch_x3(const GemmArgsB& p_in, hipStream_t stream) {
   p.splitk_skew = x3_kskew();
   const int forced = x3_cfg();
   const long m128 = (p.M + 127) / 128, n128 = (p.N + 127) / 128;
-  const int wv = x3_waves();
   if constexpr (A_KC) {
     if ((forced == 2 || forced < 0) && p.splitk_ws && x3_split_shape(false, p.M, p.N, p.K) &&
         p.splitk_ws_floats >= (size_t)kSplitFlagWords + (size_t)m128 * n128 * 128 * 128)
-      return wv == 8    ? launch_dma<A_KC, B_KC, EPI, 2, 4, 2, 1, 3, 32, 0, 3, 2>(p, stream)
-             : wv == 44 ? launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 2, 3, 32, 0, 3, 2, 4>(p, stream)
-                        : launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 2, 3, 32, 0, 3, 2>(p, stream);
+      return launch_dma<A_KC, B_KC, EPI, 2, 4, 2, 1, 3, 32, 0, 3, 2>(p, stream);
   } else {
     // the weight gradient of a NARROW layer (layer 0: 440 x 2048 over 1024 frames): 224 blocks of 64x64 over all of K beat 256
     // half-K blocks of 128x64 with their partial-sum exchange and their 14 % of padding rows (17.5 us against 20.8); from 2048
@@ -1558,10 +1395,7 @@ int launch_x3(const GemmArgsB& p_in, hipStream_t stream) {
       return launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 1, 4, 32, 0, 3, 2>(p, stream);
   }
   const bool big = forced >= 0 ? forced == 1 : m128 * n128 >= 200;
-  if (big)
-    return wv == 8    ? launch_dma<A_KC, B_KC, EPI, 2, 4, 2, 1, 3, 32, 0, 3>(p, stream)
-           : wv == 44 ? launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 2, 3, 32, 0, 3, 1, 4>(p, stream)
-                      : launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 2, 3, 32, 0, 3>(p, stream);
+  if (big) return launch_dma<A_KC, B_KC, EPI, 2, 4, 2, 1, 3, 32, 0, 3>(p, stream);
   return launch_dma<A_KC, B_KC, EPI, 2, 2, 2, 1, 4, 32, 0, 3>(p, stream);
 }
 
@@ -1588,32 +1422,14 @@ int launch(const GemmArgsB& p, hipStream_t stream) {
   return (int)hipErrorInvalidValue;
 }
 
-int pick_group_rows(int tiles_m, int tiles_n, int bm, int bn) {
-  // tile rows per XCD patch: ~sqrt(tiles per XCD * BN / BM) makes the patch square in bytes
-  int group_rows = g_group_rows;
-  if (group_rows <= 0) {
-    const double per_xcd = (double)tiles_m * tiles_n / NUM_XCD;
-    group_rows = (int)(sqrt(per_xcd * bn / bm) + 0.5);
-  }
-  if (group_rows < 1) group_rows = 1;
-  if (group_rows > tiles_m) group_rows = tiles_m;
-  return group_rows;
-}
-
 template <int EPI_NT, int EPI_TN, int GWM, int GWN, int GFM, int GFN, int GNS, int HWM, int HWN, int HFM, int HFN, int HNS, int HBK>
 int launch_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
   constexpr int BMA = GWM * GFM * 32, BNA = GWN * GFN * 32, BMW = HWM * HFM * 32, BNW = HWN * HFN * 32;
   constexpr size_t lds_a = (size_t)GNS * (BMA + BNA) * 128, lds_w = (size_t)HNS * (BMW + BNW) * HBK * 2;
   constexpr size_t lds = lds_a > lds_w ? lds_a : lds_w;
   static_assert(lds <= 160 * 1024, "LDS");
-  auto kern = &gemm_bf16_dual_kernel<EPI_NT, EPI_TN, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  constexpr auto kern = &gemm_bf16_dual_kernel<EPI_NT, EPI_TN, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>;
+  if (int e = allow_full_lds<kern>()) return e;
   const int tma = (a.M + BMA - 1) / BMA, tna = (a.N + BNA - 1) / BNA, tmw = (w.M + BMW - 1) / BMW, tnw = (w.N + BNW - 1) / BNW;
   hipLaunchKernelGGL(kern, dim3(tma * tna + tmw * tnw), dim3(GWM * GWN * 64), lds, stream, a, w, tma, tna,
                      pick_group_rows(tma, tna, BMA, BNA), tmw, tnw, pick_group_rows(tmw, tnw, BMW, BNW));
@@ -1622,13 +1438,9 @@ int launch_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
 
 template <int GWM, int GWN, int GFM, int GFN, int GNS, int HWM, int HWN, int HFM, int HFN, int HNS, int HBK>
 int launch_dual_epi(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
-  const int key = (a.epi == EPI_DACT ? 2 : 0) + (w.epi == EPI_ACCUM ? 1 : 0);
-  switch (key) {
-    case 0: return launch_dual<0, 0, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>(a, w, stream);
-    case 1: return launch_dual<0, EPI_ACCUM, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>(a, w, stream);
-    case 2: return launch_dual<EPI_DACT, 0, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>(a, w, stream);
-    default: return launch_dual<EPI_DACT, EPI_ACCUM, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>(a, w, stream);
-  }
+  return with_dual_epi(a, w, [&](auto e1, auto e2) {
+    return launch_dual<decltype(e1)::value, decltype(e2)::value, GWM, GWN, GFM, GFN, GNS, HWM, HWN, HFM, HFN, HNS, HBK>(a, w, stream);
+  });
 }
 
 int g_dual_cfg = -2;  // env TFK_BF16_DUAL_CFG: -1 heuristic, 0 off, 3 / 4 / 5 force that block geometry
@@ -1698,24 +1510,19 @@ size_t gemm_bf16x3_splitk_floats(GemmLayout layout, int M, int N, int K) {
 }
 
 namespace {
-template <int EPI_NT, int EPI_TN, int WN>
+template <int EPI_NT, int EPI_TN>
 int launch_x3_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
   // three ring slots + the epilogues' column-sum scratch behind them (a tile list's epilogue runs while the ring is being filled)
   constexpr size_t lds = (size_t)3 * 3 * (128 + 128) * 32 * 2 + 2 * 2 * 128 * sizeof(float);
-  auto kern = &gemm_bf16x3_dual_kernel<EPI_NT, EPI_TN, WN>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  constexpr auto kern = &gemm_bf16x3_dual_kernel<EPI_NT, EPI_TN>;
+  if (int e = allow_full_lds<kern>()) return e;
   const int tma = (a.M + 127) / 128, tna = (a.N + 127) / 128, tmw = (w.M + 127) / 128, tnw = (w.N + 127) / 128;
   const int tn_first = w.K > a.K ? 1 : 0;
   const int n_long = tn_first ? tmw * tnw : tma * tna, n_short = tn_first ? tma * tna : tmw * tnw;
   const int nk_long = ((tn_first ? w.K : a.K) + 31) / 32, nk_short = ((tn_first ? a.K : w.K) + 31) / 32;
-  const int per = WN == 0 ? 1 : x3::dual_tiles_per_block(n_long, nk_long, n_short, nk_short);
-  const int blocks = n_long + (WN == 0 ? n_short : x3::dual_short_blocks(n_short, per));
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(WN == 2 ? 256 : 512), lds, stream, a, w, tma, tna, pick_group_rows(tma, tna, 128, 128), tmw, tnw,
+  const int per = x3::dual_tiles_per_block(n_long, nk_long, n_short, nk_short);
+  const int blocks = n_long + x3::dual_short_blocks(n_short, per);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, stream, a, w, tma, tna, pick_group_rows(tma, tna, 128, 128), tmw, tnw,
                      pick_group_rows(tmw, tnw, 128, 128), tn_first, per);
   return (int)hipGetLastError();
 }
@@ -1734,42 +1541,15 @@ int gemm_bf16x3_dual(const GemmArgsB& nt, const GemmArgsB& tn, hipStream_t strea
   if (!on || tiles < 256) return -1;
   // (the dual kernel writes both results through buffer resources with 32-bit byte offsets: epilogue<>, CBUF)
   if ((long)nt.M * nt.ldc * 4 >= (1L << 31) || (long)tn.M * tn.ldc * 4 >= (1L << 31)) return -1;
-  const int key = (nt.epi == EPI_DACT ? 2 : 0) + (tn.epi == EPI_ACCUM ? 1 : 0);
-  switch (key) {
-#define TFK_X3_DUAL(E1, E2)                                                                \
-  (x3_waves() == 8    ? launch_x3_dual<E1, E2, 4>(nt, tn, stream)                            \
-   : x3_waves() == 44 ? launch_x3_dual<E1, E2, 0>(nt, tn, stream)                            \
-                      : launch_x3_dual<E1, E2, 2>(nt, tn, stream))
-    case 0: return TFK_X3_DUAL(0, 0);
-    case 1: return TFK_X3_DUAL(0, EPI_ACCUM);
-    case 2: return TFK_X3_DUAL(EPI_DACT, 0);
-    default: return TFK_X3_DUAL(EPI_DACT, EPI_ACCUM);
-#undef TFK_X3_DUAL
-  }
+  return with_dual_epi(nt, tn, [&](auto e1, auto e2) { return launch_x3_dual<decltype(e1)::value, decltype(e2)::value>(nt, tn, stream); });
 }
 
 int gemm_bf16x3(GemmLayout layout, const GemmArgsB& p, hipStream_t stream) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return (int)hipErrorInvalidValue;
   if (!x3_operands_ok(p, layout == GEMM_TN ? p.K : p.M, layout == GEMM_NT ? p.N : p.K)) return (int)hipErrorInvalidValue;
-  switch (layout) {
-    case GEMM_NN:
-      switch (p.epi) {
-        case 0: return launch_x3<true, false, 0>(p, stream);
-        case EPI_BIAS: return launch_x3<true, false, EPI_BIAS>(p, stream);
-        case EPI_BIAS | EPI_COLSTATS: return launch_x3<true, false, EPI_BIAS | EPI_COLSTATS>(p, stream);
-        case EPI_BIAS | EPI_EVAL_ACT: return launch_x3<true, false, EPI_BIAS | EPI_EVAL_ACT>(p, stream);
-      }
-      break;
-    case GEMM_NT:
-      if (p.epi == 0) return launch_x3<true, true, 0>(p, stream);
-      if (p.epi == EPI_DACT) return launch_x3<true, true, EPI_DACT>(p, stream);
-      break;
-    case GEMM_TN:
-      if (p.epi == 0) return launch_x3<false, false, 0>(p, stream);
-      if (p.epi == EPI_ACCUM) return launch_x3<false, false, EPI_ACCUM>(p, stream);
-      break;
-  }
-  return (int)hipErrorInvalidValue;
+  return with_layout_epi(layout, p.epi, [&](auto a_kc, auto b_kc, auto epi) {
+    return launch_x3<decltype(a_kc)::value, decltype(b_kc)::value, decltype(epi)::value>(p, stream);
+  });
 }
 
 int gemm_bf16(GemmLayout layout, const GemmArgsB& p, hipStream_t stream) {
@@ -1780,25 +1560,9 @@ int gemm_bf16(GemmLayout layout, const GemmArgsB& p, hipStream_t stream) {
     const long b_rows = layout == GEMM_NT ? p.N : p.K;
     if (a_rows * p.lda * 2 >= (1L << 31) || b_rows * p.ldb * 2 >= (1L << 31)) return (int)hipErrorInvalidValue;
   }
-  switch (layout) {
-    case GEMM_NN:
-      switch (p.epi) {
-        case 0: return launch<true, false, 0>(p, stream);
-        case EPI_BIAS: return launch<true, false, EPI_BIAS>(p, stream);
-        case EPI_BIAS | EPI_COLSTATS: return launch<true, false, EPI_BIAS | EPI_COLSTATS>(p, stream);
-        case EPI_BIAS | EPI_EVAL_ACT: return launch<true, false, EPI_BIAS | EPI_EVAL_ACT>(p, stream);
-      }
-      break;
-    case GEMM_NT:
-      if (p.epi == 0) return launch<true, true, 0>(p, stream);
-      if (p.epi == EPI_DACT) return launch<true, true, EPI_DACT>(p, stream);
-      break;
-    case GEMM_TN:
-      if (p.epi == 0) return launch<false, false, 0>(p, stream);
-      if (p.epi == EPI_ACCUM) return launch<false, false, EPI_ACCUM>(p, stream);
-      break;
-  }
-  return (int)hipErrorInvalidValue;
+  return with_layout_epi(layout, p.epi, [&](auto a_kc, auto b_kc, auto epi) {
+    return launch<decltype(a_kc)::value, decltype(b_kc)::value, decltype(epi)::value>(p, stream);
+  });
 }
 
 }  // namespace tfk

@@ -3,7 +3,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DTFKB_ABL=<n> -I tfkaldi_amd/csrc tools/gemm_f32x3_ablate.hip -o tools/bin/x3abl<n>
 //   tools/bin/x3abl<n> <layout> <M> <N> <K>         (block geometry: env TFK_BF16X3_CFG)
 //   env: TFK_ABL_ITERS (launches in the timed loop, default 30; thousands for a SUSTAINED figure -- a burst starts on a cold clock),
-//        TFK_ABL_DATA = random | zero | p0 | real (below), TFK_BF16X3_WAVES / TFK_BF16X3_CFG (block form / geometry)
+//        TFK_ABL_DATA = random | zero | p0 | real (below), TFK_BF16X3_CFG (block geometry),
+//        TFK_ABL_EPI = stats (NN only: bias + column statistics, as the forward contractions of a training step; default: no epilogue)
 //   tools/bin/x3abl<n> 3 <frames> <d_in> <d_out>    the backward pair of a layer in one launch (gemm_bf16x3_dual):
 //                                                   dA[frames, d_in] = dZ . W^T  and  dW[d_in, d_out] = in^T . dZ
 #include "../tfkaldi_amd/csrc/gemm_bf16.hip"
@@ -82,6 +83,14 @@ int main(int argc, char** argv) {
   hipMemcpy(dB, hb.data(), hb.size() * 2, hipMemcpyHostToDevice);
   tfk::GemmArgsB g = {};
   g.A = dA; g.B = dB; g.C = dC; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  // TFK_ABL_EPI=stats (NN): bias + column statistics, the epilogue of the training step's forward contractions
+  if (layout == 0 && getenv("TFK_ABL_EPI") && !strcmp(getenv("TFK_ABL_EPI"), "stats")) {
+    float *bias, *stats;
+    const size_t nstats = (size_t)2 * ((M + tfk::kGemmBf16x3TileRows - 1) / tfk::kGemmBf16x3TileRows) * ldc;
+    hipMalloc(&bias, (size_t)ldc * 4); hipMalloc(&stats, nstats * 4);
+    hipMemset(bias, 0, (size_t)ldc * 4);
+    g.bias = bias; g.stats = stats; g.epi = tfk::EPI_BIAS | tfk::EPI_COLSTATS;
+  }
   // the split-K form where the shape is eligible (TFK_BF16X3_CFG=0 / 1: never)
   if (const size_t need = tfk::gemm_bf16x3_splitk_floats((tfk::GemmLayout)layout, M, N, K)) {
     hipMalloc(&g.splitk_ws, need * 4);
@@ -90,7 +99,8 @@ int main(int argc, char** argv) {
   }
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int i = 0; i < 5; ++i) tfk::gemm_bf16x3((tfk::GemmLayout)layout, g, 0);
+  for (int i = 0; i < 5; ++i)
+    if (const int rc = tfk::gemm_bf16x3((tfk::GemmLayout)layout, g, 0)) { printf("launch failed: %d\n", rc); return 1; }
   const int iters = getenv("TFK_ABL_ITERS") ? atoi(getenv("TFK_ABL_ITERS")) : 30;  // (thousands: long enough to sample power)
   hipEventRecord(e0, 0);
   for (int i = 0; i < iters; ++i) tfk::gemm_bf16x3((tfk::GemmLayout)layout, g, 0);
@@ -99,6 +109,6 @@ int main(int argc, char** argv) {
   float ms = 0;
   hipEventElapsedTime(&ms, e0, e1);
   ms /= iters;
-  printf("ABL=%d %s layout %d %dx%dx%d: %7.1f us  %7.1f TF fp32-equivalent\n", TFKB_ABL, g.splitk_ws ? "split-K" : "       ", layout, M, N, K, ms * 1e3, 2.0 * M * N * K / ms / 1e9);
+  printf("ABL=%d %s layout %d epi %d %dx%dx%d: %8.2f us  %7.1f TF fp32-equivalent\n", TFKB_ABL, g.splitk_ws ? "split-K" : "       ", layout, g.epi, M, N, K, ms * 1e3, 2.0 * M * N * K / ms / 1e9);
   return 0;
 }
