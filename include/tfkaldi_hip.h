@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 14
+#define TFK_ABI_VERSION 15
 
 typedef struct tfk_engine tfk_engine;
 
@@ -470,6 +470,68 @@ int tfk_ctc_score_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T,
  * outside [0, O) is clamped). */
 int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                          const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off, float* score);
+/* (ABI 15) Training on the EXPECTED NUMBER OF LABEL ERRORS over an N-best list (MWER; Prabhavalkar et al. 2018, Shannon 2017)
+ * instead of -- or on top of -- the CTC likelihood.  Train-mode forward of the flat utterance-major frames X [T, ldx] of U
+ * utterances (utt_len[U], sum = T) as tfk_accumulate_ctc; ref_labels / ref_len[U] = the references, laid out as
+ * tfk_accumulate_ctc takes its labels; hyp_count[U] / hyp_labels / hyp_len[P] = the hypotheses y_1 .. y_N of every utterance,
+ * laid out as tfk_ctc_score takes them (N = hyp_count[u] >= 0, 0 allowed anywhere; pairs ordered by utterance, then by
+ * hypothesis; labels and hyp_len back to back in pair order; at most 511 labels each, values in [0, output_dim - 1); blank =
+ * the LAST class; P <= 1048576).  A hypothesis listed twice counts twice.  Per utterance, on the logits z of THIS pass
+ * (train mode: batch statistics, dropout -- not the evaluation-mode logits the list may have been decoded from):
+ *   s_i = log p(y_i | z), tfk_ctc_score's quantity (-inf for a pair too short for its labels; a zero-frame utterance: 0 if
+ *         the hypothesis is empty, else -inf);   e_i = Levenshtein(y_i, reference), unit costs
+ *   p_i = exp(s_i - m) / sum_j exp(s_j - m), m = the largest s_j (an infeasible pair: p_i = 0)
+ *   R_u = sum_i p_i e_i (0 when N = 0 or no pair is feasible),   w_i = p_i (e_i - R_u)
+ * formed in double, in pair order, from the pairs' log-probabilities in double; every w_i is rounded to float once.
+ *   batch_loss += sum_u R_u + ctc_weight * sum_u -log p(reference_u | z_u)     (the second term only when ctc_weight > 0)
+ *   num_frames += the number of REFERENCE labels (as the CTC loss counts), so tfk_apply returns the expected label error rate
+ *   (errors per reference label) plus ctc_weight times the CTC loss per label
+ *   dL/dz[t, c] = sum_i w_i occ_i[t, c] + ctc_weight * (softmax(z_t)[c] - occ_ref[t, c])
+ * with occ_i[t, c] = the state posteriors of y_i at frame t folded onto the classes, what the CTC loss subtracts from the
+ * softmax (sum_i w_i = 0, so the softmax terms of the first part cancel); then backward as tfk_accumulate.  Per frame the
+ * posteriors of a pair are divided by their sum where that is within 1e-2 of one, as in the CTC loss.  Sums run in a fixed
+ * order (pairs in pair order; within a pair the labels in label order) without floating-point atomics: two calls on the same
+ * input give the same bits.  A single feasible hypothesis, or hypotheses that all have the same e_i, give a zero gradient
+ * (R_u is still reported); hyp_count[u] = 0 leaves only the ctc_weight term; a reference too short for its frames under
+ * ctc_weight > 0 adds +inf to the loss and no gradient from that term, as in tfk_accumulate_ctc.
+ * Scratch: every (utterance, hypothesis) pair -- and every reference under ctc_weight > 0 -- owns a lattice of its
+ * utterance's frames x sext states (sext = 2 * the longest label sequence + 1 rounded up to 128, 256, 512 or 1024): 12 bytes
+ * per state.  Limits, refused with a message before anything is launched: more than 2^33 such states in one call; a class row
+ * plus a state row, (ldO + sext) * 4 bytes with ldO = output_dim rounded up to the engine's row stride, beyond 64 KiB of LDS.
+ * Errors (non-zero, tfk_last_error names the cause -- with the utterance and the hypothesis where there is one; the engine
+ * stays usable and its accumulators are untouched): NULL pointers, T <= 0, a negative count or length, a label outside
+ * [0, output_dim - 1), a hypothesis or reference of more than 511 labels, ctc_weight negative or not finite, P > 1048576, a
+ * shape beyond the limits.  Host pointers for the tables; X as tfk_accumulate_ctc (TFK_DEVICE_PTRS allowed);
+ * TFK_LAST_MICROBATCH as everywhere.  The eval variant: evaluation-mode forward, loss only (a validation figure); inside an
+ * open step the step's sums are set aside and restored as for every other evaluation. */
+int tfk_accumulate_ctc_mwer(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                            const int32_t* ref_labels, const int32_t* ref_len, const int32_t* hyp_count,
+                            const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight, int flags);
+int tfk_eval_accumulate_ctc_mwer(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                 const int32_t* ref_labels, const int32_t* ref_len, const int32_t* hyp_count,
+                                 const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_accumulate_ctc_raw; TFK_RAW_DEVICE allowed). */
+int tfk_accumulate_ctc_mwer_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                                int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
+                                const int32_t* hyp_count, const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight,
+                                int flags);
+int tfk_eval_accumulate_ctc_mwer_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                     int32_t U, int32_t context_width, const float* cmvn, const int32_t* ref_labels,
+                                     const int32_t* ref_len, const int32_t* hyp_count, const int32_t* hyp_labels,
+                                     const int32_t* hyp_len, float ctc_weight, int flags);
+/* (ABI 15) Tests / tools: the criterion alone on logits [T, ld] of O classes, DEVICE pointers: seg[U + 1] = first row of every
+ * utterance, pair_utt[P] = the utterance of pair p (in [0, U), NON-DECREASING: the pairs of an utterance are adjacent),
+ * lab_off[P + 1] = first label of every pair in labels, ref_off[U + 1] = first label of every reference in ref_labels.  Out:
+ * risk [U] = R_u, score [P] = s_i, edits [P] = e_i, and -- unless dlogits is NULL, which asks for those three only -- rows
+ * [seg[0], seg[U]) of dlogits [., ldd] = dL/dz as above (columns [O, ldd) zero; other rows are not written; the logits are
+ * not overwritten).  The loss of the call is sum_u risk[u] plus ctc_weight times the references' CTC losses, which this entry
+ * does not return.  The small tables are read back first and the derived tables uploaded (two synchronisations of `stream`);
+ * the kernels and the call's own scratch (from the stream's memory pool) are stream-ordered.  Labels are not validated (a
+ * value outside [0, O) is clamped where it addresses the logits).  Limits as above with ldO = ld. */
+int tfk_ctc_mwer_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
+                        const int32_t* ref_labels, const int32_t* ref_off, float ctc_weight, float* dlogits, int64_t ldd,
+                        float* risk, float* score, int32_t* edits);
 /* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
  * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */

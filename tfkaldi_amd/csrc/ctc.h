@@ -135,6 +135,62 @@ const char* ctc_score_limits(int O, int T, int U, int P, int max_labels);
 void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
                const int32_t* pair_utt, int P, const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch,
                float* score);
+// Expected label errors over an N-best list (MWER; Prabhavalkar et al. 2018) and their gradient w.r.t. the logits (the contract
+// is the comment at tfk_accumulate_ctc_mwer in tfkaldi_hip.h).  Per utterance u with hypotheses y_i (pairs ufirst[u] ..
+// ufirst[u + 1]), s_i = log p(y_i | z) as ctc_score defines it, e_i = their Levenshtein distance to the reference:
+//   p_i = softmax over the list of s_i (an infeasible pair: 0),  risk[u] = R = sum_i p_i e_i,  w_i = p_i (e_i - R)
+//   dlogits[t, c] = sum_i w_i occ_i[t, c] + ctc_weight * (softmax(z_t)[c] - occ_ref[t, c])
+// with occ = a label sequence's state posteriors folded onto the classes, what ctc_loss_grad subtracts from the softmax.
+// Every pair -- and, with ctc_weight > 0, every reference, as pair P + u -- is one "utterance" of a pair-level CtcBatch: pair p
+// owns the scratch rows [prow[p], prow[p + 1]) (as many as its utterance has frames) of lp / ab / bb / off / offb, and
+// ctc_alpha_beta_kernel sweeps it as it sweeps an utterance of the loss.  Order of every sum is fixed: see the kernels.
+// tab (ctc_mwer_table fills it on the host; ctc_mwer_table_words words):
+//   [prow NP + 1 | lab_off NP + 1 | pair_utt NP | ufirst U + 1 | ref_at P | ref_cnt P]
+// labels: the hypotheses' labels in pair order, then the references' in utterance order (lab_off / ref_at index it).
+// ctc_mwer_limits: NULL, or the limit a shape breaks (PR = the scratch rows of all NP pairs).
+struct CtcMwer {
+  const float* logits;   // [T, ld]
+  int ld, O, T, U;
+  const int32_t* seg;    // [U + 1] first row of every utterance
+  int P, NP;             // hypothesis pairs; all pairs: P, or P + U with the references appended
+  int64_t PR;            // prow[NP]
+  int sext;              // ctc_state_stride(longest label sequence of the NP pairs)
+  int max_hyp;           // longest hypothesis (selects label_edit_distance's tile)
+  float ctc_weight;
+  const int32_t* tab;
+  const int32_t* labels;
+  // scratch (ctc_mwer_carve points these into one block of ctc_mwer_scratch_bytes bytes)
+  double *off, *offb, *logz;  // [PR] [PR] [NP]
+  float *lp, *ab, *bb;        // [PR, sext]
+  float *lse, *utt_loss, *w;  // [T] [NP] [P]
+  // out
+  float* risk;      // [U]
+  float* score;     // [P] log p(y_i | z), -inf for an infeasible pair
+  int32_t* edits;   // [P]
+};
+__host__ __device__ inline const int32_t* ctc_mwer_prow(const CtcMwer& m) { return m.tab; }
+__host__ __device__ inline const int32_t* ctc_mwer_lab_off(const CtcMwer& m) { return m.tab + m.NP + 1; }
+__host__ __device__ inline const int32_t* ctc_mwer_pair_utt(const CtcMwer& m) { return m.tab + 2 * (m.NP + 1); }
+__host__ __device__ inline const int32_t* ctc_mwer_ufirst(const CtcMwer& m) { return m.tab + 2 * (m.NP + 1) + m.NP; }
+__host__ __device__ inline const int32_t* ctc_mwer_ref_at(const CtcMwer& m) { return ctc_mwer_ufirst(m) + m.U + 1; }
+__host__ __device__ inline const int32_t* ctc_mwer_ref_cnt(const CtcMwer& m) { return ctc_mwer_ref_at(m) + m.P; }
+constexpr int64_t kCtcMwerMaxStates = (int64_t)1 << 33;
+constexpr int64_t kCtcMwerMaxLds = 64 * 1024;
+const char* ctc_mwer_limits(int O, int64_t ld, int T, int U, int P, int max_labels, int64_t PR);
+size_t ctc_mwer_table_words(int U, int P, int NP);
+// (host arrays; hyp_len[P] in pair order; with_ref appends the references as pairs P .. P + U - 1)
+void ctc_mwer_table(const int32_t* utt_len, int U, const int32_t* hyp_count, const int32_t* hyp_len, const int32_t* ref_len,
+                    bool with_ref, int32_t* tab);
+size_t ctc_mwer_scratch_bytes(int T, int NP, int P, int64_t PR, int sext);
+void ctc_mwer_carve(void* scratch, CtcMwer* m);
+// risk, score, edits; with dlogits != NULL also rows [row0, row0 + rows) of dlogits [., ldd] (columns beyond O: zero) and
+// its twin.  dlogits may be the logits themselves: every read of a row precedes its write.
+// stages: the sweeps (row log-sum-exps, emissions, alpha and -- with dlogits -- beta), the weights (edits, risk, score, w), the
+// gradient; a caller that times them apart enqueues them one by one, in this order.
+constexpr int kCtcMwerSweep = 1, kCtcMwerWeights = 2, kCtcMwerGrad = 4, kCtcMwerAll = 7;
+void ctc_mwer(hipStream_t s, const CtcMwer& m, float* dlogits, int ldd, int row0, int rows, Twin tw, int stages = kCtcMwerAll);
+// scalars[0] (+)= sum_u risk[u] + ctc_weight * the references' losses, scalars[1] (+)= ref_labels, scalars[2] (+)= 1
+void ctc_mwer_loss_reduce(hipStream_t s, const CtcMwer& m, int ref_labels, float* scalars, bool overwrite);
 // tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
 // ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
 // length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,

@@ -1595,6 +1595,155 @@ ctc_score_kernel(const float* __restrict__ logits, int ld, int O, const int32_t*
   if (lane == 0) score[p] = log_z_rel > -1e29f ? (float)(off + (double)log_z_rel) : -INFINITY;
 }
 
+// ---- expected label errors over an N-best list (MWER; the contract is stated in ctc.h and at tfk_accumulate_ctc_mwer) ----
+//
+// Every (utterance, hypothesis) pair -- and, under ctc_weight > 0, every (utterance, reference) -- is one "utterance" of a
+// pair-level CtcBatch whose rows are the pair's own copy of its utterance's frames: ctc_alpha_beta_kernel runs on it unchanged.
+
+// lp[prow[p] + f, s] = z[seg[u] + f, class(s)] - lse[seg[u] + f], u = pair_utt[p]: ctc_gather_kernel through the pair map
+__global__ void __launch_bounds__(256)
+ctc_pair_gather_kernel(CtcMwer m) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)m.PR * m.sext) return;
+  const int pr = (int)(idx / m.sext), s = (int)(idx % m.sext);
+  const int32_t* prow = ctc_mwer_prow(m);
+  const int32_t* lab_off = ctc_mwer_lab_off(m);
+  const int p = utt_of(prow, m.NP, pr);
+  const int l0 = lab_off[p], n = 2 * (lab_off[p + 1] - l0) + 1;
+  float v = NEG;
+  if (s < n) {
+    const size_t t = (size_t)(m.seg[ctc_mwer_pair_utt(m)[p]] + (pr - prow[p]));
+    const int k = (s & 1) ? min(max(m.labels[l0 + (s >> 1)], 0), m.O - 1) : m.O - 1;  // (clamped: never a bad address)
+    v = m.logits[t * m.ld + k] - m.lse[t];
+  }
+  m.lp[idx] = v;
+}
+
+// acc + v(lane 0) + v(lane 1) + ... + v(lane 63), one addition after the other: the same in every lane, in lane order
+__device__ __forceinline__ double wave_add_in_order(double acc, double v) {
+  for (int l = 0; l < 64; ++l) acc += __shfl(v, l);
+  return acc;
+}
+
+// ONE WAVE PER UTTERANCE: the distribution over its list, the expected number of label errors and the weights of the
+// gradient, in double and in pair order from the pairs' log Z:
+//   p_i = exp(s_i - m) / sum_j exp(s_j - m) (m = the largest feasible s_j; an infeasible pair: p_i = 0),
+//   R = sum_i p_i e_i,   w_i = p_i (e_i - R), rounded to float once;   no feasible pair: R = 0, w = 0
+__global__ void __launch_bounds__(64)
+ctc_mwer_weights_kernel(CtcMwer m) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int32_t* ufirst = ctc_mwer_ufirst(m);
+  const int p0 = ufirst[u], p1 = ufirst[u + 1];
+  double mx = -INFINITY;
+  for (int p = p0 + lane; p < p1; p += 64)
+    if (m.utt_loss[p] < INFINITY) mx = fmax(mx, m.logz[p]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+  const bool any = mx > -INFINITY;
+  double Z = 0.0;
+  for (int q = p0; q < p1; q += 64) {
+    const int p = q + lane;
+    const double ex = (any && p < p1 && m.utt_loss[p] < INFINITY) ? exp(m.logz[p] - mx) : 0.0;
+    Z = wave_add_in_order(Z, ex);
+  }
+  double R = 0.0;
+  for (int q = p0; q < p1; q += 64) {
+    const int p = q + lane;
+    const double ex = (any && p < p1 && m.utt_loss[p] < INFINITY) ? exp(m.logz[p] - mx) : 0.0;
+    R = wave_add_in_order(R, any && p < p1 ? ex / Z * (double)m.edits[p] : 0.0);
+  }
+  for (int p = p0 + lane; p < p1; p += 64) {
+    const bool ok = any && m.utt_loss[p] < INFINITY;
+    const double pi = ok ? exp(m.logz[p] - mx) / Z : 0.0;
+    m.w[p] = (float)(pi * ((double)m.edits[p] - R));
+    m.score[p] = m.utt_loss[p] < INFINITY ? (float)m.logz[p] : -INFINITY;
+  }
+  if (lane == 0) m.risk[u] = (float)R;
+}
+
+// ONE WAVE PER LOGITS ROW t = row0 + blockIdx.x of utterance u, frame f; dynamic LDS: the class row, then one pair's state
+// posteriors.  row[c] = ctc_weight * softmax(z_t)[c] (only where the reference is feasible), then for the utterance's pairs
+// in pair order, and last for its reference with the coefficient -ctc_weight:
+//   gamma(s) exactly as ctc_grad_kernel forms it from the pair's rows (double exponent, divided by its sum where that is
+//   within 1e-2 of one), row[class(s)] += coefficient * gamma(s)
+// The fold: lane c % 64 owns class c and scans the pair's labels in label order, so every class sees its terms in the
+// order ctc_grad_kernel's lane 0 adds them -- pairs, then labels; the blanks as there: lane-strided sums, then the butterfly --
+// while the N * S serial LDS updates become N * S broadcast reads.  A pair with coefficient zero (a single hypothesis, an
+// infeasible one) is skipped: its rows stay exactly zero.  No atomics: the same input gives the same bits.
+__global__ void __launch_bounds__(64)
+ctc_mwer_grad_kernel(CtcMwer m, int row0, float* __restrict__ dlogits, int ldd, Twin tw) {
+  extern __shared__ float row[];
+  float* g = row + m.ld;
+  const int t = row0 + blockIdx.x, lane = threadIdx.x;
+  const int u = utt_of(m.seg, m.U, t);
+  const int f = t - m.seg[u];
+  const int32_t* prow = ctc_mwer_prow(m);
+  const int32_t* lab_off = ctc_mwer_lab_off(m);
+  const int32_t* ufirst = ctc_mwer_ufirst(m);
+  const int p0 = ufirst[u], nh = ufirst[u + 1] - p0;
+  const bool ref_live = m.NP > m.P && m.utt_loss[m.P + u] < INFINITY;
+  {
+    // (read before anything is written: dlogits may be the logits themselves)
+    const float* z = m.logits + (size_t)t * m.ld;
+    const float l = m.lse[t];
+    for (int c = lane; c < m.O; c += 64) row[c] = ref_live ? m.ctc_weight * expf(z[c] - l) : 0.f;
+  }
+  for (int i = 0; i < nh + (ref_live ? 1 : 0); ++i) {
+    const int p = i < nh ? p0 + i : m.P + u;
+    const float coef = i < nh ? m.w[p] : -m.ctc_weight;
+    if (coef == 0.f || !(m.utt_loss[p] < INFINITY)) continue;  // (uniform over the wave)
+    const int l0 = lab_off[p], S = lab_off[p + 1] - l0, n = 2 * S + 1;
+    const size_t pr = (size_t)prow[p] + f;
+    const double shift = m.off[pr] + m.offb[pr] - m.logz[p];
+    const float* al = m.ab + pr * m.sext;
+    const float* be = m.bb + pr * m.sext;
+    const float* lp = m.lp + pr * m.sext;
+    float tot = 0.f;
+    for (int s = lane; s < n; s += 64) {
+      g[s] = __expf((float)((double)al[s] + (double)be[s] - (double)lp[s] + shift));
+      tot += g[s];
+    }
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    const float inv = fabsf(tot - 1.f) < 1e-2f ? 1.f / tot : 1.f;
+    for (int s = lane; s < n; s += 64) g[s] *= inv;
+    __syncthreads();
+    float blank = 0.f;
+    for (int s = 2 * lane; s < n; s += 128) blank += g[s];
+    for (int o = 32; o > 0; o >>= 1) blank += __shfl_xor(blank, o);
+    for (int cb = 0; cb < m.O; cb += 64) {
+      const int c = cb + lane;
+      float acc = c < m.O ? row[c] : 0.f;
+      if (c == m.O - 1) acc += coef * blank;
+      for (int j = 0; j < S; ++j)
+        if (m.labels[l0 + j] == c) acc += coef * g[2 * j + 1];
+      if (c < m.O) row[c] = acc;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  float* dr = dlogits + (size_t)t * ldd;
+  for (int c = lane; c < ldd; c += 64) dr[c] = c < m.O ? row[c] : 0.f;
+  if (tw.p)
+    for (int c = lane; c < ldd; c += 64) twin_put(tw, (size_t)t, c, c < m.O ? row[c] : 0.f);
+}
+
+// scalars[0] (+)= sum_u risk[u] (+ ctc_weight * the references' losses), scalars[1] (+)= labels, scalars[2] (+)= 1
+__global__ void __launch_bounds__(256)
+ctc_mwer_loss_reduce_kernel(const float* __restrict__ risk, const float* __restrict__ ref_loss, int U, float ctc_weight,
+                            float labels, float* __restrict__ scalars, int overwrite) {
+  __shared__ float sm[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < U; i += 256) s += ref_loss ? risk[i] + ctc_weight * ref_loss[i] : risk[i];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+    scalars[0] = overwrite ? s : scalars[0] + s;
+    scalars[1] = overwrite ? labels : scalars[1] + labels;
+    scalars[2] = overwrite ? 1.f : scalars[2] + 1.f;
+  }
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -1749,6 +1898,121 @@ void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const i
     case 8: hipLaunchKernelGGL(ctc_score_kernel<8>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
     default: hipLaunchKernelGGL(ctc_score_kernel<16>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
   }
+}
+
+const char* ctc_mwer_limits(int O, int64_t ld, int T, int U, int P, int max_labels, int64_t PR) {
+  if (O < 2) return "output_dim < 2 (one label + blank)";
+  if (max_labels < 0) return "a negative length";
+  if (max_labels > kCtcMaxLabels) return "more than 511 labels in one hypothesis or reference";
+  if (T < 0 || T > kCtcAlignMaxFrames) return "more than 8388607 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  if (P < 0 || P > kCtcScoreMaxPairs) return "more than 1048576 (utterance, hypothesis) pairs";
+  const int64_t sext = ctc_state_stride(max_labels);
+  if (PR < 0 || PR * sext > kCtcMwerMaxStates)
+    return "more than 2^33 lattice states (frames x hypotheses x padded states per frame) in one call";
+  if (ld < O || (ld + sext) * (int64_t)sizeof(float) > kCtcMwerMaxLds)
+    return "the class row and the state row of one frame exceed 64 KiB of LDS";
+  return nullptr;
+}
+
+size_t ctc_mwer_table_words(int U, int P, int NP) { return 3 * (size_t)NP + 2 + (size_t)U + 1 + 2 * (size_t)P; }
+
+void ctc_mwer_table(const int32_t* utt_len, int U, const int32_t* hyp_count, const int32_t* hyp_len, const int32_t* ref_len,
+                    bool with_ref, int32_t* tab) {
+  int P = 0;
+  for (int u = 0; u < U; ++u) P += hyp_count[u];
+  const int NP = with_ref ? P + U : P;
+  int32_t* prow = tab;
+  int32_t* lab_off = prow + NP + 1;
+  int32_t* pair_utt = lab_off + NP + 1;
+  int32_t* ufirst = pair_utt + NP;
+  int32_t* ref_at = ufirst + U + 1;
+  int32_t* ref_cnt = ref_at + P;
+  int32_t hyp_total = 0;
+  for (int p = 0; p < P; ++p) hyp_total += hyp_len[p];
+  prow[0] = lab_off[0] = ufirst[0] = 0;
+  int p = 0;
+  int32_t ref_first = hyp_total;
+  for (int u = 0; u < U; ++u) {
+    for (int h = 0; h < hyp_count[u]; ++h, ++p) {
+      pair_utt[p] = u;
+      prow[p + 1] = prow[p] + utt_len[u];
+      lab_off[p + 1] = lab_off[p] + hyp_len[p];
+      ref_at[p] = ref_first;
+      ref_cnt[p] = ref_len[u];
+    }
+    ufirst[u + 1] = p;
+    ref_first += ref_len[u];
+  }
+  for (int u = 0; with_ref && u < U; ++u) {
+    pair_utt[P + u] = u;
+    prow[P + u + 1] = prow[P + u] + utt_len[u];
+    lab_off[P + u + 1] = lab_off[P + u] + ref_len[u];
+  }
+}
+
+size_t ctc_mwer_scratch_bytes(int T, int NP, int P, int64_t PR, int sext) {
+  const size_t rows = (size_t)PR, t = (size_t)(T > 0 ? T : 0);
+  return (2 * rows + (size_t)NP) * sizeof(double) + (3 * rows * (size_t)sext + t + (size_t)NP + (size_t)P) * sizeof(float) + 16;
+}
+
+void ctc_mwer_carve(void* scratch, CtcMwer* m) {
+  const size_t rows = (size_t)m->PR;
+  double* d = static_cast<double*>(scratch);
+  m->off = d;
+  m->offb = d + rows;
+  m->logz = d + 2 * rows;
+  float* f = reinterpret_cast<float*>(d + 2 * rows + (size_t)m->NP);
+  m->lp = f;
+  m->ab = f + rows * m->sext;
+  m->bb = f + 2 * rows * m->sext;
+  f += 3 * rows * m->sext;
+  m->lse = f;
+  m->utt_loss = f + (m->T > 0 ? m->T : 0);
+  m->w = m->utt_loss + m->NP;
+}
+
+static void ctc_mwer_sweep(hipStream_t s, const CtcMwer& m, bool with_grad);
+
+void ctc_mwer(hipStream_t s, const CtcMwer& m, float* dlogits, int ldd, int row0, int rows, Twin tw, int stages) {
+  if (m.U <= 0) return;
+  if (stages & kCtcMwerSweep) ctc_mwer_sweep(s, m, dlogits != nullptr);
+  // the distance is symmetric: the references are the kernel's `hyp` operand (start and length per pair), the pairs'
+  // labels its `ref` operand (the one that selects the register tile)
+  if ((stages & kCtcMwerWeights) && m.P > 0)
+    label_edit_distance(s, m.labels, ctc_mwer_ref_at(m), ctc_mwer_ref_cnt(m), m.labels, ctc_mwer_lab_off(m), m.P, m.max_hyp,
+                        m.edits);
+  if (stages & kCtcMwerWeights) hipLaunchKernelGGL(ctc_mwer_weights_kernel, dim3(m.U), dim3(64), 0, s, m);
+  if ((stages & kCtcMwerGrad) && dlogits && rows > 0)
+    hipLaunchKernelGGL(ctc_mwer_grad_kernel, dim3(rows), dim3(64), (size_t)(m.ld + m.sext) * sizeof(float), s, m, row0, dlogits,
+                       ldd, tw);
+}
+
+// row log-sum-exps, the pairs' emissions, the sweeps (backward too: with_grad)
+static void ctc_mwer_sweep(hipStream_t s, const CtcMwer& m, bool with_grad) {
+  if (m.T > 0)
+    hipLaunchKernelGGL(ctc_row_lse_kernel, dim3((unsigned)((m.T + 3) / 4)), dim3(256), 0, s, m.logits, m.ld, m.O, m.T, m.lse);
+  const size_t n = (size_t)m.PR * m.sext;
+  if (n > 0) hipLaunchKernelGGL(ctc_pair_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m);
+  if (m.NP > 0) {
+    CtcBatch b = {};
+    b.seg = ctc_mwer_prow(m); b.labels = m.labels; b.lab_off = ctc_mwer_lab_off(m);
+    b.U = m.NP; b.T = (int)m.PR; b.O = m.O; b.sext = m.sext;
+    b.lp = m.lp; b.ab = m.ab; b.bb = m.bb; b.off = m.off; b.offb = m.offb; b.logz = m.logz; b.utt_loss = m.utt_loss;
+    const dim3 grid(m.NP, with_grad ? 2 : 1);
+    switch (m.sext / 64) {
+      case 2: hipLaunchKernelGGL(ctc_alpha_beta_kernel<2>, grid, dim3(64), 0, s, b); break;
+      case 4: hipLaunchKernelGGL(ctc_alpha_beta_kernel<4>, grid, dim3(64), 0, s, b); break;
+      case 8: hipLaunchKernelGGL(ctc_alpha_beta_kernel<8>, grid, dim3(64), 0, s, b); break;
+      default: hipLaunchKernelGGL(ctc_alpha_beta_kernel<16>, grid, dim3(64), 0, s, b); break;
+    }
+  }
+}
+
+void ctc_mwer_loss_reduce(hipStream_t s, const CtcMwer& m, int ref_labels, float* scalars, bool overwrite) {
+  hipLaunchKernelGGL(ctc_mwer_loss_reduce_kernel, dim3(1), dim3(256), 0, s, m.risk,
+                     m.NP > m.P ? m.utt_loss + m.P : (const float*)nullptr, m.U, m.ctc_weight, (float)ref_labels, scalars,
+                     overwrite ? 1 : 0);
 }
 
 void label_edit_distance(hipStream_t s, const int32_t* hyp, const int32_t* hyp_off, const int32_t* hyp_cnt,

@@ -67,7 +67,7 @@ struct LayerLayout {
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
   KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
-  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_COUNT
+  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_CTC_MWER_SWEEP, KF_CTC_MWER_WEIGHTS, KF_CTC_MWER_GRAD, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
@@ -75,7 +75,8 @@ const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)
                                      "loss_reduce",             "softmax_rows",     "adam_apply",      "bn_ema_apply",
                                      "misc",                    "ctc_best_path",    "edit_distance",
                                      "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm",
-                                     "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score"};
+                                     "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score",
+                                     "ctc_mwer_sweep",          "ctc_mwer_weights", "ctc_mwer_grad"};
 
 struct ProfRec {
   int family;
@@ -215,6 +216,10 @@ struct tfk_engine {
   int32_t* h_pair = nullptr;
   size_t h_pair_cap = 0;
   hipEvent_t ctc_pair_staged = nullptr;
+  // expected label errors (tfk_accumulate_ctc_mwer): the pair-level lattices of ctc_mwer, then [risk U | score P | edits P];
+  // its tables travel through ctc_pair / h_pair
+  unsigned char* ctc_mw = nullptr;
+  size_t ctc_cap_mw = 0;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1394,11 +1399,21 @@ int create_impl(const tfk_config* cfg, void* state, size_t state_bytes, void* st
   return 0;
 }
 
+struct MwerSpec {  // expected label errors over an N-best list on top of (ctc_weight times) the CTC loss
+  const int32_t* hyp_count;   // [U]
+  const int32_t* hyp_labels;  // the hypotheses' labels back to back in pair order
+  const int32_t* hyp_len;     // [P]
+  float ctc_weight;
+  // what mwer_check derives
+  int P, max_hyp, max_labels, hyp_total, ref_total;
+  int64_t PR;
+};
 struct CtcSpec {  // CTC loss instead of the frame-level cross-entropy
   const int32_t* utt_len;    // [U] frames per utterance (sum = T)
   int U;
   const int32_t* labels;     // concatenated label sequences
   const int32_t* label_len;  // [U]
+  const MwerSpec* mwer = nullptr;  // the MWER criterion: labels / label_len are the references
 };
 template <class Tp>
 int grow(tfk_engine* e, Tp** p, size_t* cap, size_t need) {
@@ -1505,6 +1520,126 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
     ProfScope ps(e, KF_LOSS_REDUCE, 0, 4.0 * c.U);
     if (!train) CHK(stash_scalars(e));
     ctc_loss_reduce(e->stream, e->ctc_utt_loss, e->ctc_lab_off, c.U, e->p_scalars(), e->scalars_fresh);
+    e->scalars_fresh = false;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Validate the tables of an MWER batch (all on the host) and derive its sizes; nothing is touched on the device.  The
+// messages name the utterance and the hypothesis, as tfk_ctc_score's do.
+int mwer_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const int32_t* ref_labels, const int32_t* ref_len,
+               MwerSpec* mw) {
+  if (U <= 0 || !utt_len || !ref_len || !mw->hyp_count)
+    return fail(-1, "CTC MWER: utt_len / ref_len / hyp_count is NULL or no utterances");
+  if (!(mw->ctc_weight >= 0.f) || !std::isfinite(mw->ctc_weight))
+    return fail(-1, "CTC MWER: ctc_weight %g is negative or not finite", (double)mw->ctc_weight);
+  int64_t P64 = 0, PR = 0, frames = 0, ref_total = 0;
+  int max_ref = 0;
+  for (int u = 0; u < U; ++u) {
+    if (mw->hyp_count[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative hypothesis count", u);
+    if (utt_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative length", u);
+    if (ref_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative reference length", u);
+    if (ref_len[u] > kCtcMaxLabels)
+      return fail(-1, "CTC MWER: utterance %d has a reference of %d labels (limit %d)", u, ref_len[u], kCtcMaxLabels);
+    P64 += mw->hyp_count[u];
+    if (P64 > kCtcScoreMaxPairs)
+      return fail(-1, "CTC MWER: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
+    PR += (int64_t)(mw->hyp_count[u] + (mw->ctc_weight > 0.f ? 1 : 0)) * utt_len[u];
+    frames += utt_len[u];
+    ref_total += ref_len[u];
+    max_ref = ref_len[u] > max_ref ? ref_len[u] : max_ref;
+  }
+  if (frames != T) return fail(-1, "CTC MWER: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
+  if (ref_total > 0 && !ref_labels) return fail(-1, "CTC MWER: ref_labels is NULL");
+  {
+    int64_t at = 0;
+    for (int u = 0; u < U; ++u)
+      for (int32_t i = 0; i < ref_len[u]; ++i, ++at)
+        if (ref_labels[at] < 0 || ref_labels[at] >= e->O - 1)
+          return fail(-1, "CTC MWER: utterance %d: reference label %d outside [0, %d)", u, ref_labels[at], e->O - 1);
+  }
+  const int P = (int)P64;
+  if (P > 0 && !mw->hyp_len) return fail(-1, "CTC MWER: hyp_len is NULL");
+  int max_hyp = 0;
+  int64_t first = 0;
+  for (int u = 0, p = 0; u < U; ++u)
+    for (int h = 0; h < mw->hyp_count[u]; ++h, ++p) {
+      const int32_t n = mw->hyp_len[p];
+      if (n < 0) return fail(-1, "CTC MWER: utterance %d, hypothesis %d has a negative length", u, h);
+      if (n > kCtcMaxLabels)
+        return fail(-1, "CTC MWER: utterance %d, hypothesis %d has %d labels (limit %d)", u, h, n, kCtcMaxLabels);
+      if (n > 0 && !mw->hyp_labels) return fail(-1, "CTC MWER: hyp_labels is NULL");
+      for (int32_t i = 0; i < n; ++i)
+        if (mw->hyp_labels[first + i] < 0 || mw->hyp_labels[first + i] >= e->O - 1)
+          return fail(-1, "CTC MWER: utterance %d, hypothesis %d: label %d outside [0, %d)", u, h, mw->hyp_labels[first + i],
+                      e->O - 1);
+      first += n;
+      max_hyp = n > max_hyp ? n : max_hyp;
+    }
+  if (first + ref_total > 0x7fffffff) return fail(-1, "CTC MWER: more than 2^31 - 1 labels in one call");
+  mw->P = P;
+  mw->max_hyp = max_hyp;
+  mw->max_labels = mw->ctc_weight > 0.f && max_ref > max_hyp ? max_ref : max_hyp;
+  mw->hyp_total = (int)first;
+  mw->ref_total = (int)ref_total;
+  mw->PR = PR;
+  if (const char* why = ctc_mwer_limits(e->O, e->ldO, T, U, P, mw->max_labels, PR))
+    return fail(-1, "CTC MWER (output_dim %d, T %d, U %d, P %d, longest label sequence %d): %s", e->O, T, U, P, mw->max_labels,
+                why);
+  return 0;
+}
+
+// Loss + dLogits of one MWER micro-batch (logits already in e->logits; c.mwer has passed mwer_check): batch_loss += sum_u R_u
+// + ctc_weight * sum_u -log p(reference_u), num_frames += number of REFERENCE labels; dLogits overwrite the logits in place
+// (every read of the logits is enqueued before the gradient kernel, which reads a row before it writes it).
+int ctc_mwer_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
+  const MwerSpec& mw = *c.mwer;
+  int max_ref = 0;
+  CHK(ctc_stage(e, c, T, true, &max_ref));  // (e->ctc_seg; the references are staged with the pair tables below)
+  const int P = mw.P, NP = mw.ctc_weight > 0.f ? P + c.U : P;
+  const size_t tab_words = ctc_mwer_table_words(c.U, P, NP), total = (size_t)mw.hyp_total + (size_t)mw.ref_total;
+  const int sext = ctc_state_stride(mw.max_labels);
+  const size_t lattice = (ctc_mwer_scratch_bytes(T, NP, P, mw.PR, sext) + 15) & ~(size_t)15;
+  CHK(grow(e, &e->ctc_mw, &e->ctc_cap_mw, lattice + ((size_t)c.U + 2 * (size_t)P + 4) * sizeof(float)));
+  CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, tab_words + total + 1));
+  // pinned staging, guarded by its own event, as tfk_ctc_score stages its pair tables
+  if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
+  CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, tab_words + total + 1, /*slack=*/true, /*sync=*/false));
+  ctc_mwer_table(c.utt_len, c.U, mw.hyp_count, mw.hyp_len, c.label_len, NP > P, e->h_pair);
+  if (mw.hyp_total > 0) memcpy(e->h_pair + tab_words, mw.hyp_labels, (size_t)mw.hyp_total * sizeof(int32_t));
+  if (mw.ref_total > 0) memcpy(e->h_pair + tab_words + mw.hyp_total, c.labels, (size_t)mw.ref_total * sizeof(int32_t));
+  HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, (tab_words + total) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
+  CtcMwer m = {};
+  m.logits = e->logits; m.ld = e->ldO; m.O = e->O; m.T = T; m.U = c.U; m.seg = e->ctc_seg;
+  m.P = P; m.NP = NP; m.PR = mw.PR; m.sext = sext; m.max_hyp = mw.max_hyp; m.ctc_weight = mw.ctc_weight;
+  m.tab = e->ctc_pair; m.labels = e->ctc_pair + tab_words;
+  ctc_mwer_carve(e->ctc_mw, &m);
+  m.risk = reinterpret_cast<float*>(e->ctc_mw + lattice);
+  m.score = m.risk + c.U;
+  m.edits = reinterpret_cast<int32_t*>(m.score + P);
+  Twin tw;
+  if (e->bf16 && train) { tw.p = e->logb; tw.ld = e->ldOb; tw.x3 = e->x3; }
+  float* dl = train ? e->logits : nullptr;
+  const double states = (double)mw.PR * sext;
+  {
+    ProfScope ps(e, KF_CTC_MWER_SWEEP, 0, 4.0 * T * e->O + 4.0 * states * (train ? 4.0 : 2.0));
+    ctc_mwer(e->stream, m, dl, e->ldO, 0, T, tw, kCtcMwerSweep);
+  }
+  {
+    ProfScope ps(e, KF_CTC_MWER_WEIGHTS, 0, 4.0 * (double)total + 24.0 * NP);
+    ctc_mwer(e->stream, m, dl, e->ldO, 0, T, tw, kCtcMwerWeights);
+  }
+  if (train) {
+    ProfScope ps(e, KF_CTC_MWER_GRAD, 0, 12.0 * states + 8.0 * T * e->O);
+    ctc_mwer(e->stream, m, dl, e->ldO, 0, T, tw, kCtcMwerGrad);
+  }
+  {
+    ProfScope ps(e, KF_LOSS_REDUCE, 0, 8.0 * c.U);
+    if (!train) CHK(stash_scalars(e));
+    ctc_mwer_loss_reduce(e->stream, m, mw.ref_total, e->p_scalars(), e->scalars_fresh);
     e->scalars_fresh = false;
   }
   HIPCHK(hipGetLastError());
@@ -1673,7 +1808,7 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
   const int nfw = (train && e->cfg.layerwise_init && e->cfg.batch_norm) ? e->L : p.nact;
   CHK(forward(e, p.Xd, p.ld, T, train, p.nact, nfw, p.call, st));
   if (ctc) {
-    CHK(ctc_loss(e, *ctc, T, train));
+    CHK(ctc->mwer ? ctc_mwer_loss(e, *ctc, T, train) : ctc_loss(e, *ctc, T, train));
   } else {
     {
       ProfScope ps(e, KF_SOFTMAX_XENT, 0, (train ? 8.0 : 4.0) * T * e->O);
@@ -1897,7 +2032,7 @@ int tfk_destroy(tfk_engine* e) {
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
                   (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
-                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair})
+                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw})
     if (p) hipFree(p);
   if (e->h_pair) hipHostFree(e->h_pair);
   if (e->ctc_pair_staged) hipEventDestroy(e->ctc_pair_staged);
@@ -2136,6 +2271,50 @@ int tfk_eval_accumulate_ctc_raw(tfk_engine* e, const float* raw, int64_t ldraw, 
   CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   const CtcSpec c = {utt_len, U, labels, label_len};
   return train_or_eval(e, raw, ldraw, nullptr, T, flags & ~TFK_LAST_MICROBATCH, 0, &r, &c);
+}
+
+// Expected label errors over an N-best list (MWER) on top of ctc_weight times the CTC loss: everything is validated on the
+// host before the pass starts, so a refused call leaves the engine as it was.
+static int ctc_mwer_entry(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                          const int32_t* ref_labels, const int32_t* ref_len, const int32_t* hyp_count,
+                          const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight, int flags, int train,
+                          const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (T <= 0) return fail(-1, "empty micro-batch (T = %d)", T);
+  MwerSpec mw = {hyp_count, hyp_labels, hyp_len, ctc_weight, 0, 0, 0, 0, 0, 0};
+  CHK(mwer_check(e, utt_len, U, T, ref_labels, ref_len, &mw));
+  const CtcSpec c = {utt_len, U, ref_labels, ref_len, &mw};
+  return train_or_eval(e, X, ldx, nullptr, T, train ? flags : flags & ~TFK_LAST_MICROBATCH, train, raw, &c);
+}
+int tfk_accumulate_ctc_mwer(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                            const int32_t* ref_labels, const int32_t* ref_len, const int32_t* hyp_count,
+                            const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight, int flags) {
+  return ctc_mwer_entry(e, X, ldx, T, utt_len, U, ref_labels, ref_len, hyp_count, hyp_labels, hyp_len, ctc_weight, flags, 1,
+                        nullptr);
+}
+int tfk_eval_accumulate_ctc_mwer(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                 const int32_t* ref_labels, const int32_t* ref_len, const int32_t* hyp_count,
+                                 const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight, int flags) {
+  return ctc_mwer_entry(e, X, ldx, T, utt_len, U, ref_labels, ref_len, hyp_count, hyp_labels, hyp_len, ctc_weight, flags, 0,
+                        nullptr);
+}
+int tfk_accumulate_ctc_mwer_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                                int32_t context_width, const float* cmvn, const int32_t* ref_labels, const int32_t* ref_len,
+                                const int32_t* hyp_count, const int32_t* hyp_labels, const int32_t* hyp_len, float ctc_weight,
+                                int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_mwer_entry(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp_count, hyp_labels, hyp_len, ctc_weight, flags, 1,
+                        &r);
+}
+int tfk_eval_accumulate_ctc_mwer_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                     int32_t U, int32_t context_width, const float* cmvn, const int32_t* ref_labels,
+                                     const int32_t* ref_len, const int32_t* hyp_count, const int32_t* hyp_labels,
+                                     const int32_t* hyp_len, float ctc_weight, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_mwer_entry(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp_count, hyp_labels, hyp_len, ctc_weight, flags, 0,
+                        &r);
 }
 
 // The optimiser step in three parts, so that a data-parallel host can run Adam on each span of parameters as soon
@@ -2960,6 +3139,93 @@ int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t 
   ctc_score((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, max_labels, scratch, score);
   const hipError_t launched = hipGetLastError();
   const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+int tfk_ctc_mwer_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
+                        const int32_t* ref_labels, const int32_t* ref_off, float ctc_weight, float* dlogits, int64_t ldd,
+                        float* risk, float* score, int32_t* edits) {
+  hipStream_t st = (hipStream_t)stream;
+  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
+  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC MWER: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
+  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight))
+    return fail(-1, "CTC MWER: ctc_weight %g is negative or not finite", (double)ctc_weight);
+  if (U == 0) return P == 0 ? 0 : fail(-1, "CTC MWER: %d pairs and no utterance", P);
+  if (!seg || !ref_off || !risk || (T > 0 && !logits)) return fail(-1, "logits / seg / ref_off / risk is NULL");
+  if (P > 0 && (!pair_utt || !lab_off || !score || !edits)) return fail(-1, "pair_utt / lab_off / score / edits is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
+  // The shapes live in the small tables, which only the device knows: they come back first (one synchronisation)
+  std::vector<int32_t> h(2 * ((size_t)U + 1) + 2 * (size_t)P + 1);
+  int32_t* h_seg = h.data();
+  int32_t* h_roff = h_seg + U + 1;
+  int32_t* h_utt = h_roff + U + 1;
+  int32_t* h_off = h_utt + P;
+  HIPCHK(hipMemcpyAsync(h_seg, seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_roff, ref_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (P > 0) {
+    HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  } else {
+    h_off[0] = 0;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<int32_t> utt_len(U), ref_len(U), hyp_count(U, 0), hyp_len(P > 0 ? P : 1);
+  int max_hyp = 0, max_ref = 0;
+  int64_t PR = 0;
+  for (int u = 0; u < U; ++u) {
+    utt_len[u] = h_seg[u + 1] - h_seg[u];
+    ref_len[u] = h_roff[u + 1] - h_roff[u];
+    if (utt_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative length", u);
+    if (ref_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative reference length", u);
+    max_ref = ref_len[u] > max_ref ? ref_len[u] : max_ref;
+  }
+  if (h_seg[0] < 0 || h_seg[U] > T) return fail(-1, "CTC MWER: seg = [%d, %d] outside [0, T = %d]", h_seg[0], h_seg[U], T);
+  if (h_roff[0] < 0 || h_off[0] < 0) return fail(-1, "CTC MWER: lab_off[0] / ref_off[0] < 0");
+  for (int p = 0; p < P; ++p) {
+    hyp_len[p] = h_off[p + 1] - h_off[p];
+    if (hyp_len[p] < 0) return fail(-1, "CTC MWER: pair %d has a negative length", p);
+    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC MWER: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
+    if (p > 0 && h_utt[p] < h_utt[p - 1]) return fail(-1, "CTC MWER: pair %d: the pairs are not ordered by utterance", p);
+    ++hyp_count[h_utt[p]];
+    max_hyp = hyp_len[p] > max_hyp ? hyp_len[p] : max_hyp;
+  }
+  for (int u = 0; u < U; ++u) PR += (int64_t)(hyp_count[u] + (ctc_weight > 0.f ? 1 : 0)) * utt_len[u];
+  const int max_labels = std::max(max_hyp, max_ref);  // (the references' edit distance rides the same limit)
+  if (const char* why = ctc_mwer_limits(O, ld, T, U, P, max_labels, PR))
+    return fail(-1, "CTC MWER (O %d, T %d, U %d, P %d, longest label sequence %d): %s", O, T, U, P, max_labels, why);
+  const int hyp_total = h_off[P] - h_off[0], ref_total = h_roff[U] - h_roff[0];
+  if ((hyp_total > 0 && !labels) || (ref_total > 0 && !ref_labels)) return fail(-1, "CTC MWER: labels / ref_labels is NULL");
+  const int NP = ctc_weight > 0.f ? P + U : P;
+  const int sext = ctc_state_stride(ctc_weight > 0.f ? max_labels : max_hyp);
+  const size_t tab_words = ctc_mwer_table_words(U, P, NP), total = (size_t)hyp_total + (size_t)ref_total;
+  const size_t ints = ((tab_words + total + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
+  std::vector<int32_t> tab(tab_words);
+  ctc_mwer_table(utt_len.data(), U, hyp_count.data(), hyp_len.data(), ref_len.data(), NP > P, tab.data());
+  unsigned char* scratch = nullptr;  // the call's own scratch, released in stream order: [tables | labels | lattices]
+  HIPCHK(hipMallocAsync((void**)&scratch, ints + ctc_mwer_scratch_bytes(T, NP, P, PR, sext), st));
+  int32_t* d_tab = reinterpret_cast<int32_t*>(scratch);
+  hipError_t copied = hipMemcpyAsync(d_tab, tab.data(), tab_words * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (copied == hipSuccess && hyp_total > 0)
+    copied = hipMemcpyAsync(d_tab + tab_words, labels + h_off[0], (size_t)hyp_total * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+  if (copied == hipSuccess && ref_total > 0)
+    copied = hipMemcpyAsync(d_tab + tab_words + hyp_total, ref_labels + h_roff[0], (size_t)ref_total * sizeof(int32_t),
+                            hipMemcpyDeviceToDevice, st);
+  if (copied == hipSuccess) copied = hipStreamSynchronize(st);  // (the table leaves pageable host memory)
+  hipError_t launched = copied;
+  if (copied == hipSuccess) {
+    CtcMwer m = {};
+    m.logits = logits; m.ld = (int)ld; m.O = O; m.T = T; m.U = U; m.seg = seg;
+    m.P = P; m.NP = NP; m.PR = PR; m.sext = sext; m.max_hyp = max_hyp; m.ctc_weight = ctc_weight;
+    m.tab = d_tab; m.labels = d_tab + tab_words;
+    ctc_mwer_carve(scratch + ints, &m);
+    m.risk = risk; m.score = score; m.edits = edits;
+    ctc_mwer(st, m, dlogits, (int)ldd, h_seg[0], h_seg[U] - h_seg[0], Twin());
+    launched = hipGetLastError();
+  }
+  const hipError_t freed = hipFreeAsync(scratch, st);  // also when a copy or the launch failed
   HIPCHK(launched);
   HIPCHK(freed);
   return 0;

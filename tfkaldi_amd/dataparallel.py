@@ -117,8 +117,71 @@ class CtcMicroBatch(object):
         self.context_width, self.cmvn = context_width, cmvn  # context_width set: X holds UNSPLICED frames
 
 
+class CtcMwerMicroBatch(CtcMicroBatch):
+    """A CTC micro-batch trained on the expected number of label errors over an N-best list (tfk_accumulate_ctc_mwer) plus
+    ctc_weight x the CTC loss.  It carries EITHER the pair tables (hyp_counts, hyp_labels, hyp_lens as Engine.ctc_score takes
+    them) OR the settings of the search that finds the list: then the rank that trains the micro-batch decodes its N best
+    itself, on the same engine, right before the accumulate (beam_width, top_paths; lm: an NgramLM that ranks the search;
+    label_topk: the pruned search).  add_reference: the reference joins every list that lacks it."""
+
+    def __init__(self, X, utt_lens, labels, label_lens, context_width=None, cmvn=None, hyp_counts=None, hyp_labels=None,
+                 hyp_lens=None, beam_width=None, top_paths=None, lm=None, label_topk=None, add_reference=False,
+                 ctc_weight=0.0):
+        CtcMicroBatch.__init__(self, X, utt_lens, labels, label_lens, context_width, cmvn)
+        tables = hyp_counts is not None
+        if tables == (beam_width is not None):
+            raise ValueError("a CtcMwerMicroBatch carries either the pair tables or the search settings (beam_width)")
+        if tables and (hyp_labels is None or hyp_lens is None):
+            raise ValueError("pair tables: hyp_counts, hyp_labels and hyp_lens go together")
+        if not tables:
+            top_paths = beam_width if top_paths is None else top_paths
+            if not 1 <= int(top_paths) <= int(beam_width):
+                raise ValueError("top_paths %r outside [1, beam_width = %r]" % (top_paths, beam_width))
+        self.hyp_counts, self.hyp_labels, self.hyp_lens = hyp_counts, hyp_labels, hyp_lens
+        self.beam_width, self.top_paths, self.lm, self.label_topk = beam_width, top_paths, lm, label_topk
+        self.add_reference, self.ctc_weight = bool(add_reference), float(ctc_weight)
+
+
+def _mwer_tables(engine, mb):
+    """the pair tables of an MWER micro-batch: its own, or the N best of a search on `engine` (evaluation passes that leave
+    the sums of an open step alone); padding paths -- beam score -inf -- are dropped, as _label_errors drops them"""
+    import numpy as np
+    from .neuralNetworks.ctc_mwer import pair_tables
+    refs = np.split(np.asarray(mb.labels, dtype=np.int32), np.cumsum(mb.label_lens, dtype=np.int64)[:-1])
+    if mb.hyp_counts is not None:
+        if not mb.add_reference:
+            return mb.hyp_counts, mb.hyp_labels, mb.hyp_lens
+        flat = np.split(np.asarray(mb.hyp_labels, dtype=np.int32), np.cumsum(mb.hyp_lens, dtype=np.int64)[:-1]) \
+            if len(mb.hyp_lens) else []
+        cuts = np.cumsum(mb.hyp_counts, dtype=np.int64)
+        hyps = [flat[int(a):int(b)] for a, b in zip(np.concatenate([[0], cuts[:-1]]), cuts)]
+        return pair_tables(hyps, refs, add_reference=True)
+    entry, kw = "ctc_beam", {"beam_width": mb.beam_width}
+    if mb.lm is not None:
+        entry, kw = "ctc_beam_lm", dict(kw, lm=mb.lm)
+    if mb.label_topk is not None:
+        kw = dict(kw, label_topk=mb.label_topk)
+    if mb.context_width is not None:
+        entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
+    found, beam = getattr(engine, entry)(mb.X, mb.utt_lens, top_paths=int(mb.top_paths), **kw)[:2]
+    kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+    return pair_tables(kept, refs, add_reference=mb.add_reference)
+
+
+def _accumulate_mwer(engine, mb, last, train):
+    counts, labels, lens = _mwer_tables(engine, mb)
+    if mb.context_width is not None:
+        engine.accumulate_ctc_mwer_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, counts, labels, lens,
+                                       ctc_weight=mb.ctc_weight, last=last, cmvn=mb.cmvn, train=train)
+    else:
+        engine.accumulate_ctc_mwer(mb.X, mb.utt_lens, mb.labels, mb.label_lens, counts, labels, lens,
+                                   ctc_weight=mb.ctc_weight, last=last, train=train)
+
+
 def _accumulate(engine, mb, last):
-    if isinstance(mb, CtcMicroBatch):
+    if isinstance(mb, CtcMwerMicroBatch):
+        _accumulate_mwer(engine, mb, last, True)
+    elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, last=last,
                                       cmvn=mb.cmvn)
@@ -133,7 +196,9 @@ def _accumulate(engine, mb, last):
 
 
 def _eval_accumulate(engine, mb):
-    if isinstance(mb, CtcMicroBatch):
+    if isinstance(mb, CtcMwerMicroBatch):
+        _accumulate_mwer(engine, mb, False, False)
+    elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, cmvn=mb.cmvn,
                                       train=False)

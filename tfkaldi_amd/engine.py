@@ -627,6 +627,54 @@ class Engine(object):
                                                labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
                                                0))
 
+    # ---- expected label errors over an N-best list (MWER) on top of ctc_weight x the CTC loss ----
+    @staticmethod
+    def _mwer_args(utt_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight):
+        hyp_counts = np.ascontiguousarray(hyp_counts, dtype=np.int32).reshape(-1)
+        hyp_labels = np.ascontiguousarray(hyp_labels, dtype=np.int32).reshape(-1)
+        hyp_lens = np.ascontiguousarray(hyp_lens, dtype=np.int32).reshape(-1)
+        if hyp_counts.size != utt_lens.size or np.any(hyp_counts < 0):
+            raise ValueError("hypotheses: %d counts (smallest %d) for %d utterances"
+                             % (hyp_counts.size, int(hyp_counts.min()) if hyp_counts.size else 0, utt_lens.size))
+        P = int(hyp_counts.sum(dtype=np.int64))
+        if hyp_lens.size != P or np.any(hyp_lens < 0) or int(hyp_lens.sum(dtype=np.int64)) != hyp_labels.size:
+            raise ValueError("hypotheses: %d label counts (sum %d) for %d hypotheses and %d labels"
+                             % (hyp_lens.size, int(hyp_lens.sum(dtype=np.int64)), P, hyp_labels.size))
+        ctc_weight = float(ctc_weight)
+        if not (np.isfinite(ctc_weight) and ctc_weight >= 0.0):
+            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
+        return hyp_counts, hyp_labels, hyp_lens, ctc_weight
+
+    def accumulate_ctc_mwer(self, X, utt_lens, labels, label_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight=0.0,
+                            last=False, train=True):
+        """One micro-batch of the MWER criterion (tfk_accumulate_ctc_mwer; the contract is stated in include/tfkaldi_hip.h):
+        the expected number of label errors over the utterances' hypothesis lists, on the train-mode logits of this pass,
+        plus ctc_weight x the CTC loss of the references.  X, utt_lens, labels (the references), label_lens as
+        accumulate_ctc; hyp_counts[u] hypotheses per utterance (0 allowed), hyp_labels back to back in pair order, hyp_lens
+        per pair, as ctc_score takes them (neuralNetworks/ctc_mwer.pair_tables builds the three from lists).  The step's
+        average (apply) is expected label errors per reference label + ctc_weight x CTC loss per label.
+        train=False: evaluation-mode forward, loss only."""
+        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
+        hyp_counts, hyp_labels, hyp_lens, ctc_weight = self._mwer_args(utt_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight)
+        fn = self.lib.tfk_accumulate_ctc_mwer if train else self.lib.tfk_eval_accumulate_ctc_mwer
+        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
+                 hyp_counts.ctypes.data_as(c_void_p), hyp_labels.ctypes.data_as(c_void_p),
+                 hyp_lens.ctypes.data_as(c_void_p), ctc_weight, _lib.LAST_MICROBATCH if (last and train) else 0))
+
+    def accumulate_ctc_mwer_raw(self, raw, utt_lens, context_width, labels, label_lens, hyp_counts, hyp_labels, hyp_lens,
+                                ctc_weight=0.0, last=False, cmvn=None, train=True):
+        """accumulate_ctc_mwer from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
+        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
+        hyp_counts, hyp_labels, hyp_lens, ctc_weight = self._mwer_args(utt_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight)
+        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
+        fn = self.lib.tfk_accumulate_ctc_mwer_raw if train else self.lib.tfk_eval_accumulate_ctc_mwer_raw
+        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
+                 label_lens.ctypes.data_as(c_void_p), hyp_counts.ctypes.data_as(c_void_p),
+                 hyp_labels.ctypes.data_as(c_void_p), hyp_lens.ctypes.data_as(c_void_p), ctc_weight,
+                 _lib.LAST_MICROBATCH if (last and train) else 0))
+
     # ---- the optimiser step in parts (data parallel: Adam per reduced span, see dataparallel.BucketReducer) ----
     def apply_begin(self):
         check(self.lib.tfk_apply_begin(self._h))

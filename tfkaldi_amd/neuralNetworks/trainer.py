@@ -389,3 +389,64 @@ class CTCTrainer(Trainer):
         if rescore_paths is not None:
             kw["rescore_paths"] = rescore_paths
         return self.dp.label_errors(self.engine, self._microbatches(inputs, targets), beam_width=beam_width, **kw)
+
+    # ---- training on the expected number of label errors over an N-best list (MWER) ----
+    def _mwer_microbatches(self, inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk, add_reference, hyps):
+        from ..dataparallel import CtcMwerMicroBatch
+        from .ctc_mwer import pair_tables
+        if hyps is None:
+            if beam_width is None:
+                raise ValueError("MWER needs an N-best list: give beam_width (and top_paths), or hyps")
+            top_paths = beam_width if top_paths is None else top_paths
+            if not 1 <= int(top_paths) <= int(beam_width):
+                raise ValueError("top_paths %r outside [1, beam_width = %r]" % (top_paths, beam_width))
+        elif len(hyps) != len(inputs):
+            raise ValueError("hyps: %d hypothesis lists for %d utterances" % (len(hyps), len(inputs)))
+        if lm is not None and (beam_width is None or hyps is not None):
+            raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm (and no hyps)")
+        if label_topk is not None and (beam_width is None or hyps is not None):
+            raise ValueError("label_topk prunes a beam search: give beam_width with label_topk (and no hyps)")
+        if not (np.isfinite(ctc_weight) and ctc_weight >= 0):
+            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
+        out = []
+        plan = [idx for idx in microbatch_indices(len(inputs), self.numutterances_per_minibatch) if idx]
+        plain = self._microbatches(inputs, targets)  # (one per non-empty group that holds frames, in plan order)
+        plan = [idx for idx in plan if sum(np.asarray(inputs[i]).shape[0] for i in idx) > 0]
+        assert len(plan) == len(plain)
+        for idx, mb in zip(plan, plain):
+            kw = dict(context_width=mb.context_width, cmvn=mb.cmvn, add_reference=add_reference, ctc_weight=ctc_weight)
+            if hyps is None:
+                kw.update(beam_width=int(beam_width), top_paths=int(top_paths), lm=lm, label_topk=label_topk)
+            else:
+                counts, labels, lens = pair_tables([hyps[i] for i in idx])
+                kw.update(hyp_counts=counts, hyp_labels=labels, hyp_lens=lens)
+            out.append(CtcMwerMicroBatch(mb.X, mb.utt_lens, mb.labels, mb.label_lens, **kw))
+        return out
+
+    def update_mwer(self, inputs, targets, beam_width=None, top_paths=None, ctc_weight=0.01, lm=None, label_topk=None,
+                    add_reference=False, hyps=None):
+        """One optimiser step on the EXPECTED NUMBER OF LABEL ERRORS over every utterance's N-best list (MWER,
+        tfk_accumulate_ctc_mwer; Prabhavalkar et al. 2018) plus ctc_weight x the CTC loss -- the criterion label_errors
+        reports, where update minimises the likelihood.  The list: the top_paths best (default: all beam_width) of a prefix
+        beam search of width beam_width, decoded in evaluation mode by the rank that trains the micro-batch right before it
+        does (lm: a ctc_lm.NgramLM ranks the search; label_topk: the pruned search, for models of more than 64 outputs); or
+        hyps, a list per utterance of label arrays, which skips the search.  add_reference: the reference joins every list
+        that lacks it.  The hypotheses are scored on the train-mode logits of the step itself.  Returns the step's loss:
+        expected label errors per reference label + ctc_weight x CTC loss per label, before the update."""
+        microbatches = self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
+                                               add_reference, hyps)
+        if not microbatches:
+            raise ValueError("CTCTrainer.update_mwer: the batch holds no frames (no micro-batch could be built from %d "
+                             "utterance(s))" % len(inputs))
+        loss = self.dp.train_step(self.engine, microbatches)
+        self._summarise(loss)
+        return loss
+
+    def evaluate_mwer(self, inputs, targets, beam_width=None, top_paths=None, ctc_weight=0.01, lm=None, label_topk=None,
+                      add_reference=False, hyps=None):
+        """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
+        if inputs is None or targets is None:
+            return None
+        microbatches = self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
+                                               add_reference, hyps)
+        return self.dp.eval_step(self.engine, microbatches)

@@ -23,6 +23,9 @@ kernel's time per frame step against K + 1.
 profiler's time of the ctc_score kernels and that time per frame step, the loss's forward family (tfk_eval_accumulate_ctc) on
 the same batch as the yardstick, the host alternative (the float64 numpy restatement of the tests, timed on utterance 0's
 pairs and scaled), how many utterances change their best hypothesis, and the best-path / rescored / oracle label error rates.
+`--mwer` runs the MWER leg alone: one step on the expected label errors over the N-best (tfk_accumulate_ctc_mwer, N = 10 and 100
+from the tool's own search at that width, ctc_weight 0.01) against one plain CTC step on the same build -- warm-up, 20 timed
+steps each, the median with the spread, the decode excluded and included, and the profiler's rows of the new kernels.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -66,6 +69,14 @@ def main():
         bias[O - 1] = 2.0
         eng.set(_lib.BIASES, eng.L, bias)
         score_leg(eng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
+        eng.close()
+        return
+    if "--mwer" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        bias = np.zeros(O, np.float32)
+        bias[O - 1] = 2.0
+        eng.set(_lib.BIASES, eng.L, bias)
+        mwer_leg(eng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
         eng.close()
         return
     if "--topk-only" in sys.argv:
@@ -348,6 +359,61 @@ def score_leg(eng, X, utt, labels, lab, case):
               % (case, W, len(flat), max(hn), ms, kern, kern * 1e3 / max(utt), kern / loss_kern, ed, host, len(kept[0]),
                  host * len(flat) / len(kept[0]), len(flat), moved, len(utt), gap, best_edits.sum() / total, rescored / total,
                  oracle / total, float(np.max(np.abs(scores[0] - s64)))))
+
+
+def _median_ms(call, warm=3, K=20):
+    """(median, smallest, largest) ms of K timed calls after `warm` untimed ones"""
+    for _ in range(warm):
+        call()
+    ts = []
+    for _ in range(K):
+        t0 = time.perf_counter()
+        call()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), min(ts), max(ts)
+
+
+def mwer_leg(eng, X, utt, labels, lab, case):
+    """the learning rate is set to zero first, so that every step sees the same model and the same lists"""
+    from tfkaldi_amd.neuralNetworks.ctc_mwer import pair_tables
+    for _ in range(40):
+        eng.halve_learning_rate()
+    K = 20
+
+    def ctc_step():
+        eng.accumulate_ctc(X, utt, labels, lab, last=True)
+        return eng.apply()
+    base = _median_ms(ctc_step)
+    eng.profile_begin()
+    for _ in range(K):
+        ctc_step()
+    base_rows = {s["name"]: s["total_ms"] / K for s in eng.profile_end()}
+    print("  mwer (%s): yardstick, one plain CTC step (tfk_accumulate_ctc + tfk_apply): median %.3f ms (%.3f .. %.3f), its loss "
+          "family (softmax, gather, both sweeps, gradient) %.3f ms" % ((case,) + base + (base_rows.get("softmax_xent", 0.0),)))
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    for N in (10, 100):
+        def decode():
+            found, beam = eng.ctc_beam(X, utt, beam_width=N, top_paths=N)[:2]
+            return pair_tables([[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)], refs)
+        counts, hl, hn = decode()
+
+        def step(tables=None):
+            c, l, n = tables if tables is not None else (counts, hl, hn)
+            eng.accumulate_ctc_mwer(X, utt, labels, lab, c, l, n, ctc_weight=0.01, last=True)
+            return eng.apply()
+        loss = step()
+        alone = _median_ms(step)
+        both = _median_ms(lambda: step(decode()))
+        eng.profile_begin()
+        for _ in range(K):
+            step()
+        rows = {s["name"]: s["total_ms"] / K for s in eng.profile_end()}
+        print("  mwer (%s) N=%3d: %d pairs, longest hypothesis %d labels, loss %.4f; one MWER step median %.3f ms (%.3f .. %.3f) "
+              "= %.2f x the CTC step; with the decode %.3f ms (%.3f .. %.3f) = %.2f x; kernels per step: sweep %.3f ms "
+              "(%.2f x the CTC loss family), weights %.3f ms, gradient %.3f ms"
+              % ((case, N, int(np.sum(counts)), int(max(hn)), loss) + alone + (alone[0] / base[0],) + both + (both[0] / base[0],)
+                 + (rows.get("ctc_mwer_sweep", 0.0), rows.get("ctc_mwer_sweep", 0.0) / max(base_rows.get("softmax_xent", 0.0), 1e-9),
+                    rows.get("ctc_mwer_weights", 0.0), rows.get("ctc_mwer_grad", 0.0))))
 
 
 def align_leg(eng, X, utt, labels, lab, case):
