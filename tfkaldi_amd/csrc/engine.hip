@@ -82,6 +82,12 @@ struct ProfRec {
   int family;
   hipEvent_t a, b;
   double flops, bytes;
+  // An apply kernel behind a dual launch with EPI_DACT_BN: slot of tfk_engine::bnb_log that holds a copy of that launch's mode
+  // word, and the value it has when the dA blocks did the pass (then this launch moved nothing and the dual launch moved
+  // `bytes_moved` more than it was booked for); -1: no such launch in front
+  int bnb_slot = -1;
+  unsigned bnb_value = 0;
+  double bytes_moved = 0;
 };
 
 }  // namespace
@@ -171,6 +177,13 @@ struct tfk_engine {
                                  // (colsum_loss, launched with the loss sum right behind softmax_xent)
   bool fuse_hb_enabled = true;   // env TFK_FUSE_HB=0: separate statistics pass (experiments)
   bool dual_gemm = true;         // env TFK_DUAL_GEMM=0: dA and dW of a layer as two launches
+  // Batch norm's backward inside the dA blocks of the fp32-emulating dual launch (gemm_bf16.h: BnbArgs).  env TFK_X3_FUSE_BNB:
+  // 1 (default) where the shapes allow it, 0 never, 2 the launch always decides UNFUSED (its fallback, for tests)
+  int x3_fuse_bnb = 1;
+  unsigned* bnb_words = nullptr;  // the launches' sync words, zero from creation
+  unsigned bnb_gen = 0;           // generation of the last such launch
+  unsigned* bnb_log = nullptr;    // profiling only: the mode word as every such launch left it (kBnbLogSlots copies, stream order)
+  int bnb_log_n = 0;
   bool stack_enabled = true;     // env TFK_STACK=0: tfk_accumulate_stacked* run their micro-batches one after the other
   bool fuse_eval = true;         // env TFK_FUSE_EVAL=0: evaluation-mode layers as GEMM + bn_stats_eval + act_forward
   int post_chunk = 2048;         // env TFK_POST_CHUNK: rows per chunk of a pipelined tfk_posteriors pass (0: off)
@@ -370,6 +383,7 @@ hipEvent_t get_event(tfk_engine* e) {
   }
   return e->ev_pool[e->ev_next++];
 }
+constexpr int kBnbLogSlots = 256;
 struct ProfScope {
   tfk_engine* e;
   ProfRec r;
@@ -559,7 +573,10 @@ int run_gemm(tfk_engine* e, GemmLayout layout, const float* A, int lda, const fl
 // ONE launch (gemm_f32_dual).  Returns 1 when the pair is not eligible (the caller launches them separately).
 int run_gemm_dual(tfk_engine* e, const float* dz, int ld_dz, const float* W, int ldw, float* da_out, int ld_da, int T,
                   int N_da, int K_da, const ActEpi* act, float* stats, const float* in, int ld_in, float* Gw, int ld_g,
-                  int d_in, int d_out, int epi_w, int* chunk_rows) {
+                  int d_in, int d_out, int epi_w, int* chunk_rows, const Twin* bnb_twin = nullptr, unsigned* bnb_done = nullptr) {
+  // bnb_twin: where dz of the layer `act` describes goes as operand planes -- the launch may then do that layer's batch-norm
+  // backward too (EPI_DACT_BN); *bnb_done = the value the launch's mode word holds when it did (0: not such a launch)
+  if (bnb_done) *bnb_done = 0;
   if (!e->dual_gemm) return 1;
   const double flops = 2.0 * T * N_da * K_da + 2.0 * d_in * d_out * T;
   const double out_w = (double)d_in * d_out * ((epi_w & EPI_ACCUM) ? 2 : 1);
@@ -576,13 +593,38 @@ int run_gemm_dual(tfk_engine* e, const float* dz, int ld_dz, const float* W, int
     if (!a.A || !a.B || !w.A || !w.B) return fail(-1, "internal: GEMM operand without a bf16 twin");
     a.C = da_out;
     fill_epilogue(a, act, stats, nullptr);
+    // (where a kernel of this launch reports a wait that ran out: the rendezvous of EPI_DACT_BN; check_kernel_errors)
+    if (e->x3) a.err = reinterpret_cast<unsigned*>(e->h_scalars_dev + kErrWord);
     a.M = T; a.N = N_da; a.K = K_da; a.lda = ld_a; a.ldb = ld_b; a.ldc = ld_da; a.epi = act ? EPI_DACT : 0;
     w.C = Gw;
     w.M = d_in; w.N = d_out; w.K = T; w.lda = ld_c; w.ldb = ld_d; w.ldc = ld_g; w.epi = epi_w;
     const double ob = e->x3 ? 6.0 : 2.0;  // operand bytes per element: one bf16 value, or three planes
     ProfScope ps(e, KF_GEMM_DUAL, flops, ob * ((double)T * K_da + (double)K_da * N_da) + 4.0 * (double)T * N_da +
                                              ob * ((double)T * d_in + (double)T * d_out) + 4.0 * out_w);
-    const int rc = e->x3 ? gemm_bf16x3_dual(a, w, e->stream) : gemm_bf16_dual(a, w, e->stream);
+    int rc = -1;
+    if (e->x3 && act && bnb_twin && bnb_twin->p && bnb_twin->x3 && bnb_done && e->x3_fuse_bnb != 0) {
+      BnbArgs bn = {};
+      bn.words = e->bnb_words;
+      bn.gen = e->bnb_gen + 1;
+      if (bn.gen >= (1u << 30)) {  // the generations start over, from zeroed words (consecutive launches alternate sets)
+        HIPCHK(hipMemsetAsync(e->bnb_words, 0, kBnbWords * sizeof(unsigned), e->stream));
+        bn.gen = 1;
+      }
+      bn.force_unfused = e->x3_fuse_bnb == 2;
+      bn.rows_per = hidden_backward_rows_per(T);
+      bn.rs = row_splits(T);
+      bn.nt = hidden_backward_nt_mode(*bnb_twin, T, ld_da);
+      bn.twin = bnb_twin->p;
+      bn.ld_twin = bnb_twin->ld;
+      a.epi = EPI_DACT_BN;
+      rc = gemm_bf16x3_dual_bnb(a, w, bn, kMergeOnceChunks, e->stream);
+      if (rc == 0) {
+        e->bnb_gen = bn.gen;
+        *bnb_done = bnb_fused_value(bn.gen);
+      }
+      a.epi = EPI_DACT;
+    }
+    if (rc == -1) rc = e->x3 ? gemm_bf16x3_dual(a, w, e->stream) : gemm_bf16_dual(a, w, e->stream);
     if (rc != 0) ps.drop();
     if (rc == -1) return 1;
     if (rc != 0) return fail(rc, "gemm_bf16%s_dual launch failed: %s", e->x3 ? "x3" : "", hipGetErrorString((hipError_t)rc));
@@ -1080,11 +1122,19 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
     return run_gemm(e, GEMM_NT, dz, ld_dz, W, ldw, out, ldH, T, H, K, nullptr, EPI_DACT, nullptr, ws_of(target), cfg, &act);
   };
   int bm_in = rows_o;  // rows per chunk of the EPI_DACT partial sums of the GEMM that produced the current `da`
+  // the operand planes of dz that belong to e->dA[q]; the dual launch that produces dA[q] may write them itself (EPI_DACT_BN)
+  auto twin_of_da = [&](int q) {
+    Twin tw;
+    if (e->bf16) { tw.p = e->dAb[q]; tw.ld = e->ldHb; tw.x3 = e->x3; }
+    return tw;
+  };
+  unsigned bnb_done = 0;  // what the mode word of the launch that produced the current `da` holds if it did BN backward too
   {
     const ActEpi act = act_of(nact - 1);
+    const Twin tw0 = twin_of_da(pp);
     const int rc = run_gemm_dual(e, e->logits, e->ldO, e->p_param() + o.w_off, o.ld_out, e->dA[pp], ldH, T, H, e->O,
                                  fuse_hb ? &act : nullptr, fuse_hb ? ws_of(nact - 1) : nullptr, e->a[nact - 1], ldH,
-                                 G + o.w_off, o.ld_out, H, e->O, epi_w, &bm_in);
+                                 G + o.w_off, o.ld_out, H, e->O, epi_w, &bm_in, st ? nullptr : &tw0, &bnb_done);
     if (rc < 0) return rc;
     if (rc > 0) {
       CHK(run_gemm(e, GEMM_TN, e->a[nact - 1], ldH, e->logits, e->ldO, G + o.w_off, o.ld_out, H, e->O, T, nullptr, epi_w));
@@ -1111,8 +1161,7 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
         fin.n = 0;
       }
     };
-    Twin tw;
-    if (e->bf16) { tw.p = e->dAb[pp]; tw.ld = e->ldHb; tw.x3 = e->x3; }
+    const Twin tw = twin_of_da(pp);
     if (st) {
       if (!fuse_hb || stack_align(e) % bm_in || chunks_in > kMaxRowSplits)
         return fail(-1, "internal: EPI_DACT chunks of %d rows do not fit a stacked pass of %d rows", bm_in, T);
@@ -1139,24 +1188,42 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
         act_backward_rows(e->stream, d, da, e->v[l], e->rowscale[l], T, H, ldH);
         pre_du = 1;
       }
+      // (profiling: what the dual launch in front decided is known only on the device -- a copy of its mode word, taken here in
+      // stream order, lets tfk_profile_end book this launch's bytes where they were moved)
+      int bnb_slot = -1;
+      if (e->profiling && bnb_done && e->bnb_log && e->bnb_log_n < kBnbLogSlots) {
+        bnb_slot = e->bnb_log_n++;
+        HIPCHK(hipMemcpyAsync(e->bnb_log + bnb_slot, e->bnb_words, sizeof(unsigned), hipMemcpyDeviceToDevice, e->stream));
+      }
       ProfScope ps(e, KF_HIDDEN_BWD, 0, (e->cfg.batch_norm ? 28.0 : 12.0) * T * H);
+      if (ps.live && bnb_slot >= 0) {
+        ps.r.bnb_slot = bnb_slot;
+        ps.r.bnb_value = bnb_done;
+        // fused, the dual launch reads z (4 B) and writes the three planes of dz (6 B) instead of du (4 B) per element
+        ps.r.bytes_moved = 6.0 * T * H;
+      }
       int chunks_eff = fuse_hb ? chunks_in : 0;
       if (chunks_eff > kMergeOnceChunks) {  // tall micro-batch: reduce the EPI_DACT partial sums once
         chunk_totals(e->stream, ws_of(l), chunks_eff, ldH);
         chunks_eff = 1;
       }
-      hidden_backward(e->stream, d, pre_du, da, e->a[l], e->z[l], mean[l], rstd[l], T, H, ldH, ws_of(l), chunks_eff, tw);
+      // (behind a dual launch with EPI_DACT_BN the apply kernel is enqueued all the same: its blocks read the launch's
+      // decision and return at once when the dA blocks have done this pass)
+      hidden_backward(e->stream, d, pre_du, da, e->a[l], e->z[l], mean[l], rstd[l], T, H, ldH, ws_of(l), chunks_eff, tw, 0, nullptr,
+                      bnb_done ? e->bnb_words : nullptr, bnb_done);
       fin_layer(fuse_hb ? chunks_eff : rs, rs);
     }
     const float* in = l == 0 ? Xd : e->a[l - 1];
     const int ld_in = l == 0 ? ldx : ldH;
     bool fused = false;
     bm_in = rows_h;
+    bnb_done = 0;
     if (l > 0) {  // dW_l and the dA that feeds layer l - 1 both read dz_l: one launch when eligible
       const ActEpi act = act_of(l - 1);
+      const Twin twn = twin_of_da(pp ^ 1);
       const int rc = run_gemm_dual(e, da, ldH, e->p_param() + y.w_off, y.ld_out, e->dA[pp ^ 1], ldH, T, H, H,
                                    fuse_hb ? &act : nullptr, fuse_hb ? ws_of(l - 1) : nullptr, in, ld_in, G + y.w_off,
-                                   y.ld_out, y.d_in, H, epi_w, &bm_in);
+                                   y.ld_out, y.d_in, H, epi_w, &bm_in, st ? nullptr : &twn, &bnb_done);
       if (rc < 0) return rc;
       fused = rc == 0;
     }
@@ -1185,8 +1252,11 @@ int check_kernel_errors(tfk_engine* e) {
   *w = 0;
   if (e->ws_splitk)  // (flag words of the interrupted exchange may be left set: start the next launch from zeros)
     (void)hipMemsetAsync(e->ws_splitk, 0, e->ws_splitk_floats * sizeof(float), e->stream);
+  if (e->bnb_words) (void)hipMemsetAsync(e->bnb_words, 0, kBnbWords * sizeof(unsigned), e->stream);  // (and the dual launch's words)
   return fail(-1, "split-K exchange timed out: a block of the fp32-emulating contraction waited ~1 s for its partner's partial "
-                  "sums (workspace not zeroed, or the partner block failed); the results of this step are invalid");
+                  "sums (workspace not zeroed, or the partner block failed) -- or the rendezvous of the dual launch did (EPI_DACT_BN: a "
+                  "dA block waited ~1 s for the column sums of the other row tiles of its block column; sync words not zero, or "
+                  "another block failed); the results of this step are invalid");
 }
 
 int settle_scalars(tfk_engine* e) {
@@ -1308,6 +1378,7 @@ int create_impl(const tfk_config* cfg, void* state, size_t state_bytes, void* st
     if ((v = getenv("TFK_FUSE_HB"))) e->fuse_hb_enabled = atoi(v) != 0;
     if ((v = getenv("TFK_POST_CHUNK"))) e->post_chunk = atoi(v) > 0 ? (int)up((size_t)atoi(v), 64) : 0;
     if ((v = getenv("TFK_DUAL_GEMM"))) e->dual_gemm = atoi(v) != 0;
+    if ((v = getenv("TFK_X3_FUSE_BNB"))) e->x3_fuse_bnb = atoi(v);
     if ((v = getenv("TFK_STACK"))) e->stack_enabled = atoi(v) != 0;
     if ((v = getenv("TFK_LOSS_EVENT"))) e->loss_event = atoi(v) != 0;
     if ((v = getenv("TFK_SLOT_EVENT"))) e->slot_lazy = atoi(v) == 0;
@@ -1329,6 +1400,9 @@ int create_impl(const tfk_config* cfg, void* state, size_t state_bytes, void* st
     for (int l = 0; l <= e->L; ++l) HIPB(hipEventCreateWithFlags(&e->ev_adam[l], hipEventDisableTiming));
   }
   HIPB(hipMalloc((void**)&e->d_snap, 16 * sizeof(float)));
+  HIPB(hipMalloc((void**)&e->bnb_words, kBnbWords * sizeof(unsigned)));
+  HIPB(hipMemset(e->bnb_words, 0, kBnbWords * sizeof(unsigned)));
+  HIPB(hipMalloc((void**)&e->bnb_log, kBnbLogSlots * sizeof(unsigned)));
   HIPB(hipEventCreateWithFlags(&e->ev_loss, hipEventDisableTiming));
   HIPB(hipEventCreateWithFlags(&e->ev_grow, hipEventDisableTiming));
   for (int s = 0; s < 2; ++s) {
@@ -2021,6 +2095,8 @@ int tfk_destroy(tfk_engine* e) {
   for (hipEvent_t ev : e->ev_adam) if (ev) hipEventDestroy(ev);
   if (e->opt_stream) hipStreamDestroy(e->opt_stream);
   if (e->d_snap) hipFree(e->d_snap);
+  if (e->bnb_words) hipFree(e->bnb_words);
+  if (e->bnb_log) hipFree(e->bnb_log);
   for (auto p : e->mean) if (p) hipFree(p);
   for (auto p : e->seg_mean) if (p) hipFree(p);
   for (auto p : e->seg_rstd) if (p) hipFree(p);
@@ -3413,6 +3489,7 @@ int tfk_profile_begin(tfk_engine* e) {
   if (!e) return fail(-1, "engine is NULL");
   e->prof.clear();
   e->ev_next = 0;
+  e->bnb_log_n = 0;
   e->profiling = true;
   return 0;
 }
@@ -3424,13 +3501,20 @@ int tfk_profile_end(tfk_engine* e, tfk_kernel_stat* stats, int capacity, int* co
   tfk_kernel_stat acc[KF_COUNT];
   memset(acc, 0, sizeof(acc));
   for (int f = 0; f < KF_COUNT; ++f) snprintf(acc[f].name, sizeof(acc[f].name), "%s", kFamilyName[f]);
+  std::vector<unsigned> bnb_log(e->bnb_log_n);
+  if (e->bnb_log_n > 0) HIPCHK(hipMemcpy(bnb_log.data(), e->bnb_log, bnb_log.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+  e->bnb_log_n = 0;
   for (const ProfRec& r : e->prof) {
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
     acc[r.family].launches += 1;
     acc[r.family].total_ms += ms;
     acc[r.family].flops += r.flops;
-    acc[r.family].bytes += r.bytes;
+    // an apply kernel whose pass the dA blocks of the dual launch in front did (EPI_DACT_BN, decided FUSED) returned at once:
+    // nothing moved here, and the dual launch moved the difference
+    const bool fused = r.bnb_slot >= 0 && r.bnb_slot < (int)bnb_log.size() && bnb_log[r.bnb_slot] == r.bnb_value;
+    acc[r.family].bytes += fused ? 0.0 : r.bytes;
+    if (fused) acc[KF_GEMM_DUAL].bytes += r.bytes_moved;
   }
   int n = 0;
   for (int f = 0; f < KF_COUNT; ++f)

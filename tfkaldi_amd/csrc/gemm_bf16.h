@@ -105,6 +105,38 @@ size_t gemm_bf16x3_splitk_floats(GemmLayout layout, int M, int N, int K);
 // (as gemm_bf16_dual; -1: not eligible -- fewer than a tile per CU between them).  Rows per EPI_DACT chunk: kGemmBf16x3TileRows.
 int gemm_bf16x3_dual(const GemmArgsB& nt, const GemmArgsB& tn, hipStream_t stream);
 
+// EPI_DACT_BN: the NT half of gemm_bf16x3_dual also does the work of the column-tiled apply kernel behind it (kernels.hip:
+// hb_apply_kernel) -- dz of batch norm's backward from du and the column means over ALL row tiles, the three operand planes of
+// dz, the per-chunk column sums of dz -- in the time its blocks would otherwise idle while the dW blocks finish.  The means
+// need every row tile of a block column, so the tiles of a column meet (8 of them at 1024 frames).
+// Waiting for another block is safe only when that block is running.  Per launch:
+//   * every dA block adds 1 to `started` when it begins;
+//   * the first dA block to finish its K loop decides for the whole launch, once (compare-and-swap on `mode`): FUSED when
+//     all dA blocks had started by then, UNFUSED otherwise (a GPU shared with other processes, a grid that is not resident at
+//     once).  A block that has started never waits before its arrival -- the dual launch has no split-K hand-over, its K loop
+//     synchronises inside the block only -- so in a FUSED launch every wait is bounded by the skew between blocks' K loops,
+//     whatever else runs on the GPU;
+//   * UNFUSED: the blocks run the EPI_DACT epilogue, and the apply kernel that follows does its work as ever.  FUSED: du is
+//     not written at all and the apply kernel's blocks return when they read `mode` (hidden_backward: done_word).
+// The words: word 0 = mode = (gen << 2) | {1 FUSED, 2 UNFUSED}; two sets of {started, one arrival counter per block column}
+// used by launches of even / odd `gen` in turn -- the block that decides a launch zeroes the OTHER set, which the launch
+// before it (complete, in stream order) was the last to touch.  All zero before the first launch; no memset in between.
+constexpr int kBnbSetWords = 512, kBnbMaxCols = kBnbSetWords - 64, kBnbWords = 64 + 2 * kBnbSetWords;
+struct BnbArgs {
+  unsigned* words;    // kBnbWords of them, launches in stream order
+  unsigned gen;       // this launch's generation: 1, 2, .. (below 2^30), consecutive
+  int force_unfused;  // the decision is UNFUSED whatever `started` says (tests)
+  int rows_per, rs;   // the apply kernel's rows per block (divides 128) and its number of blocks along T
+  int nt;             // its store mode (bit 1: streaming stores of the planes)
+  bf16_t* twin;       // dz as three planes (x3_layout.h), leading dimension ld_twin
+  int ld_twin;
+};
+inline unsigned bnb_fused_value(unsigned gen) { return (gen << 2) | 1u; }
+// As gemm_bf16x3_dual with nt.epi == EPI_DACT_BN.  -1 also when the shapes do not allow the fused epilogue
+// (x3_layout.h: dual_bnb_eligible, `max_tiles` = the apply kernel's limit of per-tile sums) or when nt.err is not set (a
+// rendezvous whose bounded wait ran out must be able to say so): launch with EPI_DACT instead.
+int gemm_bf16x3_dual_bnb(const GemmArgsB& nt, const GemmArgsB& tn, const BnbArgs& bn, int max_tiles, hipStream_t stream);
+
 // rows of the block tile gemm_bf16 uses for an [M, N] result (= rows per EPI_COLSTATS / EPI_DACT chunk)
 int gemm_bf16_tile_rows(int M, int N);
 

@@ -30,6 +30,7 @@
 //         operands are k-strided, so a slot may be any multiple of 16 k deep) on a PING-PONG schedule: see SCHED 2.
 // (2) register-staged ring of round 1 (configs 0-2; kept for A/B runs: tools/gemm_bf16_sweep.py).
 #include "gemm_bf16.h"
+#include "hb_math.h"
 #include "x3_layout.h"
 
 #include <math.h>
@@ -83,7 +84,9 @@ __device__ __forceinline__ uint16_t f2bf(float x) { return __builtin_bit_cast(ui
 // per-lane operand: a register outside the matrix is dropped by the range check, and a store is one address addition + the
 // store -- the flat form costs twelve instructions per register (two compares, a 64-bit multiply-add, an exec-mask branch),
 // ~2 us of issue time per 128x128 tile on eight waves.  The caller guarantees M * ldc * 4 < 2^31.
-template <int EPI, int WAVES_M, int WAVES_N, int FM, int FN, bool CBUF = false>
+// SUMS_ONLY (EPI_DACT, the fused batch-norm backward -- epilogue_dact_bn): du stays in the accumulators and is not stored; the
+// two column sums are written THROUGH to memory (sc0 sc1), where the other row tiles of the block column fetch them.
+template <int EPI, int WAVES_M, int WAVES_N, int FM, int FN, bool CBUF = false, bool SUMS_ONLY = false>
 __device__ __forceinline__ void epilogue(const GemmArgsB& p, f32x16 (&acc)[FM][FN], int tiles_m, int tm, int m0, int n0,
                                          int wm, int wn, int i, int h, float* red) {
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
@@ -208,10 +211,21 @@ __device__ __forceinline__ void epilogue(const GemmArgsB& p, f32x16 (&acc)[FM][F
           t1 += red[(0 * WAVES_M + w) * BN + cidx];
           t2 += red[(1 * WAVES_M + w) * BN + cidx];
         }
-        p.stats[((size_t)0 * p.stats_stride + tm) * p.ldc + col] = t1;
-        p.stats[((size_t)1 * p.stats_stride + tm) * p.ldc + col] = t2;
+        if constexpr (SUMS_ONLY) {
+          const __amdgpu_buffer_rsrc_t srs =
+              __builtin_amdgcn_make_buffer_rsrc((void*)p.stats, 0, (int)((unsigned)(2 * p.stats_stride) * p.ldc * 4u), 0x00020000);
+          constexpr int kSys = 1 | (1 << 4);  // sc0 sc1
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t1), srs,
+                                                ((unsigned)(0 * p.stats_stride + tm) * p.ldc + col) * 4u, 0, kSys);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t2), srs,
+                                                ((unsigned)(1 * p.stats_stride + tm) * p.ldc + col) * 4u, 0, kSys);
+        } else {
+          p.stats[((size_t)0 * p.stats_stride + tm) * p.ldc + col] = t1;
+          p.stats[((size_t)1 * p.stats_stride + tm) * p.ldc + col] = t2;
+        }
       }
       __syncthreads();
+      if constexpr (SUMS_ONLY) continue;
     }
     if constexpr (CBUF) {
       static_assert((EPI & EPI_EVAL_ACT) == 0, "no bf16 twin on this path");
@@ -268,6 +282,148 @@ __device__ __forceinline__ void epilogue(const GemmArgsB& p, f32x16 (&acc)[FM][F
         }
       }
     }
+  }
+}
+
+// ---- EPI_DACT_BN: batch norm's backward in the dA blocks of the fp32-emulating dual launch (gemm_bf16.h: BnbArgs) --------------
+// Called by every thread of a 128x128 dA block (8 waves of 64x32) behind its K loop's last barrier; `smem` is the drained ring.
+// TFKB_TL(event, tile of the block's list) (tools/ubench/x3_dual_timeline.hip only): a time stamp per block and tile at entry,
+// in front of the first MFMA, behind the last one and behind the epilogue (dma_tile); event 4, here: the block's arrival at its
+// column's rendezvous.  Nothing in the library.
+#ifndef TFKB_TL
+#define TFKB_TL(ev, ti)
+#endif
+constexpr int kBnbDuLd = 132;  // floats per row of the du tile in LDS (528 B: 16-byte aligned quads, rows 4 apart 16 banks apart)
+constexpr int kBnbDuOff = 4096, kBnbSmOff = kBnbDuOff + 128 * kBnbDuLd * 4, kBnbMeanOff = kBnbSmOff + 2 * 8 * 32 * 16;
+static_assert(kBnbMeanOff + 2 * 2 * 32 * 16 <= 3 * 3 * (128 + 128) * 32 * 2, "the fused epilogue's scratch lies inside the ring");
+template <int WAVES_M, int WAVES_N, int FM, int FN>
+__device__ __forceinline__ void epilogue_dact_bn(const GemmArgsB& p, const BnbArgs& bn, f32x16 (&acc)[FM][FN], int tiles_m, int n_da,
+                                                 int tm, int m0, int n0, int wm, int wn, int i, int h, char* smem) {
+  static_assert(WAVES_M == 2 && WAVES_N == 4 && FM == 2 && FN == 1, "128x128 block of eight 64x32 waves");
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x;
+  unsigned* const set = bn.words + 64 + (bn.gen & 1u) * kBnbSetWords;        // {started, -, .., arrival counter of column c at 64 + c}
+  unsigned* const other = bn.words + 64 + ((bn.gen & 1u) ^ 1u) * kBnbSetWords;
+  unsigned* sh = reinterpret_cast<unsigned*>(smem);
+  if (tid == 0) {
+    // the launch's decision, taken once by whoever gets here first
+    unsigned m = __hip_atomic_load(bn.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned won = 0;
+    if ((m >> 2) != bn.gen) {
+      const unsigned started = __hip_atomic_load(set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned want = (bn.gen << 2) | ((started == (unsigned)n_da && !bn.force_unfused) ? 1u : 2u);
+      // (a failed exchange leaves the winner's value in m: the word changes once per launch)
+      if (__hip_atomic_compare_exchange_strong(bn.words, &m, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        m = want;
+        won = 1;
+      }
+    }
+    sh[0] = m & 3u;
+    sh[1] = won;
+  }
+  __syncthreads();
+  const bool fused = sh[0] == 1u;
+  if (sh[1]) {  // the other set, for the next launch: the launch before this one is complete, nobody else touches it
+    for (int w = tid; w < kBnbSetWords; w += WAVES_M * WAVES_N * 64) __hip_atomic_store(other + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();  // (sh is the epilogue's `red`)
+  if (!fused) {
+    epilogue<EPI_DACT, WAVES_M, WAVES_N, FM, FN, true>(p, acc, tiles_m, tm, m0, n0, wm, wn, i, h, reinterpret_cast<float*>(smem));
+    return;
+  }
+  // du = acc * f' in the accumulators, the tile's two column sums written through to the slots grad_final reads as well
+  epilogue<EPI_DACT, WAVES_M, WAVES_N, FM, FN, true, true>(p, acc, tiles_m, tm, m0, n0, wm, wn, i, h, reinterpret_cast<float*>(smem));
+  float* const du_s = reinterpret_cast<float*>(smem + kBnbDuOff);
+#pragma unroll
+  for (int a = 0; a < FM; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      du_s[((wm * FM + a) * 32 + 4 * h + (r & 3) + 8 * (r >> 2)) * kBnbDuLd + wn * 32 + i] = acc[a][0][r];
+  // the apply kernel's thread geometry, two of its blocks side by side: 32 quads of columns x 8 row lanes each
+  const int vb = tid >> 8, y = (tid >> 5) & 7, x = tid & 31;
+  const int ld = p.ldc, T = p.M, H = p.N;
+  const int col = n0 + 4 * x;
+  const bool valid = col < ld;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 mu = zero4, rsd = zero4;
+  if (valid) {
+    mu = *reinterpret_cast<const float4*>(p.act_mean + col);
+    rsd = *reinterpret_cast<const float4*>(p.act_rstd + col);
+  }
+  // the sums are acknowledged by memory before the arrival is counted
+  asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+  __syncthreads();
+  TFKB_TL(4, 0);
+  if (tid == 0) {
+    unsigned* const arrived = set + 64 + n0 / 128;
+    __hip_atomic_fetch_add(arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // Every block of this column has started (the decision above) and nothing makes a started block wait before it arrives:
+    // the others are at most their K loops' skew away.  The bound -- about a second, as for the split-K hand-over -- only
+    // keeps broken sync words from hanging the device; the host fails the step on p.err.
+    int spin = 0;
+    for (; spin < (1 << 23) && __hip_atomic_load(arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)tiles_m; ++spin)
+      __builtin_amdgcn_s_sleep(2);
+    if (spin == (1 << 23) && p.err) __hip_atomic_store(p.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  __syncthreads();
+  // column means of du and du * xhat over all row tiles, in the apply kernel's order (hb_math.h)
+  float4(*const sm)[hb::kQuads] = reinterpret_cast<float4(*)[hb::kQuads]>(smem + kBnbSmOff + vb * (8 * 32 * 16));
+  float4* const smm = reinterpret_cast<float4*>(smem + kBnbMeanOff + vb * (2 * 32 * 16));
+  float4 p1 = zero4, p2 = zero4;
+  if (valid) {
+    const __amdgpu_buffer_rsrc_t srs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)p.stats, 0, (int)((unsigned)(2 * p.stats_stride) * ld * 4u), 0x00020000);
+    constexpr int kSys = 1 | (1 << 4);  // sc0 sc1: past every cache
+    for (int k = y; k < tiles_m; k += hb::kLanes) {
+      const f32x4 q1 = __builtin_bit_cast(
+          f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, ((unsigned)(0 * p.stats_stride + k) * ld + col) * 4u, 0, kSys));
+      const f32x4 q2 = __builtin_bit_cast(
+          f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, ((unsigned)(1 * p.stats_stride + k) * ld + col) * 4u, 0, kSys));
+      hb::add4(p1, make_float4(q1.x, q1.y, q1.z, q1.w));
+      hb::add4(p2, make_float4(q2.x, q2.y, q2.z, q2.w));
+    }
+  }
+  p1 = hb::sum_lanes(p1, sm, x, y);
+  p2 = hb::sum_lanes(p2, sm, x, y);
+  if (y == 0) {
+    const float invT = 1.f / (float)T;
+    smm[x] = hb::scale4(p1, invT);
+    smm[32 + x] = hb::scale4(p2, invT);
+  }
+  __syncthreads();
+  const float4 m1 = smm[x], m2 = smm[32 + x];
+  // the apply kernel's blocks of this tile, two at a time: rows r0 + y + 8 j of block k = first block of the tile + c
+  const int nc = 128 / bn.rows_per;
+  float* const ws_dz = p.stats + (size_t)2 * p.stats_stride * ld;
+  for (int c0 = 0; c0 < nc; c0 += 2) {
+    const int k = tm * nc + c0 + vb;
+    const bool live = valid && c0 + vb < nc && k < bn.rs;
+    const int r0 = k * bn.rows_per, r1 = live ? min(T, r0 + bn.rows_per) : r0;
+    float4 sz = zero4;
+    for (int rb = r0 + y; rb < r1; rb += hb::kLanes * 4) {
+      float4 zv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = rb + j * hb::kLanes;
+        zv[j] = *reinterpret_cast<const float4*>(p.act_z + (size_t)(r < r1 ? r : rb) * ld + col);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = rb + j * hb::kLanes;
+        if (r >= r1) continue;
+        const float4 du = *reinterpret_cast<const float4*>(du_s + (r - m0) * kBnbDuLd + 4 * x);
+        float4 dz = hb::dz4(du, zv[j], mu, rsd, m1, m2);
+        if (col + 0 >= H) dz.x = 0.f;
+        if (col + 1 >= H) dz.y = 0.f;
+        if (col + 2 >= H) dz.z = 0.f;
+        if (col + 3 >= H) dz.w = 0.f;
+        if (bn.nt & 2) hb::store_x3<true>(bn.twin, bn.ld_twin, (size_t)r, col, dz);
+        else hb::store_x3<false>(bn.twin, bn.ld_twin, (size_t)r, col, dz);
+        hb::add4(sz, dz);
+      }
+    }
+    sz = hb::sum_lanes(sz, sm, x, y);
+    if (y == 0 && live) *reinterpret_cast<float4*>(ws_dz + (size_t)k * ld + col) = sz;
   }
 }
 
@@ -469,12 +625,6 @@ struct Frag3 {
 #define TFKB_ABL 0
 #endif
 
-// TFKB_TL(event, tile of the block's list) (tools/ubench/x3_dual_timeline.hip only): a time stamp per block and tile at entry,
-// in front of the first MFMA, behind the last one and behind the epilogue.  Nothing in the library.
-#ifndef TFKB_TL
-#define TFKB_TL(ev, ti)
-#endif
-
 #define TFKB_WAIT_BARRIER(n) \
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" : : "n"(n) : "memory")
 
@@ -496,9 +646,16 @@ constexpr int kSplitXccWord = 2048;
 template <bool A_KC, bool B_KC, int EPI, int WAVES_M, int WAVES_N, int FM, int FN, int NS, int BKT = 64, int SCHED = 0,
           int NPL = 1, int KSPLIT = 1, int DUAL = 0>
 __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int tiles_n, int group_rows, int bid, char* smem,
-                                         int seq0 = 0, int ntiles = 1) {
+                                         int seq0 = 0, int ntiles = 1, const BnbArgs* bnb = nullptr) {
   static_assert(DUAL == 0 || (NPL == 3 && KSPLIT == 1), "the dual launch: the unsplit fp32-emulating contraction");
   constexpr bool LIST = DUAL == 2, CBUF = DUAL != 0;
+  // EPI_DACT_BN: a one-tile dA block of the dual launch that may do batch norm's backward as well (epilogue_dact_bn)
+  constexpr bool BNB = EPI == EPI_DACT_BN;
+  static_assert(!BNB || DUAL == 1, "EPI_DACT_BN: one-tile blocks of the dual launch only");
+  if constexpr (BNB) {
+    if (threadIdx.x == 0)  // "this block is running": what the launch's decision counts (gemm_bf16.h: BnbArgs)
+      __hip_atomic_fetch_add(bnb->words + 64 + (bnb->gen & 1u) * kBnbSetWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   constexpr int NTH = WAVES_M * WAVES_N * 64;
   constexpr int BM = WAVES_M * FM * 32, BN = WAVES_N * FN * 32;
   // (NPL == 3: one image per operand holds its three planes, x3_layout.h)
@@ -968,7 +1125,10 @@ __device__ __forceinline__ void dma_tile(const GemmArgsB& p, int tiles_m, int ti
           }
       __syncthreads();  // (the epilogue reuses smem)
     }
-    epilogue<EPI, WAVES_M, WAVES_N, FM, FN, CBUF>(p, acc, tiles_m, tm_out, m0_out, n0_out, wm, wn, i, h, red);
+    if constexpr (BNB)
+      epilogue_dact_bn<WAVES_M, WAVES_N, FM, FN>(p, *bnb, acc, tiles_m, tiles_m * tiles_n, tm_out, m0_out, n0_out, wm, wn, i, h, smem);
+    else
+      epilogue<EPI, WAVES_M, WAVES_N, FM, FN, CBUF>(p, acc, tiles_m, tm_out, m0_out, n0_out, wm, wn, i, h, red);
     TFKB_TL(3, ti);
     if constexpr (LIST) {
       primed = chain_next;
@@ -1222,6 +1382,25 @@ gemm_bf16x3_dual_kernel(GemmArgsB p1, GemmArgsB p2, int tiles_m1, int tiles_n1, 
     dma_tile<true, true, EPI_NT, 2, 4, 2, 1, 3, 32, 0, 3, 1, 2>(p1, tiles_m1, tiles_n1, group1, b - n_long, smem, seq0, count);
   else
     dma_tile<false, false, EPI_TN, 2, 4, 2, 1, 3, 32, 0, 3, 1, 2>(p2, tiles_m2, tiles_n2, group2, b - n_long, smem, seq0, count);
+}
+
+// The same launch with dA as the long-K problem and EPI_DACT_BN on its blocks (gemm_bf16.h: BnbArgs): the dA blocks are blocks
+// 0 .. n1 - 1, one tile each; the dW blocks behind them are gemm_bf16x3_dual_kernel's.
+template <int EPI_TN>
+__global__ void __launch_bounds__(512)
+gemm_bf16x3_dual_bnb_kernel(GemmArgsB p1, GemmArgsB p2, int tiles_m1, int tiles_n1, int group1, int tiles_m2, int tiles_n2, int group2,
+                            int per, BnbArgs bn) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int n1 = tiles_m1 * tiles_n1, n2 = tiles_m2 * tiles_n2;
+  const int b = blockIdx.x;
+  if (b < n1) {
+    dma_tile<true, true, EPI_DACT_BN, 2, 4, 2, 1, 3, 32, 0, 3, 1, 1>(p1, tiles_m1, tiles_n1, group1, b, smem, 0, 1, &bn);
+    return;
+  }
+  int seq0, count;
+  x3::dual_block_tiles(n2, per, b - n1, seq0, count);
+  if (count == 0) return;
+  dma_tile<false, false, EPI_TN, 2, 4, 2, 1, 3, 32, 0, 3, 1, 2>(p2, tiles_m2, tiles_n2, group2, b - n1, smem, seq0, count);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -1526,6 +1705,18 @@ int launch_x3_dual(const GemmArgsB& a, const GemmArgsB& w, hipStream_t stream) {
                      pick_group_rows(tmw, tnw, 128, 128), tn_first, per);
   return (int)hipGetLastError();
 }
+template <int EPI_TN>
+int launch_x3_dual_bnb(const GemmArgsB& a, const GemmArgsB& w, const BnbArgs& bn, hipStream_t stream) {
+  constexpr size_t lds = (size_t)3 * 3 * (128 + 128) * 32 * 2 + 2 * 2 * 128 * sizeof(float);  // (as launch_x3_dual)
+  constexpr auto kern = &gemm_bf16x3_dual_bnb_kernel<EPI_TN>;
+  if (int e = allow_full_lds<kern>()) return e;
+  const int tma = (a.M + 127) / 128, tna = (a.N + 127) / 128, tmw = (w.M + 127) / 128, tnw = (w.N + 127) / 128;
+  const int per = x3::dual_tiles_per_block(tma * tna, (a.K + 31) / 32, tmw * tnw, (w.K + 31) / 32);
+  const int blocks = tma * tna + x3::dual_short_blocks(tmw * tnw, per);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, stream, a, w, tma, tna, pick_group_rows(tma, tna, 128, 128), tmw, tnw,
+                     pick_group_rows(tmw, tnw, 128, 128), per, bn);
+  return (int)hipGetLastError();
+}
 bool x3_operands_ok(const GemmArgsB& p, long a_rows, long b_rows) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.lda & 31) || (p.ldb & 31) || (p.ldc & 3)) return false;
   // (the three planes of an operand are addressed through ONE buffer resource with 32-bit byte offsets)
@@ -1542,6 +1733,28 @@ int gemm_bf16x3_dual(const GemmArgsB& nt, const GemmArgsB& tn, hipStream_t strea
   // (the dual kernel writes both results through buffer resources with 32-bit byte offsets: epilogue<>, CBUF)
   if ((long)nt.M * nt.ldc * 4 >= (1L << 31) || (long)tn.M * tn.ldc * 4 >= (1L << 31)) return -1;
   return with_dual_epi(nt, tn, [&](auto e1, auto e2) { return launch_x3_dual<decltype(e1)::value, decltype(e2)::value>(nt, tn, stream); });
+}
+
+int gemm_bf16x3_dual_bnb(const GemmArgsB& nt, const GemmArgsB& tn, const BnbArgs& bn, int max_tiles, hipStream_t stream) {
+  if (!x3_operands_ok(nt, nt.M, nt.N) || !x3_operands_ok(tn, tn.K, tn.K)) return (int)hipErrorInvalidValue;
+  if (nt.epi != EPI_DACT_BN || (tn.epi != 0 && tn.epi != EPI_ACCUM)) return -1;
+  static const bool on = !getenv("TFK_BF16X3_DUAL") || atoi(getenv("TFK_BF16X3_DUAL")) != 0;
+  const int tma = (nt.M + 127) / 128, tna = (nt.N + 127) / 128;
+  const long tiles = (long)tma * tna + (long)((tn.M + 127) / 128) * ((tn.N + 127) / 128);
+  if (!on || tiles < 256) return -1;
+  if ((long)nt.M * nt.ldc * 4 >= (1L << 31) || (long)tn.M * tn.ldc * 4 >= (1L << 31)) return -1;
+  // the fused epilogue: the rule of x3_layout.h, and what its addressing takes for granted
+  if (!x3::dual_bnb_eligible(nt.M, bn.rows_per, nt.K, false, max_tiles) || tn.K != nt.M) return -1;
+  if (!bn.words || !bn.twin || bn.gen == 0 || bn.gen >= (1u << 30) || bn.rs < 1 || (long)bn.rs * bn.rows_per < nt.M) return -1;
+  if (!nt.stats || !nt.act_z || !nt.act_mean || !nt.act_rstd || !nt.act_a) return -1;
+  // (the bounded wait of the rendezvous reports its expiry through nt.err: without the word a launch whose wait ran out would
+  // hand on wrong dz silently, so there is no fused launch without it)
+  if (!nt.err) return -1;
+  if (tna > kBnbMaxCols || nt.ldc > tna * 128 || bn.ld_twin < nt.ldc || nt.N > nt.ldc || (nt.ldc & 3) || nt.stats_stride < tma || nt.stats_stride < bn.rs ||
+      (long)3 * nt.stats_stride * nt.ldc * 4 >= (1L << 31))
+    return -1;
+  if (tn.epi == EPI_ACCUM) return launch_x3_dual_bnb<EPI_ACCUM>(nt, tn, bn, stream);
+  return launch_x3_dual_bnb<0>(nt, tn, bn, stream);
 }
 
 int gemm_bf16x3(GemmLayout layout, const GemmArgsB& p, hipStream_t stream) {

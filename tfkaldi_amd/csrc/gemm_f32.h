@@ -35,6 +35,9 @@ enum : int {
                        // BM-row tile the column sums batch-norm's backward needs:
                        // stats[(0 * stats_stride + tile_m) * ldc + col] = sum du,
                        // stats[(1 * stats_stride + tile_m) * ldc + col] = sum du * (act_z - mean) * rstd
+  EPI_DACT_BN = 16 | 64,  // gemm_bf16x3_dual only (gemm_bf16.h: BnbArgs): EPI_DACT, and where the launch finds it safe to wait
+                          // for the other row tiles of a block column, batch norm's backward of the tile as well -- dz instead
+                          // of du, straight into the operand planes of the next contraction
 };
 
 struct GemmArgs {

@@ -82,9 +82,15 @@ void act_backward_rows(hipStream_t s, const ActDesc& d, float* da, const float* 
 // `stats_chunks` > 0: slabs 0 / 1 already hold that many chunks (EPI_DACT): the statistics pass is skipped.
 void hidden_backward(hipStream_t s, const ActDesc& d, int pre_du, float* da, const float* a, const float* z,
                      const float* mean, const float* rstd, int T, int H, int ld, float* ws, int stats_chunks = 0,
-                     Twin tw = Twin(), int T_apply = 0, float* ws_dz = nullptr);
+                     Twin tw = Twin(), int T_apply = 0, float* ws_dz = nullptr, const unsigned* done_word = nullptr,
+                     unsigned done_value = 0);
 // (stacked pass: rows [T, T_apply) are padding -- their dz is written as zero; ws_dz = where this launch's slab-2
 // partial sums go, default slab 2 of ws)
+// done_word: device word that holds done_value when the dual launch in front has done this pass in its epilogue (EPI_DACT_BN,
+// gemm_bf16.h): every block of the apply kernel then returns at once.
+// What that epilogue needs to repeat hb_apply's work bit for bit: rows per block of the apply kernel and its store mode.
+int hidden_backward_rows_per(int T);
+int hidden_backward_nt_mode(const Twin& tw, int T, int ld);
 // per-chunk partial column sums of x[T, ld] into slab 0 of ws (bias gradient of the output layer)
 // Tall micro-batches (more than kMergeOnceChunks GEMM row tiles): merge the per-tile statistics / partial sums ONCE
 // instead of in every block of the column-tiled kernels.

@@ -13,6 +13,8 @@
 //   mean/clip/Adam  trainer.py:174-184
 #include "kernels.h"
 
+#include "hb_math.h"
+
 #include <math.h>
 #include <stdlib.h>
 
@@ -102,17 +104,7 @@ __device__ __forceinline__ uint16_t to_bf16(float x) { return __builtin_bit_cast
 __device__ __forceinline__ void st4_twin(const Twin& t, size_t row, int col, float4 v) {
   if (!t.p) return;
   if (t.x3) {  // three interleaved planes whose sum is the value exactly
-    uint16_t a[4], b[4], c[4];
-    twin_split3(v.x, a[0], b[0], c[0]); twin_split3(v.y, a[1], b[1], c[1]);
-    twin_split3(v.z, a[2], b[2], c[2]); twin_split3(v.w, a[3], b[3], c[3]);
-    u16x4 q1, q2, q3;
-    q1.x = a[0]; q1.y = a[1]; q1.z = a[2]; q1.w = a[3];
-    q2.x = b[0]; q2.y = b[1]; q2.z = b[2]; q2.w = b[3];
-    q3.x = c[0]; q3.y = c[1]; q3.z = c[2]; q3.w = c[3];
-    uint16_t* d = t.p + x3::at(row, col, t.ld);  // (col is a multiple of 4: the four values share a unit)
-    *reinterpret_cast<u16x4*>(d) = q1;
-    *reinterpret_cast<u16x4*>(d + 64) = q2;
-    *reinterpret_cast<u16x4*>(d + 128) = q3;
+    hb::store_x3<false>(t.p, t.ld, row, col, v);
     return;
   }
   u16x4 q;
@@ -131,17 +123,7 @@ __device__ __forceinline__ void st4_nt(float* p, float4 v) {
 __device__ __forceinline__ void st4_twin_nt(const Twin& t, size_t row, int col, float4 v) {
   if (!t.p) return;
   if (t.x3) {
-    uint16_t a[4], b[4], c[4];
-    twin_split3(v.x, a[0], b[0], c[0]); twin_split3(v.y, a[1], b[1], c[1]);
-    twin_split3(v.z, a[2], b[2], c[2]); twin_split3(v.w, a[3], b[3], c[3]);
-    u16x4 q1, q2, q3;
-    q1.x = a[0]; q1.y = a[1]; q1.z = a[2]; q1.w = a[3];
-    q2.x = b[0]; q2.y = b[1]; q2.z = b[2]; q2.w = b[3];
-    q3.x = c[0]; q3.y = c[1]; q3.z = c[2]; q3.w = c[3];
-    uint16_t* d = t.p + x3::at(row, col, t.ld);
-    __builtin_nontemporal_store(q1, reinterpret_cast<u16x4*>(d));
-    __builtin_nontemporal_store(q2, reinterpret_cast<u16x4*>(d + 64));
-    __builtin_nontemporal_store(q3, reinterpret_cast<u16x4*>(d + 128));
+    hb::store_x3<true>(t.p, t.ld, row, col, v);
     return;
   }
   u16x4 q;
@@ -194,18 +176,8 @@ __device__ __forceinline__ ColTile col_tile(int T, int ld, int rows_per) {
 }
 // Sum a float4 over the 8 row lanes; result valid in threadIdx.y == 0.
 __device__ __forceinline__ float4 reduce_rows(float4 v, float4 (*sm)[CT_X]) {
-  sm[threadIdx.y][threadIdx.x] = v;
-  __syncthreads();
-  float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (threadIdx.y == 0) {
-#pragma unroll
-    for (int k = 0; k < CT_Y; ++k) {
-      const float4 q = sm[k][threadIdx.x];
-      t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w;
-    }
-  }
-  __syncthreads();
-  return t;
+  static_assert(CT_X == hb::kQuads && CT_Y == hb::kLanes, "hb_math.h: the column tile");
+  return hb::sum_lanes(v, sm, threadIdx.x, threadIdx.y);
 }
 
 // ---- batch-norm forward statistics ----
@@ -635,7 +607,10 @@ __global__ void __launch_bounds__(CT_X * CT_Y)
 hb_apply_kernel(ActDesc d, int pre_du, float* __restrict__ da, const float* __restrict__ a,
                 const float* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ rstd, int T,
                 int H, int ld, int rows_per, int rs_in, float* __restrict__ ws, Twin tw, int T_apply,
-                float* __restrict__ ws_dz, int nt) {
+                float* __restrict__ ws_dz, int nt, const unsigned* done_word, unsigned done_value) {
+  // done_word: the mode word of the dual launch in front of this one (gemm_bf16.h: BnbArgs).  When it holds done_value, the dA
+  // blocks of that launch have done all of this kernel's work in their epilogue (EPI_DACT_BN): nothing is left to do.
+  if (done_word && __hip_atomic_load(done_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == done_value) return;
   // rows [T, T_apply): padding behind a segment of a stacked pass -- their dz is written as ZERO (both contractions
   // that consume dz run over the padded rows) and they count for nothing.  ws_dz: where slab 2 of this launch goes.
   __shared__ float4 sm[CT_Y][CT_X];
@@ -667,16 +642,16 @@ hb_apply_kernel(ActDesc d, int pre_du, float* __restrict__ da, const float* __re
       for (int k = threadIdx.y; k < rs_in; k += CT_Y) {
         const float4 q1 = ld4(ws + ((size_t)0 * kMaxRowSplits + k) * ld + t.col);
         const float4 q2 = ld4(ws + ((size_t)1 * kMaxRowSplits + k) * ld + t.col);
-        p1.x += q1.x; p1.y += q1.y; p1.z += q1.z; p1.w += q1.w;
-        p2.x += q2.x; p2.y += q2.y; p2.z += q2.z; p2.w += q2.w;
+        hb::add4(p1, q1);
+        hb::add4(p2, q2);
       }
     __shared__ float4 smm[2][CT_X];
     p1 = reduce_rows(p1, sm);
     p2 = reduce_rows(p2, sm);
     if (threadIdx.y == 0) {
       const float invT = 1.f / (float)T;
-      smm[0][threadIdx.x] = make_float4(p1.x * invT, p1.y * invT, p1.z * invT, p1.w * invT);
-      smm[1][threadIdx.x] = make_float4(p2.x * invT, p2.y * invT, p2.z * invT, p2.w * invT);
+      smm[0][threadIdx.x] = hb::scale4(p1, invT);
+      smm[1][threadIdx.x] = hb::scale4(p2, invT);
     }
     __syncthreads();
     m1 = smm[0][threadIdx.x];
@@ -700,13 +675,7 @@ hb_apply_kernel(ActDesc d, int pre_du, float* __restrict__ da, const float* __re
         const int r = rb + j * CT_Y;
         if (r >= t.r1) continue;
         float4 dz = compute_du(d, pre_du, g[j], av[j], r, t.c4);
-        if (d.bn) {
-          // dz = rstd * (du - mean(du) - xhat * mean(du * xhat))
-          dz.x = rsd.x * (dz.x - m1.x - (zv[j].x - mu.x) * rsd.x * m2.x);
-          dz.y = rsd.y * (dz.y - m1.y - (zv[j].y - mu.y) * rsd.y * m2.y);
-          dz.z = rsd.z * (dz.z - m1.z - (zv[j].z - mu.z) * rsd.z * m2.z);
-          dz.w = rsd.w * (dz.w - m1.w - (zv[j].w - mu.w) * rsd.w * m2.w);
-        }
+        if (d.bn) dz = hb::dz4(dz, zv[j], mu, rsd, m1, m2);  // (hb_math.h: every rounding named, shared with EPI_DACT_BN)
         if (r >= T) dz = zero4;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -719,7 +688,7 @@ hb_apply_kernel(ActDesc d, int pre_du, float* __restrict__ da, const float* __re
         } else {
           st4(da + (size_t)r * ld + t.col, dz);
         }
-        sz.x += dz.x; sz.y += dz.y; sz.z += dz.z; sz.w += dz.w;
+        hb::add4(sz, dz);
       }
 #pragma unroll
       for (int j = 0; j < RB; ++j) {
@@ -1291,7 +1260,7 @@ void act_backward_rows(hipStream_t s, const ActDesc& d, float* da, const float* 
 
 void hidden_backward(hipStream_t s, const ActDesc& d, int pre_du, float* da, const float* a, const float* z,
                      const float* mean, const float* rstd, int T, int H, int ld, float* ws, int stats_chunks,
-                     Twin tw, int T_apply, float* ws_dz) {
+                     Twin tw, int T_apply, float* ws_dz, const unsigned* done_word, unsigned done_value) {
   if (T_apply < T) T_apply = T;
   const int rs = row_splits(T_apply), rows_per = (T_apply + rs - 1) / rs;
   if (d.bn && stats_chunks <= 0)  // (never with T_apply > T: a stacked pass always brings the EPI_DACT partial sums)
@@ -1299,8 +1268,13 @@ void hidden_backward(hipStream_t s, const ActDesc& d, int pre_du, float* da, con
                        rows_per, rs, ws);
   hipLaunchKernelGGL(hb_apply_kernel, ct_grid(ld, rs), ct_block(), 0, s, d, pre_du, da, a, z, mean, rstd, T, H, ld,
                      rows_per, stats_chunks > 0 ? stats_chunks : rs, ws, tw, T_apply,
-                     ws_dz ? ws_dz : ws + (size_t)2 * kMaxRowSplits * ld, bn_nt_mode(tw, T_apply, ld));
+                     ws_dz ? ws_dz : ws + (size_t)2 * kMaxRowSplits * ld, bn_nt_mode(tw, T_apply, ld), done_word, done_value);
 }
+int hidden_backward_rows_per(int T) {
+  const int rs = row_splits(T);
+  return (T + rs - 1) / rs;
+}
+int hidden_backward_nt_mode(const Twin& tw, int T, int ld) { return bn_nt_mode(tw, T, ld); }
 
 void bn_stats_from_chunks(hipStream_t s, const float* stats, int chunk_rows, int T, int H, int ld, float eps, float decay,
                           float* mean, float* rstd, float* e_mean, float* e_var) {

@@ -136,6 +136,22 @@ X3_HD int dual_short_blocks(int n_short, int per) {
   return (r > 0 && j_q1 > j_q) ? kXcds * j_q + r : kXcds * j_q;
 }
 
+// ---- batch norm's backward inside the dA blocks of the dual launch (gemm_bf16.hip: EPI_DACT_BN) --------------------
+// The dA blocks may do the column-tiled apply kernel's work (kernels.hip: hb_apply_kernel) on their own 128-row tile when
+//   * the pass is not stacked (one segment, one pair of column means);
+//   * dA is the problem with the longer K (T <= k_da), so that every dA tile has a block of its own and those blocks are the
+//     lowest block ids of the grid -- dispatched first, and the rendezvous of a block column waits for one-tile blocks only;
+//   * the apply kernel's blocks of `chunk_rows` rows tile the 128-row GEMM tile exactly (a chunk never straddles two tiles);
+//   * the slots fit: no more row tiles than `max_tiles` per-tile partial sums are summed by the apply kernel itself
+//     (kernels.h: kMergeOnceChunks; beyond that a merge kernel runs in between and the sums associate differently).
+constexpr int kDualTileRows = 128;
+X3_HD bool dual_bnb_eligible(int T, int chunk_rows, int k_da, bool stacked, int max_tiles) {
+  if (stacked || T < 1 || chunk_rows < 1) return false;
+  if (kDualTileRows % chunk_rows != 0) return false;
+  if (T > k_da) return false;
+  return (T + kDualTileRows - 1) / kDualTileRows <= max_tiles;
+}
+
 #if defined(__HIPCC__)
 // x = p1 + p2 + p3 exactly, each a bf16, by ROUND TO NEAREST (even): p1 = RN(x), p2 = RN(x - p1), p3 = x - p1 - p2.
 // Both subtractions are exact in fp32 (x - p1 keeps the low 16 bits of x's significand, sign included; the remainder after

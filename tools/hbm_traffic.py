@@ -32,7 +32,7 @@ def scope(kernel):
     """the engine's kernel-family label (bench.py: kernel_label) of a demangled kernel name; None: not a kernel of the step"""
     if "gemm_f32_dual_kernel" in kernel:
         return "gemm_f32_dual(dA+dW)"
-    if "gemm_bf16x3_dual_kernel" in kernel:
+    if "gemm_bf16x3_dual_kernel" in kernel or "gemm_bf16x3_dual_bnb_kernel" in kernel:  # (bnb: batch norm's backward in the dA blocks)
         return "gemm_bf16x3_dual(dA+dW)"
     if "gemm_bf16_dual_kernel" in kernel:
         return "gemm_bf16_dual(dA+dW)"

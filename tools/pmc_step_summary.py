@@ -6,7 +6,8 @@ import glob
 import sys
 
 src, dst = sys.argv[1], sys.argv[2]
-FAMILIES = [("gemm_bf16x3_dual_kernel", "gemm_bf16x3_dual(dA+dW)"), ("gemm_bf16_dual_kernel", "gemm_bf16_dual(dA+dW)"),
+FAMILIES = [("gemm_bf16x3_dual_kernel", "gemm_bf16x3_dual(dA+dW)"), ("gemm_bf16x3_dual_bnb_kernel", "gemm_bf16x3_dual(dA+dW)"),
+            ("gemm_bf16_dual_kernel", "gemm_bf16_dual(dA+dW)"),
             ("gemm_bf16_dma_kernel", "gemm_bf16 / bf16x3 (fwd / dW0)"),
             ("gemm_f32_dual_kernel", "gemm_f32_dual(dA+dW)"), ("gemm_f32_kernel", "gemm_f32 (fwd / dW0)"),
             ("adam_kernel", "adam_apply"), ("bn_act_forward", "bn_act_forward"), ("hb_apply", "hb_apply"),

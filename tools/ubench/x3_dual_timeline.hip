@@ -3,14 +3,17 @@
 // tfkaldi_amd/csrc/gemm_bf16.hip with the TFKB_TL hook defined: thread 0 of a block writes wall_clock64() (100 MHz) with plain
 // stores into a scratch buffer, plus HW_REG_XCC_ID / HW_REG_HW_ID at entry.  The library is built without the hook.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I tfkaldi_amd/csrc tools/ubench/x3_dual_timeline.hip -o tools/bin/x3_dual_timeline
-//   tools/bin/x3_dual_timeline [frames d_in d_out]        (default 1024 2048 2048: bench.py's hidden layer)
+//   tools/bin/x3_dual_timeline [frames d_in d_out [bnb | unfused]]   (default 1024 2048 2048: bench.py's hidden layer)
+// bnb: the launch with EPI_DACT_BN on its dA blocks (gemm_bf16.h: BnbArgs; ReLU, batch norm's backward in the blocks' tail) -- two
+// more stamps per dA block, at its arrival at the column's rendezvous and (the end stamp) behind the fused epilogue; unfused: the
+// same launch made to decide UNFUSED.
 // Prints, in microseconds from the first block's entry: when the blocks of the long-K problem end, and for every CU that ran
 // two short-K tiles the gap between the first tile's last MFMA and the second tile's first one, the epilogue's length, and the
 // end of the launch; then the launch's average time over 200 back-to-back launches (with the stamps being written).
 #include <hip/hip_runtime.h>
 
 __device__ unsigned long long* tfkb_tl_buf;
-constexpr int kTlTiles = 4, kTlWords = 5;  // per block: up to 4 tiles x {entry, first MFMA, last MFMA, end, where}
+constexpr int kTlTiles = 4, kTlWords = 6;  // per block: up to 4 tiles x {entry, first MFMA, last MFMA, end, arrival (EPI_DACT_BN), where}
 __device__ __forceinline__ void tfkb_tl_stamp(int ev, int ti) {
   if (threadIdx.x != 0 || ti >= kTlTiles) return;
   unsigned long long* r = tfkb_tl_buf + ((size_t)blockIdx.x * kTlTiles + ti) * kTlWords;
@@ -20,7 +23,7 @@ __device__ __forceinline__ void tfkb_tl_stamp(int ev, int ti) {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
     // HW_ID (gfx9): cu 11:8, sh 12, se 15:13
-    r[4] = 1ull | ((unsigned long long)(xcc & 15) << 8) | ((unsigned long long)((hwid >> 8) & 0xff) << 16);
+    r[5] = 1ull | ((unsigned long long)(xcc & 15) << 8) | ((unsigned long long)((hwid >> 8) & 0xff) << 16);
   }
 }
 #define TFKB_TL(ev, ti) tfkb_tl_stamp(ev, ti)
@@ -75,34 +78,62 @@ int main(int argc, char** argv) {
   hipMalloc(&buf, words * 8);
   hipMemset(buf, 0, words * 8);
   hipMemcpyToSymbol(HIP_SYMBOL(tfkb_tl_buf), &buf, sizeof(buf));
+  // bnb / unfused: the operands of the fused epilogue (zeros: a ReLU layer that passed nothing -- the timing does not depend on it)
+  const int bnb = argc > 4 ? (argv[4][0] == 'b' ? 1 : 2) : 0;
+  tfk::BnbArgs bn = {};
+  if (bnb) {
+    auto zeros = [](size_t bytes) { void* q; hipMalloc(&q, bytes); hipMemset(q, 0, bytes); return q; };
+    a.act_a = (const float*)zeros((size_t)T * ld_in * 4);
+    a.act_z = (const float*)zeros((size_t)T * ld_in * 4);
+    a.act_mean = (const float*)zeros((size_t)ld_in * 4);
+    a.act_rstd = (const float*)zeros((size_t)ld_in * 4);
+    a.stats = (float*)zeros((size_t)3 * 256 * ld_in * 4);
+    a.stats_stride = 256;
+    a.err = (unsigned*)zeros(4);  // (where a rendezvous that ran out of time would say so: no fused launch without it)
+    a.act_nonlin = 0;
+    a.epi = tfk::EPI_DACT_BN;
+    bn.words = (unsigned*)zeros(tfk::kBnbWords * 4);
+    bn.force_unfused = bnb == 2;
+    bn.rows_per = 32;
+    bn.rs = (T + 31) / 32;
+    bn.nt = 3;
+    bn.twin = (uint16_t*)zeros(tfk::x3::elems((size_t)T, ld_in) * 2);
+    bn.ld_twin = ld_in;
+  }
+  auto launch = [&]() {
+    if (!bnb) return tfk::gemm_bf16x3_dual(a, g, 0);
+    ++bn.gen;
+    return tfk::gemm_bf16x3_dual_bnb(a, g, bn, 32, 0);
+  };
   for (int i = 0; i < 50; ++i)
-    if (tfk::gemm_bf16x3_dual(a, g, 0) != 0) { printf("dual launch not eligible\n"); return 1; }
+    if (launch() != 0) { printf("dual launch not eligible\n"); return 1; }
   hipDeviceSynchronize();
   hipMemset(buf, 0, words * 8);
-  tfk::gemm_bf16x3_dual(a, g, 0);
+  launch();
   if (hipDeviceSynchronize() != hipSuccess) { printf("launch failed\n"); return 1; }
   std::vector<unsigned long long> h(words);
   hipMemcpy(h.data(), buf, words * 8, hipMemcpyDeviceToHost);
 
-  struct Rec { int block, ti; double t[4]; };
+  struct Rec { int block, ti; double t[5]; };
   unsigned long long t0 = ~0ull;
   for (size_t r = 0; r < words; r += kTlWords)
-    if (h[r + 4]) t0 = std::min(t0, h[r]);
+    if (h[r + 5]) t0 = std::min(t0, h[r]);
   std::map<unsigned long long, std::vector<Rec>> by_cu;  // short-problem tiles per CU
-  std::vector<double> long_entry, long_first, long_last, long_end, all_end, short_entry;
+  std::vector<double> long_entry, long_first, long_last, long_end, all_end, short_entry, long_arrive;
   int n_blocks = 0, n_tiles = 0;
   for (int b = 0; b < max_blocks; ++b)
     for (int ti = 0; ti < kTlTiles; ++ti) {
       const unsigned long long* r = &h[((size_t)b * kTlTiles + ti) * kTlWords];
-      const unsigned long long where = h[((size_t)b * kTlTiles) * kTlWords + 4];  // (a list's later tiles: the block's CU)
+      const unsigned long long where = h[((size_t)b * kTlTiles) * kTlWords + 5];  // (a list's later tiles: the block's CU)
       if (!r[0]) continue;
-      Rec rec = {b, ti, {0, 0, 0, 0}};
-      for (int e = 0; e < 4; ++e) rec.t[e] = (double)(r[e] - t0) * 0.01;  // 100 MHz -> us
+      Rec rec = {b, ti, {0, 0, 0, 0, 0}};
+      for (int e = 0; e < 5; ++e) rec.t[e] = r[e] ? (double)(r[e] - t0) * 0.01 : 0.0;  // 100 MHz -> us
       n_tiles++;
       if (ti == 0) n_blocks++;
       all_end.push_back(rec.t[3]);
       if (b < n_long) {
         long_entry.push_back(rec.t[0]); long_first.push_back(rec.t[1]); long_last.push_back(rec.t[2]); long_end.push_back(rec.t[3]);
+        if (r[4]) long_arrive.push_back(rec.t[4]);
       } else {
         if (ti == 0) short_entry.push_back(rec.t[0]);
         by_cu[where].push_back(rec);
@@ -113,6 +144,9 @@ int main(int argc, char** argv) {
   printf("# microseconds from the first block's entry; median [min .. max]\n");
   printf("long-K blocks : entry %6.2f [%6.2f .. %6.2f]  first MFMA %6.2f  last MFMA %6.2f  end %6.2f [%6.2f .. %6.2f]\n", med(long_entry),
          vmin(long_entry), vmax(long_entry), med(long_first), med(long_last), med(long_end), vmin(long_end), vmax(long_end));
+  if (!long_arrive.empty())  // (EPI_DACT_BN, decided FUSED: no arrival stamp otherwise)
+    printf("long-K blocks : arrival at the rendezvous %6.2f [%6.2f .. %6.2f]; last MFMA -> arrival %6.2f, arrival -> end %6.2f (medians)\n",
+           med(long_arrive), vmin(long_arrive), vmax(long_arrive), med(long_arrive) - med(long_last), med(long_end) - med(long_arrive));
   std::vector<double> ramp1, gap, epi1, epi2, end2, first_end, cus_tiles;
   for (auto& kv : by_cu) {
     auto& v = kv.second;
@@ -139,7 +173,7 @@ int main(int argc, char** argv) {
   hipEventCreate(&e0); hipEventCreate(&e1);
   const int iters = 200;
   hipEventRecord(e0, 0);
-  for (int i = 0; i < iters; ++i) tfk::gemm_bf16x3_dual(a, g, 0);
+  for (int i = 0; i < iters; ++i) launch();
   hipEventRecord(e1, 0);
   hipEventSynchronize(e1);
   float ms = 0;
