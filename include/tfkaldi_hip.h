@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 15
+#define TFK_ABI_VERSION 16
 
 typedef struct tfk_engine tfk_engine;
 
@@ -397,6 +397,48 @@ int tfk_ctc_beam_topk_logits(void* stream, const float* logits, int64_t ld, int3
                              int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* lm_dev, int32_t order,
                              float lm_weight, float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score,
                              float* am_score);
+/* (ABI 16) A FINITE-STATE GRAMMAR in place of the n-gram table: a DETERMINISTIC weighted acceptor over the labels (a lexicon
+ * trie, a closed grammar, a backed-off n-gram expanded on the host).  With O = output_dim and S = num_states >= 1:
+ *   weight[S][O] float32, row-major.  weight[s][c], c < O - 1: the natural-log weight of the arc that leaves state s with
+ *   label c; -inf means THERE IS NO SUCH ARC.  Column O - 1: the final weight of s, -inf = not final; read only under
+ *   TFK_CTC_LM_EOS, like the end column of the table.  NaN and +inf are rejected anywhere.
+ *   next[S][O] int32: next[s][c] in [0, S) wherever the arc exists; ignored where it does not, and in column O - 1.
+ *   start in [0, S).
+ * weight alone says whether an arc exists.  Host pointers, copied to the device; S * O <= 2^25 entries per table (128 MB each),
+ * a larger model is refused with the limit in the message before anything is read or allocated.  The call replaces whatever
+ * model the engine holds, table or graph (tfk_ctc_lm_set likewise replaces a graph); weight == NULL drops it.  A bad start, a
+ * NaN / +inf weight or a next out of range on an existing arc (tfk_last_error names the first offending index) is rejected; on
+ * any failure the engine keeps the model it had.  A graph over more than 64 outputs serves tfk_ctc_beam_topk only.
+ * tfk_ctc_beam_lm[_raw] and tfk_ctc_beam_topk[_raw] under TFK_CTC_LM rank by whichever model is set; signatures, limits and
+ * errors are unchanged.  Everything of tfk_ctc_beam_lm (under TFK_CTC_LM: of tfk_ctc_beam_topk) holds; the differences (this
+ * comment is the contract):
+ *   a prefix carries g and a STATE; the empty prefix has g = 0 and state `start`.
+ *   The extension of p by c exists only if weight[state(p)][c] > -inf; otherwise there is no candidate (p, c), as if
+ *   lp[c] = -inf (the wording of the pruned search for labels outside keep(t)).  Where it exists,
+ *   g(p + c) = (g(p) + lm_weight * weight[state(p)][c]) + label_bonus in the same three roundings, and
+ *   state(p + c) = next[state(p)][c].  Stay is unchanged.  The graph is deterministic, so the state, like g, is a function of
+ *   the label sequence alone: every route to a prefix computes the same bits, an extension that merges into a beam prefix
+ *   takes that prefix's values, and a missing extension can never be one that merges.
+ *   The constraint does not depend on lm_weight: with lm_weight = 0 a missing arc is still missing (existence is decided
+ *   before any arithmetic on the weight).
+ *   Candidate indices, tie-breaks, re-centring on the acoustic part and the double offset are unchanged.  A frame may have
+ *   far fewer live candidates than beam_width; the stay candidates are always live, so the beam never empties.
+ *   Final ranking by tot + g; under TFK_CTC_LM_EOS + lm_weight * weight[state][O - 1], and a prefix whose state is not final
+ *   has the combined value -inf whatever lm_weight is.  It is still listed (labels, hyp_len, finite am_score, score = -inf)
+ *   behind every finite one; among themselves such prefixes are ordered like any tie: shorter, then lower slot.
+ *   A zero-frame utterance: the empty hypothesis, am_score 0, score 0 or lm_weight * weight[start][O - 1] under the end flag
+ *   (-inf if start is not final).
+ * Two identities, bit for bit in hyp, hyp_len, score and am_score: (a) the graph next[s][c] = (s * O + c) mod C, weight = table,
+ * start = C - 1 reproduces tfk_ctc_beam_lm / tfk_ctc_beam_topk with that table; (b) a one-state graph with every arc, zero
+ * weights and lm_weight = label_bonus = 0 reproduces tfk_ctc_beam. */
+int tfk_ctc_graph_set(tfk_engine* e, const float* weight, const int32_t* next, int32_t num_states, int32_t start);
+/* (ABI 16) Tests / tools: the search with a graph alone on logits, as tfk_ctc_beam_topk_logits; DEVICE pointers, the tables
+ * in the layout above and NOT validated.  label_topk == 0: the unpruned search (O <= 64), else the pruned one.  flags: 0 or
+ * TFK_CTC_LM_EOS.  am_score may be NULL. */
+int tfk_ctc_beam_graph_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                              int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* weight_dev,
+                              const int32_t* next_dev, int32_t num_states, int32_t start, float lm_weight, float label_bonus,
+                              int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score);
 /* (ABI 11) CTC forced alignment: the most probable alignment of every utterance's KNOWN label sequence -- which frames emit
  * which label, and with what probability (time stamps and segments, corpus cleaning by alignment score, frame-level targets).
  * Eval-mode forward of the flat utterance-major frames X [T, ldx] of U utterances (utt_len[U], sum = T); labels / label_len as

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -157,6 +157,10 @@ SYMBOLS = {
     "tfk_ctc_beam_topk_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                          c_int32, c_void_p, c_int32, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "tfk_ctc_graph_set": (c_int, [_E, c_void_p, c_void_p, c_int32, c_int32]),
+    "tfk_ctc_beam_graph_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
     "tfk_ctc_align": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "tfk_ctc_align_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int]),

@@ -67,12 +67,19 @@ void ctc_best_path(hipStream_t s, const float* logits, int ld, int O, int T, con
 // ranked by logaddexp(pb', pnb') + g, and the final paths by that (+ weight * lm[ctx][O - 1] with eos); `score` is the
 // combined value and am_score (NULL: not wanted) the acoustic part.  The contract is the comment at tfk_ctc_beam_lm in
 // tfkaldi_hip.h.  weight = bonus = 0 without eos gives the bits of lm == NULL.
+// next != NULL: the model is a deterministic graph over the labels instead (the contract: tfk_ctc_graph_set) -- table is
+// weight [num_states, O] (-inf: no such arc; column O - 1: the final weight), next [num_states, O] the transitions, the
+// context id is the state, the empty prefix has `start`, and an extension without an arc is no candidate.  `order` is not
+// read then.  Both tables have at most kCtcGraphMaxEntries entries.
 struct CtcLm {
   const float* table;
   int order;  // in [1, kCtcLmMaxOrder]
   float weight, bonus;
   bool eos;
+  const int32_t* next = nullptr;
+  int num_states = 0, start = 0;
 };
+constexpr size_t kCtcGraphMaxEntries = (size_t)1 << 25;
 constexpr int kCtcLmMaxOrder = 4;
 int ctc_lm_contexts(int O, int order);
 constexpr int kCtcBeamMaxWidth = 128;

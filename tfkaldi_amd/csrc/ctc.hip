@@ -528,10 +528,12 @@ struct BeamSideLm : BeamSide {
   float g[kCtcBeamMaxWidth];
   int ctx[kCtcBeamMaxWidth];
 };
-template <bool LM>
-struct BeamSideOf { typedef BeamSide type; };
+// the model kind of a search: none (acoustic), the dense n-gram table, a deterministic graph over the labels
+constexpr int kBeamAm = 0, kBeamNgram = 1, kBeamGraph = 2;
+template <int LM>
+struct BeamSideOf { typedef BeamSideLm type; };
 template <>
-struct BeamSideOf<true> { typedef BeamSideLm type; };
+struct BeamSideOf<kBeamAm> { typedef BeamSide type; };
 // longest run of candidates one thread owns: ceil(kBeamKeys / kBeamThreads) | 1
 constexpr int kBeamRun = ((kBeamKeys + kBeamThreads - 1) / kBeamThreads) | 1;
 
@@ -647,12 +649,20 @@ __device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, in
 // more in D, ahead of its trie probe (an atomic round trip that is on the chain anyway; the reload was not timed on its
 // own).  Issuing the gathers one phase earlier, behind D's barrier of the frame before, was measured slower
 // (profiles/ctc_decode_bench.txt).
-template <bool LM>
+//
+// LM == kBeamGraph: lm is weight [S, O] and next [S, O] its transition table (the contract: tfk_ctc_graph_set in
+// tfkaldi_hip.h); ctx holds the state, the empty prefix has `start`.  The gather at the top of the step is the same one and
+// decides alone whether an extension exists (weight > -inf): phase B tests it before any arithmetic (0 * -inf is NaN), a
+// missing arc is no candidate, and each wave's count of them travels in sel[] through the barrier that wmax[] already
+// needs (sel is written again only behind the first barrier inside beam_radix_select), so that phase C's guard and the
+// select's precondition see the true live count.  A merging extension is never a missing one (its child is in the beam, so
+// the arc existed), hence live = N - ndead - missing.  next is read for survivors only, in D beside the weight's reload.
+template <int LM>
 __global__ void __launch_bounds__(kBeamThreads)
 ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U, int T, int W,
                 int top_paths, unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp,
                 int32_t* __restrict__ hyp_len, float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w,
-                float lm_bonus, int eos, float* __restrict__ am_score) {
+                float lm_bonus, int eos, float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart) {
   typedef typename BeamSideOf<LM>::type Side;
   __shared__ Side beam[2];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
@@ -681,7 +691,8 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     Side& b = beam[0];
     b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
     b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
-    if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
+    if constexpr (LM == kBeamGraph) { b.g[0] = 0.f; b.ctx[0] = gstart; }
+    else if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
     s_nb = 1;
     s_ndead = 0;
   }
@@ -729,14 +740,21 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
         if (k0 + q < k1) keys[k0 + q] = __builtin_bit_cast(uint32_t, lmv[q]);
       });
     float lmax = NEG;
+    int missing = 0;  // (graph) this thread's extensions that have no arc
     for (int k = k0; k < k1; ++k) {
       const int i = (int)__umulhi((uint32_t)k, magic), c = k - i * O;
       float pbn, pnbn;
       beam_candidate(b, lp, i, c, blank, &pbn, &pnbn);
-      const bool live = c == blank || !((childmask[i] >> c) & 1ull);
+      bool live = c == blank || !((childmask[i] >> c) & 1ull);
       const float tot = lae(pbn, pnbn);
       float rank = tot;  // what the beam is cut by; the re-centring (lmax) stays on the acoustic part
-      if constexpr (LM) {
+      if constexpr (LM == kBeamGraph) {
+        const float g = b.g[i], wv = __builtin_bit_cast(float, keys[k]);
+        const bool arc = c == blank || wv > -INFINITY;
+        missing += !arc;
+        live = live && arc;
+        rank = tot + (c == blank || !arc ? g : beam_lm_extend(g, lm_w, wv, lm_bonus));
+      } else if constexpr (LM) {
         const float g = b.g[i];
         rank = tot + (c == blank ? g : beam_lm_extend(g, lm_w, __builtin_bit_cast(float, keys[k]), lm_bonus));
       }
@@ -745,12 +763,18 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     }
     lmax = wave_max(lmax);
     if (lane == 0) wmax[wave] = lmax;
+    if constexpr (LM == kBeamGraph) {
+      for (int o = 32; o > 0; o >>= 1) missing += __shfl_xor(missing, o);
+      if (lane == 0) sel[wave] = missing;
+    }
     __syncthreads();
     float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
     if (!(m > -1e29f)) m = 0.f;
+    int nlive = N - ndead;
+    if constexpr (LM == kBeamGraph) nlive -= sel[0] + sel[1] + sel[2] + sel[3];
     // C
     uint32_t K = 0u, K2 = 0xffffffffu;  // select: key > K, or key == K and tie-break key >= K2
-    if (N - ndead > W) {
+    if (nlive > W) {
       int take, have;
       K = beam_radix_select([&](int k) { return keys[k]; }, k0, k1, W, hist, sel, &take, &have);
       K2 = 0u;
@@ -802,7 +826,9 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
           if constexpr (LM) { nx.g[slot] = b.g[i]; nx.ctx[slot] = b.ctx[i]; }
         } else {
           float lv = 0.f;
+          int ns = 0;
           if constexpr (LM) lv = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)c];  // issued ahead of the trie probe
+          if constexpr (LM == kBeamGraph) ns = gnext[(size_t)b.ctx[i] * (size_t)O + (size_t)c];
           // find or insert (parent node, label): the slot is the node's id
           const unsigned long long nk = ((unsigned long long)(uint32_t)b.node[i] << 6) | (unsigned long long)c;
           uint32_t pos = __umulhi((uint32_t)((nk * 0x9E3779B97F4A7C15ull) >> 32), cap);
@@ -815,7 +841,8 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
           nx.node[slot] = id; nx.parent[slot] = b.node[i]; nx.last[slot] = c; nx.len[slot] = b.len[i] + 1;
           if constexpr (LM) {
             nx.g[slot] = beam_lm_extend(b.g[i], lm_w, lv, lm_bonus);
-            nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
+            if constexpr (LM == kBeamGraph) nx.ctx[slot] = ns;
+            else nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
           }
         }
       }
@@ -851,7 +878,11 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   if constexpr (LM) {  // the combined values, parked in keys[] as floats
     if (tid < nb) {
       float v = b.tot[tid] + b.g[tid];
-      if (eos) v = beam_lm_end(v, lm_w, lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank]);
+      if (eos) {
+        const float fw = lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank];
+        if (LM == kBeamGraph && !(fw > -INFINITY)) v = -INFINITY;  // not final, whatever lm_weight is
+        else v = beam_lm_end(v, lm_w, fw);
+      }
       keys[tid] = __builtin_bit_cast(uint32_t, v);
     }
     __syncthreads();
@@ -1021,13 +1052,13 @@ __device__ __forceinline__ void beam_topk_extend(const BeamSide& b, int i, int c
 //   B-D  candidate k = i * (K + 1) + q: q < K extends by flab[q], q == K stays; a stay collects its parent's extension only if
 //      lpos >= 0.  With K == O - 1 flab is 0 .. O - 2 and k, the keys, the tie-breaks and every value are ctc_beam_kernel's
 //   the trie key holds a 16-bit label
-template <bool LM>
+template <int LM>
 __global__ void __launch_bounds__(kBeamThreads)
 ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, const uint32_t* __restrict__ pre,
                      const int32_t* __restrict__ seg, int U, int T, int W, int top_paths,
                      unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp, int32_t* __restrict__ hyp_len,
                      float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w, float lm_bonus, int eos,
-                     float* __restrict__ am_score) {
+                     float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart) {
   typedef typename BeamSideOf<LM>::type Side;
   __shared__ Side beam[2];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
@@ -1061,7 +1092,8 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
     Side& b = beam[0];
     b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
     b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
-    if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
+    if constexpr (LM == kBeamGraph) { b.g[0] = 0.f; b.ctx[0] = gstart; }
+    else if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
     s_nb = 1;
     s_ndead = 0;
   }
@@ -1150,14 +1182,21 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
       else beam_topk_extend(b, i, flab[p], fval[p], pbn, pnbn);
     };
     float lmax = NEG;
+    int missing = 0;  // (graph) this thread's extensions that have no arc
     for (int k = k0; k < k1; ++k) {
       const int i = (int)__umulhi((uint32_t)k, magic), p = k - i * K1;
       float pbn, pnbn;
       candidate(i, p, &pbn, &pnbn);
-      const bool live = p == K || !((childmask[i] >> p) & 1ull);
+      bool live = p == K || !((childmask[i] >> p) & 1ull);
       const float tot = lae(pbn, pnbn);
       float rank = tot;  // what the beam is cut by; the re-centring (lmax) stays on the acoustic part
-      if constexpr (LM) {
+      if constexpr (LM == kBeamGraph) {
+        const float g = b.g[i], wv = __builtin_bit_cast(float, keys[k]);
+        const bool arc = p == K || wv > -INFINITY;
+        missing += !arc;
+        live = live && arc;
+        rank = tot + (p == K || !arc ? g : beam_lm_extend(g, lm_w, wv, lm_bonus));
+      } else if constexpr (LM) {
         const float g = b.g[i];
         rank = tot + (p == K ? g : beam_lm_extend(g, lm_w, __builtin_bit_cast(float, keys[k]), lm_bonus));
       }
@@ -1166,12 +1205,18 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
     }
     lmax = wave_max(lmax);
     if (lane == 0) wmax[wave] = lmax;
+    if constexpr (LM == kBeamGraph) {  // as ctc_beam_kernel: the missing arcs ride through wmax's barrier in sel[]
+      for (int o = 32; o > 0; o >>= 1) missing += __shfl_xor(missing, o);
+      if (lane == 0) sel[wave] = missing;
+    }
     __syncthreads();
     float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
     if (!(m > -1e29f)) m = 0.f;
+    int nlive = N - ndead;
+    if constexpr (LM == kBeamGraph) nlive -= sel[0] + sel[1] + sel[2] + sel[3];
     // C
     uint32_t Kk = 0u, K2 = 0xffffffffu;  // select: key > Kk, or key == Kk and tie-break key >= K2
-    if (N - ndead > W) {
+    if (nlive > W) {
       int take, have;
       Kk = beam_radix_select([&](int k) { return keys[k]; }, k0, k1, W, hist, sel, &take, &have);
       K2 = 0u;
@@ -1224,7 +1269,9 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
         } else {
           const int c = flab[p];
           float lv = 0.f;
+          int ns = 0;
           if constexpr (LM) lv = lm[(size_t)b.ctx[i] * (size_t)O + (size_t)c];  // issued ahead of the trie probe
+          if constexpr (LM == kBeamGraph) ns = gnext[(size_t)b.ctx[i] * (size_t)O + (size_t)c];
           // find or insert (parent node, label): the slot is the node's id
           const unsigned long long nk = ((unsigned long long)(uint32_t)b.node[i] << 16) | (unsigned long long)c;
           uint32_t pos = __umulhi((uint32_t)((nk * 0x9E3779B97F4A7C15ull) >> 32), cap);
@@ -1237,7 +1284,8 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
           nx.node[slot] = id; nx.parent[slot] = b.node[i]; nx.last[slot] = c; nx.len[slot] = b.len[i] + 1;
           if constexpr (LM) {
             nx.g[slot] = beam_lm_extend(b.g[i], lm_w, lv, lm_bonus);
-            nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
+            if constexpr (LM == kBeamGraph) nx.ctx[slot] = ns;
+            else nx.ctx[slot] = (int)(((uint32_t)b.ctx[i] * (uint32_t)O + (uint32_t)c) % (uint32_t)C);
           }
         }
       }
@@ -1275,7 +1323,11 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
   if constexpr (LM) {  // the combined values, parked in keys[] as floats
     if (tid < nb) {
       float v = b.tot[tid] + b.g[tid];
-      if (eos) v = beam_lm_end(v, lm_w, lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank]);
+      if (eos) {
+        const float fw = lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)blank];
+        if (LM == kBeamGraph && !(fw > -INFINITY)) v = -INFINITY;  // not final, whatever lm_weight is
+        else v = beam_lm_end(v, lm_w, fw);
+      }
       keys[tid] = __builtin_bit_cast(uint32_t, v);
     }
     __syncthreads();
@@ -1797,13 +1849,17 @@ void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, c
                      float* am_score) {
   if (U <= 0) return;
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
-  if (lm)
-    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
-                       hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus, (int)lm->eos,
-                       am_score);
+  if (lm && lm->next)
+    hipLaunchKernelGGL(ctc_beam_kernel<kBeamGraph>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths,
+                       trie, hyp, hyp_len, score, lm->table, lm->num_states, lm->weight, lm->bonus, (int)lm->eos, am_score,
+                       lm->next, lm->start);
+  else if (lm)
+    hipLaunchKernelGGL(ctc_beam_kernel<kBeamNgram>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths,
+                       trie, hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus, (int)lm->eos,
+                       am_score, (const int32_t*)nullptr, 0);
   else
-    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
-                       hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, (float*)nullptr);
+    hipLaunchKernelGGL(ctc_beam_kernel<kBeamAm>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
+                       hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, (float*)nullptr, (const int32_t*)nullptr, 0);
 }
 
 size_t ctc_beam_topk_scratch_words(int T) { return (size_t)(T > 0 ? T : 0) * kCtcTopkRowWords; }
@@ -1835,13 +1891,18 @@ void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int
   if (U <= 0) return;
   const int K = min(label_topk, O - 1);
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
-  if (lm)
-    hipLaunchKernelGGL(ctc_beam_topk_kernel<true>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
+  if (lm && lm->next)
+    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamGraph>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
+                       top_paths, trie, hyp, hyp_len, score, lm->table, lm->num_states, lm->weight, lm->bonus, (int)lm->eos,
+                       am_score, lm->next, lm->start);
+  else if (lm)
+    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamNgram>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
                        top_paths, trie, hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus,
-                       (int)lm->eos, am_score);
+                       (int)lm->eos, am_score, (const int32_t*)nullptr, 0);
   else
-    hipLaunchKernelGGL(ctc_beam_topk_kernel<false>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
-                       top_paths, trie, hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, am_score);
+    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamAm>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
+                       top_paths, trie, hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, am_score,
+                       (const int32_t*)nullptr, 0);
 }
 
 // scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]

@@ -217,6 +217,9 @@ struct tfk_engine {
   // the character n-gram table of tfk_ctc_lm_set, [O^(order - 1), O]; order 0: no model
   float* ctc_lm = nullptr;
   int ctc_lm_order = 0;
+  // or the graph of tfk_ctc_graph_set: ctc_lm is weight [S, O], ctc_graph_next the transitions [S, O]; 0 states: no graph
+  int32_t* ctc_graph_next = nullptr;
+  int ctc_graph_states = 0, ctc_graph_start = 0;
   // forced alignment (tfk_ctc_align): the back-pointer rows and row log-sum-exps of ctc_viterbi_align
   unsigned char* ctc_bp = nullptr;
   size_t ctc_cap_bp = 0;
@@ -2108,7 +2111,7 @@ int tfk_destroy(tfk_engine* e) {
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
                   (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
-                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw})
+                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw, (void*)e->ctc_graph_next})
     if (p) hipFree(p);
   if (e->h_pair) hipHostFree(e->h_pair);
   if (e->ctc_pair_staged) hipEventDestroy(e->ctc_pair_staged);
@@ -2777,9 +2780,10 @@ static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, 
     if (!(flags & TFK_CTC_LM)) lm = nullptr;
     flags &= ~TFK_CTC_LM;
   }
-  if (lm && !e->ctc_lm_order) return fail(-1, "%s: no language model is set (tfk_ctc_lm_set)", who);
+  if (lm && !e->ctc_lm_order && !e->ctc_graph_states)
+    return fail(-1, "%s: no language model is set (tfk_ctc_lm_set)", who);
   const CtcLm model = {e->ctc_lm, e->ctc_lm_order, lm ? lm->weight : 0.f, lm ? lm->bonus : 0.f,
-                       (flags & TFK_CTC_LM_EOS) != 0};
+                       (flags & TFK_CTC_LM_EOS) != 0, e->ctc_graph_next, e->ctc_graph_states, e->ctc_graph_start};
   flags &= ~TFK_CTC_LM_EOS;
   if (!hyp || !hyp_len || !score) return fail(-1, "hyp / hyp_len / score is NULL");
   if ((edits != nullptr) != (ref_len != nullptr)) return fail(-1, "edits and ref_len go together (both NULL or both set)");
@@ -2839,6 +2843,19 @@ static int ctc_beam_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, 
   return 0;
 }
 
+// frees whichever model the engine holds, table or graph (the caller has synchronised the stream)
+static int ctc_model_drop(tfk_engine* e) {
+  float* const w = e->ctc_lm;
+  int32_t* const nx = e->ctc_graph_next;
+  e->ctc_lm = nullptr;
+  e->ctc_lm_order = 0;
+  e->ctc_graph_next = nullptr;
+  e->ctc_graph_states = 0;
+  e->ctc_graph_start = 0;
+  if (w) HIPCHK(hipFree(w));
+  if (nx) HIPCHK(hipFree(nx));
+  return 0;
+}
 int tfk_ctc_lm_set(tfk_engine* e, const float* table, int32_t order) {
   if (!e) return fail(-1, "engine is NULL");
   HIPCHK(hipSetDevice(e->cfg.device));
@@ -2854,13 +2871,54 @@ int tfk_ctc_lm_set(tfk_engine* e, const float* table, int32_t order) {
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(table[i])) return fail(-1, "tfk_ctc_lm_set: entry %zu of the table is not finite", i);
   HIPCHK(hipStreamSynchronize(e->stream));  // a search may still be reading the model this one replaces
-  if (e->ctc_lm) HIPCHK(hipFree(e->ctc_lm));
-  e->ctc_lm = nullptr;
-  e->ctc_lm_order = 0;
+  CHK(ctc_model_drop(e));
   if (!table) return 0;
   HIPCHK(hipMalloc((void**)&e->ctc_lm, n * sizeof(float)));
   HIPCHK(hipMemcpy(e->ctc_lm, table, n * sizeof(float), hipMemcpyHostToDevice));
   e->ctc_lm_order = order;
+  return 0;
+}
+// A deterministic weighted acceptor over the labels in place of the table (the contract: tfkaldi_hip.h).  Everything is
+// validated, and both device tables are filled, before the engine's model is touched: any failure leaves it in force.
+int tfk_ctc_graph_set(tfk_engine* e, const float* weight, const int32_t* next, int32_t num_states, int32_t start) {
+  if (!e) return fail(-1, "engine is NULL");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if (!weight) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return ctc_model_drop(e);
+  }
+  if (!next) return fail(-1, "tfk_ctc_graph_set: next is NULL");
+  if (e->O < 2 || e->O > kCtcTopkMaxClasses)
+    return fail(-1, "tfk_ctc_graph_set: output_dim %d outside [2, %d] (the beam search's limit)", e->O, kCtcTopkMaxClasses);
+  if (num_states < 1) return fail(-1, "tfk_ctc_graph_set: num_states %d < 1", num_states);
+  if ((size_t)num_states * (size_t)e->O > kCtcGraphMaxEntries)
+    return fail(-1, "tfk_ctc_graph_set: a graph of %d states over %d outputs has more than %zu entries per table", num_states,
+                e->O, kCtcGraphMaxEntries);
+  if (start < 0 || start >= num_states) return fail(-1, "tfk_ctc_graph_set: start %d outside [0, %d)", start, num_states);
+  const size_t O = (size_t)e->O, n = (size_t)num_states * O;
+  for (size_t i = 0; i < n; ++i) {
+    const float w = weight[i];
+    if (std::isnan(w) || w == INFINITY) return fail(-1, "tfk_ctc_graph_set: entry %zu of weight is NaN or +inf", i);
+    if (i % O != O - 1 && w > -INFINITY && (next[i] < 0 || next[i] >= num_states))
+      return fail(-1, "tfk_ctc_graph_set: entry %zu of next is %d, outside [0, %d)", i, next[i], num_states);
+  }
+  float* d_w = nullptr;
+  int32_t* d_n = nullptr;
+  HIPCHK(hipMalloc((void**)&d_w, n * sizeof(float)));
+  hipError_t got = hipMalloc((void**)&d_n, n * sizeof(int32_t));
+  if (got == hipSuccess) got = hipMemcpy(d_w, weight, n * sizeof(float), hipMemcpyHostToDevice);
+  if (got == hipSuccess) got = hipMemcpy(d_n, next, n * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (got == hipSuccess) got = hipStreamSynchronize(e->stream);  // a search may still be reading the model this one replaces
+  if (got != hipSuccess) {
+    (void)hipFree(d_w);
+    if (d_n) (void)hipFree(d_n);
+    HIPCHK(got);
+  }
+  CHK(ctc_model_drop(e));
+  e->ctc_lm = d_w;
+  e->ctc_graph_next = d_n;
+  e->ctc_graph_states = num_states;
+  e->ctc_graph_start = start;
   return 0;
 }
 int tfk_ctc_beam_lm(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
@@ -2988,6 +3046,22 @@ int tfk_ctc_beam_lm_logits(void* stream, const float* logits, int64_t ld, int32_
   if (!lm_dev) return fail(-1, "tfk_ctc_beam_lm_logits: the table is NULL");
   const CtcLm lm = {lm_dev, order, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0};
   return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score);
+}
+int tfk_ctc_beam_graph_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
+                              int32_t U, int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* weight_dev,
+                              const int32_t* next_dev, int32_t num_states, int32_t start, float lm_weight, float label_bonus,
+                              int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score) {
+  if (label_topk < 0) return fail(-1, "tfk_ctc_beam_graph_logits: label_topk outside [0, 63]");
+  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "tfk_ctc_beam_graph_logits: flags %d, it takes 0 or TFK_CTC_LM_EOS", flags);
+  if (!weight_dev || !next_dev) return fail(-1, "tfk_ctc_beam_graph_logits: weight / next is NULL");
+  if (num_states < 1 || start < 0 || start >= num_states)
+    return fail(-1, "tfk_ctc_beam_graph_logits: start %d outside [0, num_states = %d)", start, num_states);
+  if (O >= 2 && (size_t)num_states * (size_t)O > kCtcGraphMaxEntries)
+    return fail(-1, "tfk_ctc_beam_graph_logits: a graph of %d states over %d outputs has more than %zu entries per table",
+                num_states, O, kCtcGraphMaxEntries);
+  const CtcLm lm = {weight_dev, 0, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0, next_dev, num_states, start};
+  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score,
+                              label_topk);
 }
 // Forced alignment (the Viterbi path of every utterance's known label sequence; the contract: tfkaldi_hip.h):
 // evaluation-mode forward as tfk_posteriors, then ctc_viterbi_align on the logits in HBM; T + U words go back to the host.

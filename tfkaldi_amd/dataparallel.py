@@ -121,7 +121,7 @@ class CtcMwerMicroBatch(CtcMicroBatch):
     """A CTC micro-batch trained on the expected number of label errors over an N-best list (tfk_accumulate_ctc_mwer) plus
     ctc_weight x the CTC loss.  It carries EITHER the pair tables (hyp_counts, hyp_labels, hyp_lens as Engine.ctc_score takes
     them) OR the settings of the search that finds the list: then the rank that trains the micro-batch decodes its N best
-    itself, on the same engine, right before the accumulate (beam_width, top_paths; lm: an NgramLM that ranks the search;
+    itself, on the same engine, right before the accumulate (beam_width, top_paths; lm: an NgramLM or GraphLM that ranks the search;
     label_topk: the pruned search).  add_reference: the reference joins every list that lacks it."""
 
     def __init__(self, X, utt_lens, labels, label_lens, context_width=None, cmvn=None, hyp_counts=None, hyp_labels=None,
@@ -228,7 +228,7 @@ def _eval_accumulate_all(engine, mine):
 
 def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
     """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
-    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM; label_topk:
+    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM or GraphLM; label_topk:
     pruned to the frame's label_topk most probable labels).  rescore_paths: an int N takes the search's N best, scores them
     exactly with their label errors (ctc_score) and counts the hypothesis that is best after decoder.ctc_rerank."""
     if rescore_paths is not None and beam_width is None:
@@ -1380,7 +1380,7 @@ class DataParallel(object):
     def label_errors(self, engine, microbatches, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
         """(edits, reference labels): label errors summed over the CTC micro-batches of the WHOLE batch (identical on every
         rank) under best-path decoding (beam_width None) or the best path of a prefix beam search of that width (lm: an
-        NgramLM the search ranks its prefixes with; label_topk: an int prunes the search to the frame's label_topk most
+        NgramLM or GraphLM the search ranks its prefixes with; label_topk: an int prunes the search to the frame's label_topk most
         probable labels, for models of any output size; rescore_paths: an int N re-ranks the search's N best by their exact
         scores (ctc_score + ctc_rerank, lm honoured) and counts the new best; every rank passes the same ones).
         COLLECTIVE when enabled: each rank decodes its block of micro-batches (partitioned as eval_step) and the two counts

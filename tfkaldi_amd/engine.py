@@ -44,7 +44,7 @@ class Engine(object):
         self.F, self.L, self.H, self.O = cfg.input_dim, cfg.num_layers, cfg.num_units, cfg.output_dim
         self.batch_norm = bool(cfg.batch_norm)
         self._h = c_void_p()
-        self._lm_table = None  # the NgramLM table tfk_ctc_lm_set holds (ctc_set_lm)
+        self._lm_table = None  # the NgramLM / GraphLM table tfk_ctc_lm_set / tfk_ctc_graph_set holds (ctc_set_lm)
         self._state = None
         self._stream = None
         self._cb = None
@@ -459,10 +459,12 @@ class Engine(object):
         return self._beam(self.lib.tfk_ctc_beam_raw, raw, utt_lens, beam_width, top_paths, labels, label_lens,
                           raw=(context_width, cmvn), label_topk=label_topk)
 
-    # ---- the same search ranked with a character n-gram language model (neuralNetworks/ctc_lm.NgramLM) ----
+    # ---- the same search ranked with a language model over the labels: a character n-gram (neuralNetworks/ctc_lm.NgramLM)
+    # or a deterministic finite-state grammar, which also forbids what it does not accept (ctc_lm.GraphLM) ----
     def ctc_set_lm(self, lm):
-        """Make `lm` (an NgramLM, or None to drop it) the engine's language model (tfk_ctc_lm_set: the table is copied to the
-        device).  Nothing is uploaded when the same table object is already set."""
+        """Make `lm` (an NgramLM or a GraphLM, or None to drop it) the engine's language model (tfk_ctc_lm_set /
+        tfk_ctc_graph_set: the tables are copied to the device; either replaces the other).  Nothing is uploaded when the
+        same table object is already set."""
         if lm is None:
             if self._lm_table is not None:
                 check(self.lib.tfk_ctc_lm_set(self._h, c_void_p(None), 0))
@@ -472,7 +474,10 @@ class Engine(object):
         if self._lm_table is lm.table:
             return
         self._lm_table = None
-        check(self.lib.tfk_ctc_lm_set(self._h, _ptr(lm.table), lm.order))
+        if getattr(lm, "next", None) is not None:
+            check(self.lib.tfk_ctc_graph_set(self._h, _ptr(lm.table), _ptr(lm.next), lm.num_states, lm.start))
+        else:
+            check(self.lib.tfk_ctc_lm_set(self._h, _ptr(lm.table), lm.order))
         self._lm_table = lm.table
 
     def _beam_lm(self, fn, frames, utt_lens, lm, beam_width, top_paths, labels, label_lens, raw=None, label_topk=None):
@@ -486,7 +491,8 @@ class Engine(object):
             score = np.full((top_paths, U), -np.inf, dtype=np.float32)
             am = score.copy()
             am[0] = 0.0
-            score[0] = np.float32(lm.weight) * lm.table[-1, -1] if lm.end_of_sequence else 0.0
+            end = lm.table[lm.start, -1]  # (a graph's start state that is not final: -inf whatever the weight is)
+            score[0] = (end if end == -np.inf else np.float32(lm.weight) * end) if lm.end_of_sequence else 0.0
             edits = None if labels is None else (np.empty(U, dtype=np.int32) if rows else label_lens.copy())
             return np.empty((top_paths, rows), dtype=np.int32), np.zeros((top_paths, U), dtype=np.int32), score, am, edits
 
@@ -505,8 +511,8 @@ class Engine(object):
 
     def ctc_beam_lm(self, X, utt_lens, lm, beam_width=100, top_paths=1, labels=None, label_lens=None, label_topk=None):
         """ctc_beam with prefixes ranked by acoustic score + language-model score (tfk_ctc_beam_lm; the search is stated in
-        include/tfkaldi_hip.h).  lm: an NgramLM over this model's labels -- its table is set on the engine if it is not
-        already, its weight, label bonus and end-of-sequence switch go with the call.  Returns (hyps, scores, am_scores,
+        include/tfkaldi_hip.h).  lm: an NgramLM or a GraphLM over this model's labels (a GraphLM also restricts the search to
+        the label sequences it accepts: tfk_ctc_graph_set) -- its table is set on the engine if it is not already, its weight, label bonus and end-of-sequence switch go with the call.  Returns (hyps, scores, am_scores,
         edits): as ctc_beam, scores the COMBINED values the paths are ordered by, am_scores float32 [U, top_paths] their
         acoustic parts; edits of the best path by combined score.  label_topk: as ctc_beam."""
         return self._beam_lm(self.lib.tfk_ctc_beam_lm, X, utt_lens, lm, beam_width, top_paths, labels, label_lens,

@@ -33,7 +33,7 @@ def ctc_segments(ali, labels):
 def ctc_rerank(hyps, exact_scores, lm=None):
     """Second-pass ranking of ONE utterance's N-best list: `hyps` int label arrays in the first pass's order,
     `exact_scores` their exact log-probabilities log p(labels | x) (Decoder.ctc_score).  The combined score of a hypothesis
-    is its exact score plus lm.score(h) (a ctc_lm.NgramLM: weight, label bonus and end term as the search uses them), in
+    is its exact score plus lm.score(h) (a ctc_lm.NgramLM or GraphLM: weight, label bonus and end term as the search uses them), in
     float64.  Returns (order, scores, posteriors): `order` the indices into hyps by descending combined score -- a stable
     sort, so a tie keeps the first pass's order -- `scores` float64 the combined scores in that order, `posteriors` float64
     their softmax over the list (a -inf hypothesis sorts last with posterior 0; a list without a finite score gets zeros)."""
@@ -153,7 +153,8 @@ class Decoder(object):
         return self._ctc("ctc_beam", utterances, beam_width=beam_width, top_paths=top_paths, **kw)[:2]
 
     def ctc_beam_search_lm(self, utterances, lm, beam_width=100, top_paths=1, label_topk=None):
-        """ctc_beam_search with a character n-gram language model (ctc_lm.NgramLM; tfk_ctc_beam_lm): prefixes are ranked by
+        """ctc_beam_search with a language model over the labels (ctc_lm.NgramLM, or a GraphLM, which
+        also restricts the search to the sequences it accepts; tfk_ctc_beam_lm): prefixes are ranked by
         acoustic score + lm.weight * model log-probability + lm.label_bonus per label.  Returns (hyps, scores, am_scores):
         as ctc_beam_search, scores the combined values, am_scores float32 [U, top_paths] their acoustic parts.  label_topk:
         as ctc_beam_search."""

@@ -369,7 +369,7 @@ class CTCTrainer(Trainer):
         Python ints: a corpus label error rate is sum(edits) / sum(reference labels) over its batches.  None when there is
         no data (as evaluate).  COLLECTIVE under data parallelism: the micro-batches are dealt to the ranks as in evaluate
         and the two counts summed over them.  beam_width: an int decodes by prefix beam search of that width instead
-        (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path.  lm: a ctc_lm.NgramLM ranks
+        (tf.nn.ctc_beam_search_decoder, tfk_ctc_beam) and counts the errors of its best path.  lm: a ctc_lm.NgramLM or GraphLM ranks
         the beam's prefixes by acoustic + language-model score (tfk_ctc_beam_lm); it needs a beam_width.  label_topk: an int
         prunes the search to the frame's label_topk most probable labels (tfk_ctc_beam_topk), which is what lets a model of
         more than 64 outputs be searched; it needs a beam_width too.  rescore_paths: an int N decodes the N best, scores
@@ -429,7 +429,7 @@ class CTCTrainer(Trainer):
         tfk_accumulate_ctc_mwer; Prabhavalkar et al. 2018) plus ctc_weight x the CTC loss -- the criterion label_errors
         reports, where update minimises the likelihood.  The list: the top_paths best (default: all beam_width) of a prefix
         beam search of width beam_width, decoded in evaluation mode by the rank that trains the micro-batch right before it
-        does (lm: a ctc_lm.NgramLM ranks the search; label_topk: the pruned search, for models of more than 64 outputs); or
+        does (lm: a ctc_lm.NgramLM or GraphLM ranks the search; label_topk: the pruned search, for models of more than 64 outputs); or
         hyps, a list per utterance of label arrays, which skips the search.  add_reference: the reference joins every list
         that lacks it.  The hypotheses are scored on the train-mode logits of the step itself.  Returns the step's loss:
         expected label errors per reference label + ctc_weight x CTC loss per label, before the update."""

@@ -26,6 +26,11 @@ pairs and scaled), how many utterances change their best hypothesis, and the bes
 `--mwer` runs the MWER leg alone: one step on the expected label errors over the N-best (tfk_accumulate_ctc_mwer, N = 10 and 100
 from the tool's own search at that width, ctc_weight 0.01) against one plain CTC step on the same build -- warm-up, 20 timed
 steps each, the median with the spread, the decode excluded and included, and the profiler's rows of the new kernels.
+`--graph` runs the grammar leg alone, on logits (no engine): the lexicon inputs of tests/test_ctc_beam_graph_host.py (28
+outputs, 50 words, a trie of 182 states) at the tests' size and at 16 utterances x 800 frames, W = 10 and 100, unpruned and
+with label_topk = 8 -- the search with the lexicon graph (tfk_ctc_beam_graph_logits) beside the n-gram search (order 2 over
+the references) and the acoustic search at the same shapes: HIP-event time per call (median of 20, with the spread), that
+time per frame step, the graph search's time over the n-gram search's, and the label errors against the references.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -47,6 +52,9 @@ from test_ctc_score_host import ctc_score_restated  # noqa: E402
 
 
 def main():
+    if "--graph" in sys.argv:
+        graph_leg()
+        return
     U, Tu, S, F, L, H, O = 16, 800, 100, 440, 4, 512, 36
     T = U * Tu
     cfg = _lib.make_config(F, L, H, O, nonlin="relu", batch_norm=True, max_frames=T, num_steps=1000,
@@ -359,6 +367,62 @@ def score_leg(eng, X, utt, labels, lab, case):
               % (case, W, len(flat), max(hn), ms, kern, kern * 1e3 / max(utt), kern / loss_kern, ed, host, len(kept[0]),
                  host * len(flat) / len(kept[0]), len(flat), moved, len(utt), gap, best_edits.sum() / total, rescored / total,
                  oracle / total, float(np.max(np.abs(scores[0] - s64)))))
+
+
+def graph_leg():
+    """the search with a lexicon graph beside the n-gram and the acoustic search, on the same logits (device pointers)"""
+    import torch
+    from ctypes import c_float, c_void_p
+    from test_ctc_beam_graph_host import lexicon_inputs
+    from test_ctc_decode_host import levenshtein
+    from tfkaldi_amd.neuralNetworks.ctc_lm import NgramLM
+    lib = _lib.load()
+    stream = c_void_p(torch.cuda.current_stream().cuda_stream)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    ptr = lambda t: c_void_p(t.data_ptr())
+    for U, Tn, words in ((8, 120, 3), (16, 800, 20)):
+        z, utt, refs, graph = lexicon_inputs(U, Tn, words)
+        T, O = z.shape
+        ngram = NgramLM.from_label_sequences(refs, O - 1, 2, weight=0.5, label_bonus=0.3, end_of_sequence=True)
+        d_z, d_seg = dev(z), dev(np.concatenate([[0], np.cumsum(utt)]).astype(np.int32))
+        d_tab, d_w, d_n = dev(ngram.table), dev(graph.table), dev(graph.next)
+        hyp = torch.empty((1, T), dtype=torch.int32, device="cuda")
+        hl = torch.empty((1, U), dtype=torch.int32, device="cuda")
+        sc, am = torch.empty((1, U), dtype=torch.float32, device="cuda"), torch.empty((1, U), dtype=torch.float32, device="cuda")
+        out = (ptr(hyp), ptr(hl), ptr(sc), ptr(am))
+        eos = _lib.CTC_LM_EOS
+        print("graph leg: %d utterances x %d frames, %d outputs, lexicon of 50 words = %d states, %d reference labels"
+              % (U, Tn, O, graph.num_states, sum(r.size for r in refs)))
+        for W in (10, 100):
+            for K in (0, 8):
+                head = (stream, ptr(d_z), O, O, T, ptr(d_seg), U, W, 1)
+                calls = {
+                    "acoustic": (lambda: lib.tfk_ctc_beam_topk_logits(*head, K, c_void_p(None), 0, c_float(0.0), c_float(0.0), 0, *out))
+                    if K else (lambda: lib.tfk_ctc_beam_logits(*head, *out[:3])),
+                    "n-gram": (lambda: lib.tfk_ctc_beam_topk_logits(*head, K, ptr(d_tab), 2, c_float(0.5), c_float(0.3), eos, *out))
+                    if K else (lambda: lib.tfk_ctc_beam_lm_logits(*head, ptr(d_tab), 2, c_float(0.5), c_float(0.3), eos, *out)),
+                    "graph": lambda: lib.tfk_ctc_beam_graph_logits(*head, K, ptr(d_w), ptr(d_n), graph.num_states, graph.start,
+                                                                   c_float(0.5), c_float(0.3), eos, *out),
+                }
+                row = {}
+                for name, call in calls.items():
+                    for _ in range(3):
+                        _lib.check(call())
+                    times = []
+                    for _ in range(20):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        _lib.check(call())
+                        b.record()
+                        b.synchronize()
+                        times.append(a.elapsed_time(b))
+                    h, n = hyp.cpu().numpy()[0], hl.cpu().numpy()[0]
+                    errs = sum(levenshtein(h[s:s + k], r) for s, k, r in zip(np.cumsum([0] + utt[:-1]), n, refs))
+                    row[name] = (float(np.median(times)), min(times), max(times), errs)
+                for name, (med, lo, hi, errs) in row.items():
+                    print("  graph W=%3d %-14s %-8s: %8.3f ms/call (min %.3f max %.3f) = %6.2f us per frame step%s; label errors %d"
+                          % (W, "label_topk %d" % K if K else "unpruned", name, med, lo, hi, med * 1e3 / Tn,
+                             ", %.3f x the n-gram search" % (med / row["n-gram"][0]) if name == "graph" else "", errs))
 
 
 def _median_ms(call, warm=3, K=20):
