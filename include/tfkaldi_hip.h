@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 16
+#define TFK_ABI_VERSION 17
 
 typedef struct tfk_engine tfk_engine;
 
@@ -574,6 +574,81 @@ int tfk_ctc_mwer_logits(void* stream, const float* logits, int64_t ld, int32_t O
                         const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
                         const int32_t* ref_labels, const int32_t* ref_off, float ctc_weight, float* dlogits, int64_t ldd,
                         float* risk, float* score, int32_t* edits);
+/* (ABI 17) MAXIMUM MUTUAL INFORMATION against a denominator graph (CTC-CRF; lattice-free MMI with the CTC topology).  The
+ * numerator is the CTC likelihood of the reference; the denominator is the total likelihood of EVERY label sequence the graph
+ * accepts, summed exactly by a forward-backward sweep over the graph composed with the CTC topology -- nothing is sampled, no
+ * beam prunes the sum, and no decode precedes the step.
+ * The graph G is a deterministic weighted acceptor in exactly the layout of tfk_ctc_graph_set: weight[S][O], next[S][O],
+ * start.  Column O - 1 of weight is the final weight and is ALWAYS read here; a graph in which every state is final at weight
+ * 0 expresses "no end constraint".  lm_scale (lambda >= 0, finite) multiplies every graph weight, final weights included.
+ * Composed lattice of an utterance with log-softmax rows lp_t: one state B_g per graph state g (we are in g, and the last
+ * frame was a blank or there was none), one state L_a per existing arc a = (src, c, dst) (the last frame emitted c while
+ * taking a); N = S + A states, A the number of arcs.  In the probability domain, with w_a = exp(lambda weight[src][c]) and
+ * f_g = exp(lambda weight[g][O - 1]):
+ *   alpha_0[B_start] = p_0(blank);  alpha_0[L_a] = w_a p_0(c_a) for arcs leaving start;  everything else 0
+ *   alpha_t[B_g] = p_t(blank) (alpha_{t-1}[B_g] + sum_{a: dst(a) = g} alpha_{t-1}[L_a])
+ *   alpha_t[L_a] = p_t(c_a) (alpha_{t-1}[L_a]
+ *                            + w_a (alpha_{t-1}[B_src(a)] + sum_{a': dst(a') = src(a), c_a' != c_a} alpha_{t-1}[L_a']))
+ *   Z = sum_g f_g (alpha_{T-1}[B_g] + sum_{a: dst(a) = g} alpha_{T-1}[L_a])
+ * (c_a' != c_a is CTC's rule that a repeated label needs a blank in between).  The backward variables mirror this, with the
+ * emission of frame t included, as the CTC loss has it:
+ *   beta_{T-1}[B_g] = f_g p(blank);  beta_{T-1}[L_a] = f_dst(a) p(c_a)
+ *   beta_t[B_g] = p_t(blank) (beta_{t+1}[B_g] + sum_{a: src = g} w_a beta_{t+1}[L_a])
+ *   beta_t[L_a] = p_t(c_a) (beta_{t+1}[L_a] + beta_{t+1}[B_dst(a)] + sum_{a': src(a') = dst(a), c_a' != c_a} w_a' beta_{t+1}[L_a'])
+ * Per utterance u with reference y_u, G(y) = the arc weights along y plus the final weight of the state it reaches:
+ *   loss_u      = -(log p_ctc(y_u | z) + lambda G(y_u)) + log Z_u          (>= 0 whenever y_u is accepted)
+ *   dL/dz[t, c] = occ_den[t, c] - occ_num[t, c] + ctc_weight (softmax(z_t)[c] - occ_num[t, c])
+ *   batch_loss += sum_u loss_u + ctc_weight sum_u -log p_ctc(y_u | z)     (the second term only when ctc_weight > 0)
+ *   num_frames += the number of reference labels                         (as every CTC criterion here)
+ * occ_num is what the CTC loss subtracts from the softmax; occ_den[t, c] = the posterior of the composed states whose class is
+ * c, alpha_t beta_t / (p_t(c) Z), folded onto the classes (the softmax terms of numerator and denominator cancel).  Per frame
+ * occ_den is divided by its sum where that sum is within 1e-2 of one, as the loss does for occ_num.
+ * If no accepted label sequence fits an utterance's frames (Z = 0), or G does not accept its reference, or the utterance is too
+ * short for its labels, the utterance contributes +inf to the loss and a zero gradient.  A zero-frame utterance: loss 0 if the
+ * reference is empty and start is final, +inf otherwise.  Sums run in a fixed order with no floating-point atomics: two calls
+ * on the same input give the same bits.  A sum "over the other labels" (c_a' != c_a) is formed by ADDING the other terms, never
+ * by subtracting one from a total (which cancels catastrophically when one label dominates).
+ * Numerics: fp32 values relative to an offset held in double, re-centred every frame by an exact power of two on the
+ * previous frame's maximum, offsets stored per frame; log Z, G(y) and the loss in double, rounded once.
+ * tfk_ctc_den_set: the denominator is a model of its own, separate from the decoding model of tfk_ctc_graph_set /
+ * tfk_ctc_lm_set -- neither call disturbs the other.  Validation as tfk_ctc_graph_set, and the same failure rule: a refused
+ * call leaves the old model in force.  weight == NULL drops the model.  Limits, named in the message before anything is
+ * allocated: output_dim in [2, 1024]; S x O <= 2^25 entries per table; N = S + A <= 65536 composed states (an order-3 n-gram
+ * over 35 characters plus the blank is N = 46656).  The tables are compiled on the host, once per call, into gather-only
+ * index lists (incoming arcs of a state grouped by label), so the sweeps need no scatter and no atomics.
+ * tfk_accumulate_ctc_mmi and its variants: arguments as tfk_accumulate_ctc, plus lm_scale, ctc_weight.  One workgroup per
+ * (utterance, direction); the running vector lives in LDS while [O | N | S + groups] floats fit 159 KiB, in the workgroup's
+ * own global scratch beyond.  Scratch: 8 bytes per frame and composed state (rounded up to 64).  Errors (non-zero; the
+ * accumulators are untouched and the engine stays usable): those of tfk_accumulate_ctc, checked before the pass starts; no
+ * denominator set; lm_scale or ctc_weight negative or not finite; more than 2^31 lattice cells (T x N rounded up to 64).
+ * TFK_LAST_MICROBATCH, TFK_DEVICE_PTRS and the set-aside of an open step's sums during evaluation as everywhere else. */
+int tfk_ctc_den_set(tfk_engine* e, const float* weight, const int32_t* next, int32_t num_states, int32_t start);
+/* What the compile of the denominator graph in force found (any pointer may be NULL): its states S, arcs A, groups K (the
+ * distinct (target state, label) pairs; N = S + A) and where its sweeps keep their data -- residence 0: the vector and the
+ * sums in the workgroup's global scratch; 1: both in LDS; 2: the index tables and arc weights in LDS as well.  An error when
+ * no denominator is set. */
+int tfk_ctc_den_info(tfk_engine* e, int32_t* num_states, int32_t* num_arcs, int32_t* num_groups, int32_t* residence);
+int tfk_accumulate_ctc_mmi(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                           const int32_t* labels, const int32_t* label_len, float lm_scale, float ctc_weight, int flags);
+int tfk_eval_accumulate_ctc_mmi(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                const int32_t* labels, const int32_t* label_len, float lm_scale, float ctc_weight, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_accumulate_ctc_raw; TFK_RAW_DEVICE allowed). */
+int tfk_accumulate_ctc_mmi_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                               int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                               float lm_scale, float ctc_weight, int flags);
+int tfk_eval_accumulate_ctc_mmi_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                    int32_t U, int32_t context_width, const float* cmvn, const int32_t* labels,
+                                    const int32_t* label_len, float lm_scale, float ctc_weight, int flags);
+/* (ABI 17) Tests / tools: the criterion alone on logits [T, ld] of O classes, DEVICE pointers: seg[U + 1] = first row of every
+ * utterance (seg[0] = 0, seg[U] = T > 0), lab_off[U + 1] = first label of every reference in labels (lab_off[0] = 0),
+ * weight_dev / next_dev [num_states, O] the graph.  Out: utt_loss [U] = loss_u, logz [U] = log Z_u (-inf: Z = 0) and -- unless
+ * dlogits is NULL, which asks for those two only -- dlogits [T, ldd] = dL/dz as above (columns [O, ldd) zero).  dlogits may be
+ * the logits themselves.  The tables are read back, compiled and uploaded first (synchronisations of `stream`); the kernels
+ * and the call's own scratch (from the stream's memory pool) are stream-ordered. */
+int tfk_ctc_mmi_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                       const int32_t* labels, const int32_t* lab_off, const float* weight_dev, const int32_t* next_dev,
+                       int32_t num_states, int32_t start, float lm_scale, float ctc_weight, float* utt_loss, float* logz,
+                       float* dlogits, int64_t ldd);
 /* (ABI 9) Tests / tools: tf.edit_distance(normalize=False) of U pairs of int32 sequences, stream-ordered on `stream`,
  * DEVICE pointers: dist[u] = Levenshtein distance of hyp[hyp_off[u], hyp_off[u + 1]) and ref[ref_off[u], ref_off[u + 1]);
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */

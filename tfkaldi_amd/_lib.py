@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -183,6 +183,19 @@ SYMBOLS = {
     "tfk_ctc_mwer_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p,
                                     c_void_p]),
+    "tfk_ctc_den_set": (c_int, [_E, c_void_p, c_void_p, c_int32, c_int32]),
+    "tfk_ctc_den_info": (c_int, [_E, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "tfk_accumulate_ctc_mmi": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_float,
+                                       c_int]),
+    "tfk_eval_accumulate_ctc_mmi": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_float,
+                                            c_float, c_int]),
+    "tfk_accumulate_ctc_mmi_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_float, c_float, c_int]),
+    "tfk_eval_accumulate_ctc_mmi_raw": (c_int, [_E, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                                c_void_p, c_void_p, c_float, c_float, c_int]),
+    "tfk_ctc_mmi_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_int64]),
     "tfk_label_edit_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "tfk_set_prior": (c_int, [_E, c_void_p, c_size_t]),
     "tfk_reduce_region": (c_int, [_E, POINTER(c_void_p), POINTER(c_size_t)]),

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "kernels.h"
 
 namespace tfk {
@@ -198,6 +200,88 @@ constexpr int kCtcMwerSweep = 1, kCtcMwerWeights = 2, kCtcMwerGrad = 4, kCtcMwer
 void ctc_mwer(hipStream_t s, const CtcMwer& m, float* dlogits, int ldd, int row0, int rows, Twin tw, int stages = kCtcMwerAll);
 // scalars[0] (+)= sum_u risk[u] + ctc_weight * the references' losses, scalars[1] (+)= ref_labels, scalars[2] (+)= 1
 void ctc_mwer_loss_reduce(hipStream_t s, const CtcMwer& m, int ref_labels, float* scalars, bool overwrite);
+// MMI against a denominator graph (CTC-CRF; the contract is the comment at tfk_accumulate_ctc_mmi in tfkaldi_hip.h): per
+// utterance loss = -(log p_ctc(y | z) + lm_scale * G(y)) + log Z, Z = the total likelihood of every label sequence the
+// deterministic acceptor G (layout of tfk_ctc_graph_set, final weights always read) accepts, summed exactly by a
+// forward-backward sweep over G composed with the CTC topology: one state B_g per graph state (last frame blank or none), one
+// state L_a per arc (last frame emitted the arc's label), N = S + A.
+// ctc_den_compile (host, once per graph) turns (weight, next) into GATHER-ONLY index tables, so the recursion needs no scatter
+// and no atomics.  Arcs are numbered by (label, source), so the composed states of one class are contiguous (the gradient's
+// segmented sum reads them in order); K groups = the distinct (target state, label) pairs, numbered by (state, label).
+//   tab = [fx A | bx A | g0 S+1 | ffirst S+1 | fterm A | flo K | fhi K | bfirst S+1 | bterm A | blo K | bhi K | cfirst O]
+//   fx / bx    per arc: (label << 16) | index into the frame's sums [S + K] that the arc adds to its own value -- forward: the
+//              source's group of the arc's own label if it has one (its "all other labels" sum), else the source's total;
+//              backward: the target's group of the arc's label
+//   g0         per state: its groups;  ffirst / fterm: its incoming arcs ordered by (label, arc), flo / fhi: every group's
+//              own run in that list;  bfirst / bterm: its outgoing arcs ordered by label, blo / bhi: the (at most one) arc of
+//              the group's label in that list;  cfirst: first arc of every label (cfirst[O - 1] = A)
+//   logw       [A arc weights in arc order | S final weights] natural logs, -inf: not final
+// A frame of a sweep is two phases with a workgroup barrier between them: (1) one thread per graph state forms
+// sums[g] = v[B_g] + all terms and, per group k, sums[S + k] = v[B_g] + the terms OUTSIDE [lo, hi) -- by ADDING a prefix and a
+// suffix, never by subtracting from the total; (2) one thread per composed state updates it in place from its own value and
+// one entry of sums.  Values are fp32 in the PROBABILITY domain relative to an offset held in double: every frame's vector is
+// divided by the previous vector's maximum (known one barrier earlier, so the re-centring costs no barrier of its own; a
+// period of one frame, because a grammar that forbids the frame's dominant class loses e^-30 in a single frame of a peaked
+// model), the logarithms accumulate in the offset, which is stored per frame.
+struct CtcDenGraph {  // host
+  int O = 0, S = 0, A = 0, K = 0, N = 0, start = 0;
+  std::vector<int32_t> tab;
+  std::vector<float> logw;
+  // the graph itself for ctc_den_walk: out-arcs of state g are [ofirst[g], ofirst[g + 1]), ordered by label
+  std::vector<int32_t> ofirst, olabel, odst;
+  std::vector<float> oweight;
+};
+constexpr int kCtcDenMaxStates = 65536;    // composed states N = S + A
+constexpr int kCtcDenMaxClasses = 1024;    // one thread stages one class of the frame's row
+constexpr int64_t kCtcDenMaxCells = (int64_t)1 << 31;  // frames x state stride of one direction's scratch (8 GiB)
+constexpr size_t kCtcDenMaxLds = 160 * 1024 - 1024;    // of one workgroup's dynamic LDS (the rest: its static arrays)
+// NULL, or the limit a graph breaks -- from the two tables alone, before anything is allocated (arcs: the finite entries of
+// columns [0, O - 1))
+const char* ctc_den_graph_limits(int O, int64_t num_states, int64_t arcs);
+// NULL, or the limit a batch breaks on a graph of N composed states
+const char* ctc_den_limits(int O, int T, int U, int N);
+inline int ctc_den_stride(int N) { return (N + 63) & ~63; }
+// weight / next [S, O] as tfk_ctc_graph_set takes them (validated by the caller)
+void ctc_den_compile(const float* weight, const int32_t* next, int S, int O, int start, CtcDenGraph* g);
+// lm-unscaled G(y) in double: the arc weights along y plus the final weight of the state it reaches; -inf: rejected
+double ctc_den_walk(const CtcDenGraph& g, const int32_t* labels, int n);
+inline size_t ctc_den_tab_words(int S, int A, int K, int O) { return 4 * (size_t)A + 3 * ((size_t)S + 1) + 4 * (size_t)K + O; }
+struct CtcDen {
+  const int32_t* tab;  // device copy of CtcDenGraph::tab
+  const float* logw;   // device copy of CtcDenGraph::logw
+  int O, S, A, K, N, start;
+  const float* post;   // [T, ld] softmax rows (ctc_loss_grad leaves them in CtcBatch::post)
+  int ld, T, U;
+  const int32_t* seg;  // [U + 1]
+  float lm_scale, ctc_weight;
+  int stride;          // ctc_den_stride(N)
+  bool lds;            // residence of the running vector and the sums: LDS, or the workgroup's own global scratch
+  bool tab_lds;        // the tables and wexp are copied into LDS too (they fit beside the vector)
+  // scratch (ctc_den_carve points these into one block of ctc_den_scratch_bytes bytes)
+  double *offa, *offb, *logz;  // [T] [T] [U]
+  float *va, *vb;              // [T, stride] every frame's forward / backward vector (vb: gradient only)
+  float *wexp;                 // [A + S] exp(lm_scale * logw)
+  float *gv, *gs;              // [2U, stride] [2U, S + K] global residence only
+  const double* gy;            // [U] lm-unscaled G(reference) (-inf: rejected), filled by the caller
+  float* utt_loss;             // [U] out: the MMI loss, +inf for an infeasible / rejected utterance
+};
+size_t ctc_den_lds_bytes(int O, int N, int S, int K, bool lds);
+// where a graph's sweep keeps its data: 0 = the vector and the sums in the workgroup's global scratch, 1 = both in LDS,
+// 2 = the index tables and the arc weights in LDS as well -- the one place that decides it (ctc_den_carve follows it)
+int ctc_den_residence(int O, int N, int S, int A, int K);
+size_t ctc_den_scratch_bytes(const CtcDen& d, bool with_grad);
+void ctc_den_carve(void* scratch, CtcDen* d, bool with_grad);  // (sets d->lds, d->tab_lds, d->stride)
+// stages, enqueued one by one in this order by a caller that times them apart.  Sweep: wexp, the forward (and, with_grad, the
+// backward) sweep, logz, and utt_loss from the numerator's CtcBatch (after ctc_loss_grad on the same stream: logz / utt_loss
+// of the references).  Grad: rows [row0, row0 + rows) of dlogits [., ldd] <- occ_den - softmax + (1 + ctc_weight) * g with
+// g [., ldg] = softmax - occ_num as ctc_loss_grad wrote it (zero rows for an utterance whose loss is +inf; columns beyond O:
+// zero) and the bf16 twin.  dlogits may be g itself: a thread reads an element before it writes it.
+// logz_out (NULL: not wanted): [U] floats, log Z per utterance (-inf: no accepted sequence fits)
+void ctc_den_sweep(hipStream_t s, const CtcDen& d, const CtcBatch& num, bool with_grad, float* logz_out = nullptr);
+void ctc_den_grad(hipStream_t s, const CtcDen& d, const float* g, int ldg, float* dlogits, int ldd, int row0, int rows, Twin tw);
+// scalars[0] (+)= sum_u utt_loss (+ ctc_weight * the references' CTC losses), scalars[1] (+)= ref_labels, scalars[2] (+)= 1
+void ctc_den_loss_reduce(hipStream_t s, const CtcDen& d, const float* ctc_utt_loss, int ref_labels, float* scalars,
+                         bool overwrite);
 // tf.edit_distance(normalize=False): dist[u] = Levenshtein distance (unit costs) of hyp[hyp_off[u], + H_u) and
 // ref[ref_off[u], ref_off[u + 1]), H_u = hyp_cnt ? hyp_cnt[u] : hyp_off[u + 1] - hyp_off[u].  max_ref >= every reference
 // length selects the register tile; a pair with a negative length or a reference longer than min(max_ref rounded up,

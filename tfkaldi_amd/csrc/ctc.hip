@@ -18,6 +18,7 @@
 #include "ctc.h"
 
 #include <math.h>
+#include <string.h>
 
 namespace tfk {
 namespace {
@@ -1796,6 +1797,284 @@ ctc_mwer_loss_reduce_kernel(const float* __restrict__ risk, const float* __restr
   }
 }
 
+// ---- MMI against a denominator graph: the exact sum over every label sequence a grammar accepts (the contract is stated at
+// tfk_accumulate_ctc_mmi in tfkaldi_hip.h, the tables and the two phases of a frame at CtcDenGraph in ctc.h) ----
+
+struct DenTab {
+  const int32_t *fx, *bx, *g0, *ffirst, *fterm, *flo, *fhi, *bfirst, *bterm, *blo, *bhi, *cfirst;
+};
+__host__ __device__ inline DenTab den_tab(const int32_t* t, int S, int A, int K) {
+  DenTab d;
+  d.fx = t;                    d.bx = d.fx + A;             d.g0 = d.bx + A;
+  d.ffirst = d.g0 + S + 1;     d.fterm = d.ffirst + S + 1;  d.flo = d.fterm + A;  d.fhi = d.flo + K;
+  d.bfirst = d.fhi + K;        d.bterm = d.bfirst + S + 1;  d.blo = d.bterm + A;  d.bhi = d.blo + K;
+  d.cfirst = d.bhi + K;
+  return d;
+}
+
+// wexp[i] = exp(lm_scale * logw[i]) for the A arc weights and the S final weights (-inf: exactly 0, also at lm_scale = 0)
+__global__ void __launch_bounds__(256)
+ctc_den_prep_kernel(CtcDen d) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.A + d.S) return;
+  const float w = d.logw[i];
+  d.wexp[i] = w > -INFINITY ? (float)exp((double)d.lm_scale * (double)w) : 0.f;
+}
+
+constexpr int kDenPF = 4;  // rows of the softmax in flight ahead of the chain
+
+// the power of two that brings m into [1, 2), as (factor, its binary exponent): exact in fp32, so the offset (a count of
+// binary exponents) says exactly what the stored values were multiplied by.  m == 0 (no path survives) or not finite: (1, 0)
+__device__ __forceinline__ float den_scale(float m, int* e) {
+  const int eb = (__builtin_bit_cast(int, m) >> 23) & 0xff;
+  const bool ok = m > 0.f && eb != 0xff;
+  *e = ok ? eb - 127 : 0;
+  return ok ? __builtin_bit_cast(float, (254 - eb) << 23) : 1.f;
+}
+
+// phase 1 of a frame: thread per graph state g, sums[g] = v[B_g] + every term, sums[S + k] = v[B_g] + the terms outside
+// group k's own [lo, hi) -- a suffix recorded on the way down, then a prefix added on the way up
+template <int NT, bool BWD>
+__device__ __forceinline__ void den_phase1(const float* v, float* sums, const float* __restrict__ wexp, int S,
+                                           const int32_t* __restrict__ g0, const int32_t* __restrict__ first,
+                                           const int32_t* __restrict__ term, const int32_t* __restrict__ lo,
+                                           const int32_t* __restrict__ hi) {
+  for (int g = threadIdx.x; g < S; g += NT) {
+    const int j0 = first[g], j1 = first[g + 1], k0 = g0[g], k1 = g0[g + 1];
+    const float self = v[g];
+    if (k1 - k0 == 1 && lo[k0] == j0 && hi[k0] == j1) {  // one group that is every term (a trie, an n-gram): a select
+      float tot = 0.f;
+      for (int j = j0; j < j1; ++j) {
+        const int a = term[j];
+        tot += BWD ? wexp[a] * v[S + a] : v[S + a];
+      }
+      sums[S + k0] = self;
+      sums[g] = self + tot;
+      continue;
+    }
+    if (k1 > k0) {
+      float suf = 0.f;
+      int k = k1 - 1;
+      for (int j = j1 - 1; j >= j0; --j) {
+        while (k >= k0 && hi[k] > j) sums[S + k--] = suf;
+        const int a = term[j];
+        suf += BWD ? wexp[a] * v[S + a] : v[S + a];
+      }
+      while (k >= k0) sums[S + k--] = suf;
+    }
+    float pre = 0.f;
+    int k = k0;
+    for (int j = j0; j < j1; ++j) {
+      for (; k < k1 && lo[k] <= j; ++k) sums[S + k] = self + (pre + sums[S + k]);
+      const int a = term[j];
+      pre += BWD ? wexp[a] * v[S + a] : v[S + a];
+    }
+    for (; k < k1; ++k) sums[S + k] = self + (pre + sums[S + k]);
+    sums[g] = self + pre;
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ void den_block_max(float mx, float* wmax) {
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+}
+
+// One direction of one utterance on one workgroup.  v [N]: the running vector, sums [S + K]: phase 1's results -- both in LDS
+// or both in the workgroup's own global scratch; prow [O] and wmax [NT / 64] in LDS.
+// Forward: v_{-1} = 1 at B_start, frame t: B_g <- p(blank) sums[g], L_a <- p(c_a) (v[L_a] + w_a sums[fx(a)]); at the end
+// Z = sum_g f_g sums[g] of one more phase 1.  Backward: v_T = f_g at B_g, frame t: B_g <- p(blank) sums[g] (terms w_a v[L_a]),
+// L_a <- p(c_a) (v[L_a] + sums[bx(a)]) -- beta with the emission of its own frame, as ctc_alpha_beta_kernel has it.
+template <int NT, bool BWD>
+__device__ __forceinline__ void den_sweep_body(const CtcDen& d, int u, float* v, float* sums, float* prow, float* wmax,
+                                               double* zpart, const int32_t* tab, const float* wexp) {
+  const int tid = threadIdx.x;
+  const int r0 = d.seg[u], Tn = d.seg[u + 1] - r0;
+  const int S = d.S, N = d.N, O = d.O;
+  const float* fexp = wexp + d.A;
+  const float* __restrict__ fexp_g = d.wexp + d.A;  // (the global copy: what may be read before the first barrier)
+  if (Tn <= 0) {  // an utterance without frames: only the empty sequence, accepted if the start is final
+    if (!BWD && tid == 0)
+      d.logz[u] = fexp_g[d.start] > 0.f ? (double)d.lm_scale * (double)d.logw[d.A + d.start] : -(double)INFINITY;
+    return;
+  }
+  const DenTab tb = den_tab(tab, S, d.A, d.K);
+  const int32_t* __restrict__ first = BWD ? tb.bfirst : tb.ffirst;
+  const int32_t* __restrict__ term = BWD ? tb.bterm : tb.fterm;
+  const int32_t* __restrict__ lo = BWD ? tb.blo : tb.flo;
+  const int32_t* __restrict__ hi = BWD ? tb.bhi : tb.fhi;
+  const int32_t* __restrict__ ax = BWD ? tb.bx : tb.fx;
+  float* __restrict__ rows = (BWD ? d.vb : d.va) + (size_t)r0 * d.stride;
+  double* __restrict__ offs = (BWD ? d.offb : d.offa) + r0;
+  {
+    float mx = 0.f;
+    for (int i = tid; i < N; i += NT) {
+      const float x = BWD ? (i < S ? fexp_g[i] : 0.f) : (i == d.start ? 1.f : 0.f);
+      v[i] = x;
+      mx = fmaxf(mx, x);
+    }
+    den_block_max<NT>(mx, wmax);
+  }
+  // The chain is Tn dependent frames; a row of the softmax takes longer to arrive than a frame of a small graph lasts, so
+  // kDenPF rows are in flight in registers (one class per thread), with clamped row indices instead of guards.
+  const float* pbase = d.post + (size_t)r0 * d.ld + min(tid, O - 1);
+  float pre[kDenPF];
+#pragma unroll
+  for (int j = 0; j < kDenPF; ++j) {
+    const int n = min(j, Tn - 1);
+    pre[j] = pbase[(size_t)(BWD ? Tn - 1 - n : n) * d.ld];
+  }
+  long long eacc = 0;  // the offset in binary exponents: off = eacc * ln 2
+  __syncthreads();
+  for (int n0 = 0; n0 < Tn; n0 += kDenPF) {
+#pragma unroll
+    for (int j = 0; j < kDenPF; ++j) {
+      const int n = n0 + j;
+      const float cur = pre[j];
+      {
+        const int nn = min(n + kDenPF, Tn - 1);
+        pre[j] = pbase[(size_t)(BWD ? Tn - 1 - nn : nn) * d.ld];
+      }
+      if (n < Tn) {  // (uniform over the workgroup)
+        const int t = BWD ? Tn - 1 - n : n;
+        float m = wmax[0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, wmax[w]);
+        int e;
+        const float scale = den_scale(m, &e);
+        eacc += e;
+        if (tid < O) prow[tid] = cur;
+        den_phase1<NT, BWD>(v, sums, wexp, S, tb.g0, first, term, lo, hi);
+        __syncthreads();
+        const float pb = prow[O - 1] * scale;
+        float mx = 0.f;
+        float* __restrict__ row = rows + (size_t)t * d.stride;
+        for (int i = tid; i < N; i += NT) {
+          float nv;
+          if (i < S) {
+            nv = pb * sums[i];
+          } else {
+            const int a = i - S;
+            const uint32_t wd = (uint32_t)ax[a];
+            const float in = sums[wd & 0xffffu];
+            nv = (prow[wd >> 16] * scale) * (v[i] + (BWD ? in : wexp[a] * in));
+          }
+          v[i] = nv;
+          row[i] = nv;
+          mx = fmaxf(mx, nv);
+        }
+        den_block_max<NT>(mx, wmax);
+        if (tid == 0) offs[t] = (double)eacc * 0.6931471805599453;
+        __syncthreads();
+      }
+    }
+  }
+  if (BWD) return;
+  den_phase1<NT, false>(v, sums, wexp, S, tb.g0, first, term, lo, hi);
+  __syncthreads();
+  double z = 0.0;  // fixed order: thread-strided, the butterfly, then the waves one after the other
+  for (int g = tid; g < S; g += NT) z += (double)fexp[g] * (double)sums[g];
+  for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+  if ((tid & 63) == 0) zpart[tid >> 6] = z;
+  __syncthreads();
+  if (tid == 0) {
+    z = 0.0;
+    for (int w = 0; w < NT / 64; ++w) z += zpart[w];
+    d.logz[u] = z > 0.0 ? (double)eacc * 0.6931471805599453 + log(z) : -(double)INFINITY;
+  }
+}
+
+// blockIdx.x: the utterance; blockIdx.y = 0: the forward sweep and log Z, 1 (gradient only): the backward sweep -- two
+// independent workgroups of one launch, as ctc_alpha_beta_kernel's two waves
+template <int NT, bool LDS>
+__global__ void __launch_bounds__(NT)
+ctc_den_sweep_kernel(CtcDen d) {
+  extern __shared__ float den_lds[];
+  __shared__ float wmax[NT / 64];
+  __shared__ double zpart[NT / 64];
+  const int u = blockIdx.x, wg = blockIdx.y * d.U + blockIdx.x;
+  float* prow = den_lds;
+  const int orow = (d.O + 63) & ~63;
+  float* v = LDS ? den_lds + orow : d.gv + (size_t)wg * d.stride;
+  float* sums = LDS ? den_lds + orow + d.N : d.gs + (size_t)wg * (d.S + d.K);
+  // The index tables and the weights are the same at every frame, and a frame of a small graph is a handful of DEPENDENT
+  // loads of them: where they fit beside the vector they are copied into LDS once (generic pointers from here on: the
+  // loads are flat instructions, which serve both address spaces).  The barrier that follows the initial vector covers them.
+  const int32_t* tab = d.tab;
+  const float* wexp = d.wexp;
+  if (LDS && d.tab_lds) {
+    const int words = 4 * d.A + 3 * (d.S + 1) + 4 * d.K + d.O;
+    int32_t* lt = reinterpret_cast<int32_t*>(den_lds + orow + d.N + d.S + d.K);
+    float* lw = reinterpret_cast<float*>(lt + words);
+    for (int i = threadIdx.x; i < words; i += NT) lt[i] = d.tab[i];
+    for (int i = threadIdx.x; i < d.A + d.S; i += NT) lw[i] = d.wexp[i];
+    tab = lt;
+    wexp = lw;
+  }
+  if (blockIdx.y == 0) den_sweep_body<NT, false>(d, u, v, sums, prow, wmax, zpart, tab, wexp);
+  else den_sweep_body<NT, true>(d, u, v, sums, prow, wmax, zpart, tab, wexp);
+}
+
+// utt_loss[u] = -(log p_ctc(y_u) + lm_scale G(y_u)) + log Z_u in double, rounded once; +inf where the reference does not fit
+// its frames, the graph rejects it, or no accepted sequence fits the frames
+__global__ void __launch_bounds__(256)
+ctc_den_loss_kernel(CtcDen d, const double* __restrict__ num_logz, const float* __restrict__ num_loss,
+                    float* __restrict__ logz_out) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= d.U) return;
+  const bool ok = num_loss[u] < INFINITY && d.logz[u] > -INFINITY && d.gy[u] > -INFINITY;
+  if (logz_out) logz_out[u] = (float)d.logz[u];
+  d.utt_loss[u] = ok ? (float)(-(num_logz[u] + (double)d.lm_scale * d.gy[u]) + d.logz[u]) : INFINITY;
+}
+
+// One workgroup of four waves per logits row t; dynamic LDS: occ [O].  Class c's composed states are contiguous (the blank:
+// the S states B_g; label c: arcs [cfirst[c], cfirst[c + 1])), so occ[c] = sum over them of alpha_t beta_t e^(offa + offb -
+// log Z) / p_t(c) is a segmented sum in a fixed order: wave c % 4 takes class c, lane-strided, then the butterfly.  The
+// product is formed in double (alpha and beta are each relative to their own offset, and the exponent can be large where the
+// two sweeps put their mass on different states).  occ is divided by its sum where that is within 1e-2 of one, as
+// ctc_grad_kernel does and for its reasons.
+__global__ void __launch_bounds__(256)
+ctc_den_grad_kernel(CtcDen d, const float* g, int ldg, int row0, float* dlogits, int ldd, Twin tw) {
+  extern __shared__ float occ[];
+  __shared__ float inv_s;
+  const int t = row0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int u = utt_of(d.seg, d.U, t);
+  const bool live = d.utt_loss[u] < INFINITY;
+  const float* pr = d.post + (size_t)t * d.ld;
+  if (live) {  // (uniform)
+    const DenTab tb = den_tab(d.tab, d.S, d.A, d.K);
+    const double sc = exp(d.offa[t] + d.offb[t] - d.logz[u]);
+    const float* al = d.va + (size_t)t * d.stride;
+    const float* be = d.vb + (size_t)t * d.stride;
+    for (int c = wave; c < d.O; c += 4) {
+      const int i0 = c == d.O - 1 ? 0 : d.S + tb.cfirst[c];
+      const int i1 = c == d.O - 1 ? d.S : d.S + tb.cfirst[c + 1];
+      float acc = 0.f;
+      for (int i = i0 + lane; i < i1; i += 64) acc += (float)((double)al[i] * (double)be[i] * sc);
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      const float p = pr[c];
+      if (lane == 0) occ[c] = p > 0.f ? acc / p : 0.f;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      float tot = 0.f;
+      for (int c = lane; c < d.O; c += 64) tot += occ[c];
+      for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+      if (lane == 0) inv_s = fabsf(tot - 1.f) < 1e-2f ? 1.f / tot : 1.f;
+    }
+    __syncthreads();
+  }
+  const float inv = live ? inv_s : 0.f, k = 1.f + d.ctc_weight;
+  const float* gr = g + (size_t)t * ldg;
+  float* dr = dlogits + (size_t)t * ldd;
+  for (int c = tid; c < ldd; c += 256) {
+    // (read before the write: dlogits may be g itself)
+    const float x = (live && c < d.O) ? (occ[c] * inv - pr[c]) + k * gr[c] : 0.f;
+    dr[c] = x;
+    if (tw.p) twin_put(tw, (size_t)t, c, x);
+  }
+}
+
 }  // namespace
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
@@ -2073,6 +2352,193 @@ static void ctc_mwer_sweep(hipStream_t s, const CtcMwer& m, bool with_grad) {
 void ctc_mwer_loss_reduce(hipStream_t s, const CtcMwer& m, int ref_labels, float* scalars, bool overwrite) {
   hipLaunchKernelGGL(ctc_mwer_loss_reduce_kernel, dim3(1), dim3(256), 0, s, m.risk,
                      m.NP > m.P ? m.utt_loss + m.P : (const float*)nullptr, m.U, m.ctc_weight, (float)ref_labels, scalars,
+                     overwrite ? 1 : 0);
+}
+
+const char* ctc_den_graph_limits(int O, int64_t num_states, int64_t arcs) {
+  if (O < 2 || O > kCtcDenMaxClasses) return "output_dim outside [2, 1024]";
+  if (num_states < 1) return "num_states < 1";
+  if (num_states * O > (int64_t)kCtcGraphMaxEntries) return "more than 2^25 entries per table (S x O)";
+  if (num_states + arcs > kCtcDenMaxStates) return "more than 65536 composed states (N = states + arcs)";
+  return nullptr;
+}
+
+const char* ctc_den_limits(int O, int T, int U, int N) {
+  if (O < 2 || O > kCtcDenMaxClasses) return "output_dim outside [2, 1024]";
+  if (N < 1 || N > kCtcDenMaxStates) return "more than 65536 composed states (N = states + arcs)";
+  if (T < 0 || T > kCtcAlignMaxFrames) return "more than 8388607 frames";
+  if (U < 0 || U > (1 << 20)) return "more than 1048576 utterances";
+  if ((int64_t)T * ctc_den_stride(N) > kCtcDenMaxCells)
+    return "more than 2^31 lattice cells (frames x padded composed states) in one call";
+  return nullptr;
+}
+
+void ctc_den_compile(const float* weight, const int32_t* next, int S, int O, int start, CtcDenGraph* g) {
+  struct Arc { int src, c, dst; float w; };
+  std::vector<Arc> arcs;
+  std::vector<int32_t> cfirst(O, 0);
+  for (int c = 0; c < O - 1; ++c) {  // arc order: (label, source)
+    cfirst[c] = (int32_t)arcs.size();
+    for (int s = 0; s < S; ++s) {
+      const float w = weight[(size_t)s * O + c];
+      if (w > -INFINITY) arcs.push_back({s, c, next[(size_t)s * O + c], w});
+    }
+  }
+  const int A = (int)arcs.size();
+  cfirst[O - 1] = A;
+  // per state: outgoing arcs by label, incoming arcs by (label, arc) -- both fall out of the arc order
+  std::vector<std::vector<int32_t>> out(S), in(S);
+  for (int a = 0; a < A; ++a) {
+    out[arcs[a].src].push_back(a);
+    in[arcs[a].dst].push_back(a);
+  }
+  // groups: the runs of one label in a state's incoming list
+  std::vector<int32_t> g0(S + 1, 0), ffirst(S + 1, 0), bfirst(S + 1, 0), fterm, bterm, flo, fhi, blo, bhi, garc(A, 0);
+  std::vector<int32_t> glabel;
+  for (int s = 0; s < S; ++s) {
+    for (size_t j = 0; j < in[s].size(); ++j) {
+      const int a = in[s][j];
+      if (j == 0 || arcs[in[s][j - 1]].c != arcs[a].c) {
+        if (j > 0) fhi.push_back((int32_t)fterm.size());
+        flo.push_back((int32_t)fterm.size());
+        glabel.push_back(arcs[a].c);
+      }
+      garc[a] = (int32_t)flo.size() - 1;
+      fterm.push_back(a);
+    }
+    if (!in[s].empty()) fhi.push_back((int32_t)fterm.size());
+    g0[s + 1] = (int32_t)flo.size();
+    ffirst[s + 1] = (int32_t)fterm.size();
+    for (int a : out[s]) bterm.push_back(a);
+    bfirst[s + 1] = (int32_t)bterm.size();
+  }
+  const int K = (int)flo.size();
+  blo.assign(K, 0);
+  bhi.assign(K, 0);
+  for (int s = 0; s < S; ++s)
+    for (int k = g0[s]; k < g0[s + 1]; ++k) {  // the out-arc of the group's label: out[s] is ordered by label
+      size_t j = 0;
+      while (j < out[s].size() && arcs[out[s][j]].c < glabel[k]) ++j;
+      blo[k] = bfirst[s] + (int32_t)j;
+      bhi[k] = blo[k] + ((j < out[s].size() && arcs[out[s][j]].c == glabel[k]) ? 1 : 0);
+    }
+  g->O = O; g->S = S; g->A = A; g->K = K; g->N = S + A; g->start = start;
+  g->tab.assign(ctc_den_tab_words(S, A, K, O), 0);
+  int32_t* t = g->tab.data();
+  int32_t* fx = t;
+  int32_t* bx = fx + A;
+  for (int a = 0; a < A; ++a) {
+    const Arc& r = arcs[a];
+    int x = r.src;  // the source's total, unless it is entered by this label too
+    for (int k = g0[r.src]; k < g0[r.src + 1]; ++k)
+      if (glabel[k] == r.c) x = S + k;
+    fx[a] = (int32_t)(((uint32_t)r.c << 16) | (uint32_t)x);
+    bx[a] = (int32_t)(((uint32_t)r.c << 16) | (uint32_t)(S + garc[a]));
+  }
+  int32_t* p = bx + A;
+  auto put = [&p](const std::vector<int32_t>& v) {
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(int32_t));
+    p += v.size();
+  };
+  put(g0); put(ffirst); put(fterm); put(flo); put(fhi); put(bfirst); put(bterm); put(blo); put(bhi); put(cfirst);
+  g->logw.resize((size_t)A + S);
+  for (int a = 0; a < A; ++a) g->logw[a] = arcs[a].w;
+  for (int s = 0; s < S; ++s) g->logw[(size_t)A + s] = weight[(size_t)s * O + O - 1];
+  g->ofirst = bfirst;
+  g->olabel.resize(A); g->odst.resize(A); g->oweight.resize(A);
+  for (int j = 0; j < A; ++j) {
+    g->olabel[j] = arcs[bterm[j]].c; g->odst[j] = arcs[bterm[j]].dst; g->oweight[j] = arcs[bterm[j]].w;
+  }
+}
+
+double ctc_den_walk(const CtcDenGraph& g, const int32_t* labels, int n) {
+  int s = g.start;
+  double total = 0.0;
+  for (int i = 0; i < n; ++i) {
+    int lo = g.ofirst[s], hi = g.ofirst[s + 1];
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (g.olabel[mid] < labels[i]) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= g.ofirst[s + 1] || g.olabel[lo] != labels[i]) return -(double)INFINITY;
+    total += (double)g.oweight[lo];
+    s = g.odst[lo];
+  }
+  return total + (double)g.logw[(size_t)g.A + s];
+}
+
+size_t ctc_den_lds_bytes(int O, int N, int S, int K, bool lds) {
+  return ((size_t)((O + 63) & ~63) + (lds ? (size_t)N + S + K : 0)) * sizeof(float);
+}
+
+int ctc_den_residence(int O, int N, int S, int A, int K) {
+  const size_t vec = ctc_den_lds_bytes(O, N, S, K, true);
+  if (vec > kCtcDenMaxLds) return 0;
+  return vec + (ctc_den_tab_words(S, A, K, O) + (size_t)A + S) * sizeof(float) <= kCtcDenMaxLds ? 2 : 1;
+}
+
+size_t ctc_den_scratch_bytes(const CtcDen& d, bool with_grad) {
+  const size_t t = (size_t)(d.T > 0 ? d.T : 0), u = (size_t)(d.U > 0 ? d.U : 0), stride = (size_t)ctc_den_stride(d.N);
+  const bool lds = ctc_den_residence(d.O, d.N, d.S, d.A, d.K) >= 1;
+  return (2 * t + u) * sizeof(double) +
+         ((with_grad ? 2 : 1) * t * stride + (size_t)d.A + d.S + (lds ? 0 : 2 * u * (stride + d.S + d.K))) * sizeof(float) + 16;
+}
+
+void ctc_den_carve(void* scratch, CtcDen* d, bool with_grad) {
+  const size_t t = (size_t)(d->T > 0 ? d->T : 0), u = (size_t)(d->U > 0 ? d->U : 0);
+  d->stride = ctc_den_stride(d->N);
+  const int where = ctc_den_residence(d->O, d->N, d->S, d->A, d->K);
+  d->lds = where >= 1;
+  d->tab_lds = where >= 2;
+  double* p = static_cast<double*>(scratch);
+  d->offa = p;
+  d->offb = p + t;
+  d->logz = p + 2 * t;
+  float* f = reinterpret_cast<float*>(p + 2 * t + u);
+  d->va = f;
+  f += t * d->stride;
+  d->vb = with_grad ? f : nullptr;
+  if (with_grad) f += t * d->stride;
+  d->wexp = f;
+  f += (size_t)d->A + d->S;
+  d->gv = d->lds ? nullptr : f;
+  d->gs = d->lds ? nullptr : f + 2 * u * d->stride;
+}
+
+template <int NT, bool LDS>
+static void den_launch(hipStream_t s, const CtcDen& d, bool with_grad) {
+  const size_t lds = ctc_den_lds_bytes(d.O, d.N, d.S, d.K, LDS) +
+                     (LDS && d.tab_lds ? (ctc_den_tab_words(d.S, d.A, d.K, d.O) + (size_t)d.A + d.S) * sizeof(float) : 0);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_den_sweep_kernel<NT, LDS>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((ctc_den_sweep_kernel<NT, LDS>), dim3(d.U, with_grad ? 2 : 1), dim3(NT), lds, s, d);
+}
+
+void ctc_den_sweep(hipStream_t s, const CtcDen& d, const CtcBatch& num, bool with_grad, float* logz_out) {
+  if (d.U <= 0) return;
+  hipLaunchKernelGGL(ctc_den_prep_kernel, dim3((unsigned)((d.A + d.S + 255) / 256)), dim3(256), 0, s, d);
+  // a workgroup of 256 threads while that leaves a thread at most 8 composed states (and one class of the row each); such a
+  // graph is at most 256 + 2 * 2048 floats, so its residence is always LDS
+  const bool big = d.N > 2048 || d.O > 256;
+  if (!big) den_launch<256, true>(s, d, with_grad);
+  else if (d.lds) den_launch<1024, true>(s, d, with_grad);
+  else den_launch<1024, false>(s, d, with_grad);
+  hipLaunchKernelGGL(ctc_den_loss_kernel, dim3((unsigned)((d.U + 255) / 256)), dim3(256), 0, s, d, num.logz, num.utt_loss,
+                     logz_out);
+}
+
+void ctc_den_grad(hipStream_t s, const CtcDen& d, const float* g, int ldg, float* dlogits, int ldd, int row0, int rows,
+                  Twin tw) {
+  if (rows <= 0 || d.U <= 0) return;
+  hipLaunchKernelGGL(ctc_den_grad_kernel, dim3(rows), dim3(256), (size_t)d.O * sizeof(float), s, d, g, ldg, row0, dlogits, ldd,
+                     tw);
+}
+
+void ctc_den_loss_reduce(hipStream_t s, const CtcDen& d, const float* ctc_utt_loss, int ref_labels, float* scalars,
+                         bool overwrite) {
+  hipLaunchKernelGGL(ctc_mwer_loss_reduce_kernel, dim3(1), dim3(256), 0, s, d.utt_loss,
+                     d.ctc_weight > 0.f ? ctc_utt_loss : (const float*)nullptr, d.U, d.ctc_weight, (float)ref_labels, scalars,
                      overwrite ? 1 : 0);
 }
 

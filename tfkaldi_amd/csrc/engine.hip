@@ -67,7 +67,8 @@ struct LayerLayout {
 enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
   KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
-  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_CTC_MWER_SWEEP, KF_CTC_MWER_WEIGHTS, KF_CTC_MWER_GRAD, KF_COUNT
+  KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_CTC_MWER_SWEEP, KF_CTC_MWER_WEIGHTS, KF_CTC_MWER_GRAD,
+  KF_CTC_DEN_SWEEP, KF_CTC_DEN_GRAD, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
@@ -76,7 +77,8 @@ const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)
                                      "misc",                    "ctc_best_path",    "edit_distance",
                                      "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm",
                                      "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score",
-                                     "ctc_mwer_sweep",          "ctc_mwer_weights", "ctc_mwer_grad"};
+                                     "ctc_mwer_sweep",          "ctc_mwer_weights", "ctc_mwer_grad",
+                                     "ctc_den_sweep",           "ctc_den_grad"};
 
 struct ProfRec {
   int family;
@@ -236,6 +238,19 @@ struct tfk_engine {
   // its tables travel through ctc_pair / h_pair
   unsigned char* ctc_mw = nullptr;
   size_t ctc_cap_mw = 0;
+  // the denominator graph of tfk_ctc_den_set (MMI training; a model of its own beside ctc_lm / ctc_graph_next): the compiled
+  // tables on the host and on the device (nullptr: none), the sweeps' scratch [lattices | MMI losses U], and G(reference)
+  // [U] doubles with its pinned staging (guarded by its own event)
+  CtcDenGraph* den = nullptr;
+  int32_t* den_tab = nullptr;
+  float* den_logw = nullptr;
+  unsigned char* ctc_dn = nullptr;
+  size_t ctc_cap_dn = 0;
+  double* den_gy = nullptr;
+  size_t den_cap_gy = 0;
+  double* h_den_gy = nullptr;
+  size_t h_den_gy_cap = 0;
+  hipEvent_t den_staged = nullptr;
 
   // mixed precision (cfg.compute_dtype == TFK_DTYPE_BF16): every fp32 buffer that is a GEMM operand has a bf16
   // twin written by its producer; master parameters, statistics, gradients and the optimiser stay fp32
@@ -1491,6 +1506,10 @@ struct CtcSpec {  // CTC loss instead of the frame-level cross-entropy
   const int32_t* labels;     // concatenated label sequences
   const int32_t* label_len;  // [U]
   const MwerSpec* mwer = nullptr;  // the MWER criterion: labels / label_len are the references
+  const struct MmiSpec* mmi = nullptr;  // the MMI criterion against the engine's denominator graph
+};
+struct MmiSpec {
+  float lm_scale, ctc_weight;
 };
 template <class Tp>
 int grow(tfk_engine* e, Tp** p, size_t* cap, size_t need) {
@@ -1723,6 +1742,106 @@ int ctc_mwer_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   return 0;
 }
 
+// Validate an MMI batch on the host before the pass starts (a refused call leaves the accumulators and the engine as they were)
+int mmi_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const int32_t* labels, const int32_t* label_len,
+              const MmiSpec& mm) {
+  if (!e->den) return fail(-1, "CTC MMI: no denominator graph is set (tfk_ctc_den_set)");
+  if (!(mm.lm_scale >= 0.f) || !std::isfinite(mm.lm_scale))
+    return fail(-1, "CTC MMI: lm_scale %g is negative or not finite", (double)mm.lm_scale);
+  if (!(mm.ctc_weight >= 0.f) || !std::isfinite(mm.ctc_weight))
+    return fail(-1, "CTC MMI: ctc_weight %g is negative or not finite", (double)mm.ctc_weight);
+  if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC MMI: utt_len / label_len is NULL or no utterances");
+  int64_t frames = 0, total = 0;
+  for (int u = 0; u < U; ++u) {
+    if (utt_len[u] < 0) return fail(-1, "CTC MMI: utterance %d has a negative length", u);
+    if (label_len[u] < 0) return fail(-1, "CTC MMI: utterance %d has a negative reference length", u);
+    if (label_len[u] > kCtcMaxLabels)
+      return fail(-1, "CTC MMI: utterance %d has a reference of %d labels (limit %d)", u, label_len[u], kCtcMaxLabels);
+    frames += utt_len[u];
+    total += label_len[u];
+  }
+  if (frames != T) return fail(-1, "CTC MMI: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
+  if (total > 0x7fffffff) return fail(-1, "CTC MMI: more than 2^31 - 1 labels in one call");
+  if (total > 0 && !labels) return fail(-1, "CTC MMI: labels is NULL");
+  for (int64_t i = 0; i < total; ++i)
+    if (labels[i] < 0 || labels[i] >= e->O - 1) return fail(-1, "CTC MMI: label %d outside [0, %d)", labels[i], e->O - 1);
+  if (const char* why = ctc_den_limits(e->O, T, U, e->den->N))
+    return fail(-1, "CTC MMI (output_dim %d, T %d, U %d, %d composed states): %s", e->O, T, U, e->den->N, why);
+  return 0;
+}
+
+// Loss + dLogits of one MMI micro-batch (logits already in e->logits; the batch has passed mmi_check).  The numerator is the
+// plain CTC sweep: ctc_loss_grad leaves softmax in e->post and g = softmax - occ_num over the logits; the denominator sweeps
+// read e->post alone, and the gradient kernel turns g into dLogits in place.
+int ctc_mmi_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
+  const MmiSpec& mm = *c.mmi;
+  const CtcDenGraph& g = *e->den;
+  int max_labels = 0;
+  CHK(ctc_stage(e, c, T, true, &max_labels));
+  const int sext = ctc_state_stride(max_labels);
+  CHK(grow(e, &e->ctc_utt_loss, &e->ctc_cap_loss, (size_t)c.U));
+  CHK(grow(e, &e->ctc_lp, &e->ctc_cap_lp, (size_t)T * sext));
+  CHK(grow(e, &e->ctc_ab, &e->ctc_cap_ab, (size_t)T * sext));
+  CHK(grow(e, &e->ctc_lse, &e->ctc_cap_rows, (size_t)T));
+  CHK(grow(e, &e->ctc_off, &e->ctc_cap_offrows, (size_t)T));
+  CHK(grow(e, &e->ctc_logz, &e->ctc_cap_logz, (size_t)c.U));
+  if (train) {
+    CHK(grow(e, &e->ctc_bb, &e->ctc_cap_bb, (size_t)T * sext));
+    CHK(grow(e, &e->ctc_offb, &e->ctc_cap_offb, (size_t)T));
+  }
+  CtcBatch b;
+  b.logits = e->logits; b.ld = e->ldO; b.post = e->post; b.lse = e->ctc_lse;
+  b.seg = e->ctc_seg; b.labels = e->ctc_lab; b.lab_off = e->ctc_lab_off;
+  b.U = c.U; b.T = T; b.O = e->O; b.sext = sext;
+  b.lp = e->ctc_lp; b.ab = e->ctc_ab; b.bb = e->ctc_bb; b.utt_loss = e->ctc_utt_loss;
+  b.off = e->ctc_off; b.offb = e->ctc_offb; b.logz = e->ctc_logz;
+  CtcDen d = {};
+  d.tab = e->den_tab; d.logw = e->den_logw;
+  d.O = g.O; d.S = g.S; d.A = g.A; d.K = g.K; d.N = g.N; d.start = g.start;
+  d.post = e->post; d.ld = e->ldO; d.T = T; d.U = c.U; d.seg = e->ctc_seg;
+  d.lm_scale = mm.lm_scale; d.ctc_weight = mm.ctc_weight;
+  const size_t lattice = (ctc_den_scratch_bytes(d, train != 0) + 15) & ~(size_t)15;
+  CHK(grow(e, &e->ctc_dn, &e->ctc_cap_dn, lattice + (size_t)c.U * sizeof(float)));
+  CHK(grow(e, &e->den_gy, &e->den_cap_gy, (size_t)c.U));
+  ctc_den_carve(e->ctc_dn, &d, train != 0);
+  d.utt_loss = reinterpret_cast<float*>(e->ctc_dn + lattice);
+  d.gy = e->den_gy;
+  // G(reference): a walk of the graph on the host, in double
+  if (!e->den_staged) HIPCHK(hipEventCreateWithFlags(&e->den_staged, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->den_staged));
+  CHK(grow_pinned(e, &e->h_den_gy, &e->h_den_gy_cap, (size_t)c.U, /*slack=*/true, /*sync=*/false));
+  int total = 0;
+  for (int u = 0; u < c.U; ++u) {
+    e->h_den_gy[u] = ctc_den_walk(g, c.labels + total, c.label_len[u]);
+    total += c.label_len[u];
+  }
+  HIPCHK(hipMemcpyAsync(e->den_gy, e->h_den_gy, (size_t)c.U * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->den_staged, e->stream));
+  const double cells = (double)T * d.stride;
+  {
+    ProfScope ps(e, KF_SOFTMAX_XENT, 0, 8.0 * T * e->O + 16.0 * T * sext);
+    ctc_loss_grad(e->stream, b, e->logits, train, Twin());
+  }
+  {
+    ProfScope ps(e, KF_CTC_DEN_SWEEP, 0, 4.0 * T * e->O + 4.0 * cells * (train ? 2.0 : 1.0));
+    ctc_den_sweep(e->stream, d, b, train != 0);
+  }
+  if (train) {
+    ProfScope ps(e, KF_CTC_DEN_GRAD, 0, 8.0 * cells + 12.0 * T * e->O);
+    Twin tw;
+    if (e->bf16) { tw.p = e->logb; tw.ld = e->ldOb; tw.x3 = e->x3; }
+    ctc_den_grad(e->stream, d, e->logits, e->ldO, e->logits, e->ldO, 0, T, tw);
+  }
+  {
+    ProfScope ps(e, KF_LOSS_REDUCE, 0, 8.0 * c.U);
+    if (!train) CHK(stash_scalars(e));
+    ctc_den_loss_reduce(e->stream, d, e->ctc_utt_loss, total, e->p_scalars(), e->scalars_fresh);
+    e->scalars_fresh = false;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 struct RawSpec {  // non-null utt_len selects the device-side splice
   const int32_t* utt_len;
   int U, context;
@@ -1885,7 +2004,7 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
   const int nfw = (train && e->cfg.layerwise_init && e->cfg.batch_norm) ? e->L : p.nact;
   CHK(forward(e, p.Xd, p.ld, T, train, p.nact, nfw, p.call, st));
   if (ctc) {
-    CHK(ctc->mwer ? ctc_mwer_loss(e, *ctc, T, train) : ctc_loss(e, *ctc, T, train));
+    CHK(ctc->mwer ? ctc_mwer_loss(e, *ctc, T, train) : ctc->mmi ? ctc_mmi_loss(e, *ctc, T, train) : ctc_loss(e, *ctc, T, train));
   } else {
     {
       ProfScope ps(e, KF_SOFTMAX_XENT, 0, (train ? 8.0 : 4.0) * T * e->O);
@@ -2111,8 +2230,12 @@ int tfk_destroy(tfk_engine* e) {
   for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
                   (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
-                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw, (void*)e->ctc_graph_next})
+                  (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw, (void*)e->ctc_graph_next,
+                  (void*)e->den_tab, (void*)e->den_logw, (void*)e->ctc_dn, (void*)e->den_gy})
     if (p) hipFree(p);
+  delete e->den;
+  if (e->h_den_gy) hipHostFree(e->h_den_gy);
+  if (e->den_staged) hipEventDestroy(e->den_staged);
   if (e->h_pair) hipHostFree(e->h_pair);
   if (e->ctc_pair_staged) hipEventDestroy(e->ctc_pair_staged);
   if (e->h_dec) hipHostFree(e->h_dec);
@@ -2394,6 +2517,216 @@ int tfk_eval_accumulate_ctc_mwer_raw(tfk_engine* e, const float* raw, int64_t ld
   CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_mwer_entry(e, raw, ldraw, T, utt_len, U, ref_labels, ref_len, hyp_count, hyp_labels, hyp_len, ctc_weight, flags, 0,
                         &r);
+}
+
+// MMI against the denominator graph of tfk_ctc_den_set: everything is validated on the host before the pass starts, so a
+// refused call leaves the engine as it was.
+static int ctc_mmi_entry(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                         const int32_t* labels, const int32_t* label_len, float lm_scale, float ctc_weight, int flags, int train,
+                         const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (T <= 0) return fail(-1, "empty micro-batch (T = %d)", T);
+  const MmiSpec mm = {lm_scale, ctc_weight};
+  CHK(mmi_check(e, utt_len, U, T, labels, label_len, mm));
+  CtcSpec c = {utt_len, U, labels, label_len};
+  c.mmi = &mm;
+  return train_or_eval(e, X, ldx, nullptr, T, train ? flags : flags & ~TFK_LAST_MICROBATCH, train, raw, &c);
+}
+int tfk_accumulate_ctc_mmi(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                           const int32_t* labels, const int32_t* label_len, float lm_scale, float ctc_weight, int flags) {
+  return ctc_mmi_entry(e, X, ldx, T, utt_len, U, labels, label_len, lm_scale, ctc_weight, flags, 1, nullptr);
+}
+int tfk_eval_accumulate_ctc_mmi(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                const int32_t* labels, const int32_t* label_len, float lm_scale, float ctc_weight, int flags) {
+  return ctc_mmi_entry(e, X, ldx, T, utt_len, U, labels, label_len, lm_scale, ctc_weight, flags, 0, nullptr);
+}
+int tfk_accumulate_ctc_mmi_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                               int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                               float lm_scale, float ctc_weight, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_mmi_entry(e, raw, ldraw, T, utt_len, U, labels, label_len, lm_scale, ctc_weight, flags, 1, &r);
+}
+int tfk_eval_accumulate_ctc_mmi_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                    int32_t U, int32_t context_width, const float* cmvn, const int32_t* labels,
+                                    const int32_t* label_len, float lm_scale, float ctc_weight, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_mmi_entry(e, raw, ldraw, T, utt_len, U, labels, label_len, lm_scale, ctc_weight, flags, 0, &r);
+}
+
+// Validation shared by tfk_ctc_den_set and tfk_ctc_mmi_logits (host tables): the rules of tfk_ctc_graph_set, then the limits of
+// the composed lattice -- all before anything is allocated.
+static int den_tables_check(const char* who, const float* weight, const int32_t* next, int O, int64_t num_states, int start) {
+  if (num_states < 1) return fail(-1, "%s: num_states %lld < 1", who, (long long)num_states);
+  if (const char* why = ctc_den_graph_limits(O, num_states, 0))
+    return fail(-1, "%s (%lld states over %d outputs): %s", who, (long long)num_states, O, why);
+  if (start < 0 || start >= num_states) return fail(-1, "%s: start %d outside [0, %lld)", who, start, (long long)num_states);
+  const size_t n = (size_t)num_states * (size_t)O;
+  int64_t arcs = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const float w = weight[i];
+    if (std::isnan(w) || w == INFINITY) return fail(-1, "%s: entry %zu of weight is NaN or +inf", who, i);
+    if (i % O != (size_t)O - 1 && w > -INFINITY) {
+      if (next[i] < 0 || next[i] >= num_states)
+        return fail(-1, "%s: entry %zu of next is %d, outside [0, %lld)", who, i, next[i], (long long)num_states);
+      ++arcs;
+    }
+  }
+  if (const char* why = ctc_den_graph_limits(O, num_states, arcs))
+    return fail(-1, "%s (%lld states + %lld arcs = %lld composed states, limit %d): %s", who, (long long)num_states,
+                (long long)arcs, (long long)(num_states + arcs), kCtcDenMaxStates, why);
+  return 0;
+}
+// The denominator graph: a model of its own beside the decoder's.  Everything is validated, compiled and uploaded before the
+// engine's model is touched: any failure leaves the old one in force.
+int tfk_ctc_den_set(tfk_engine* e, const float* weight, const int32_t* next, int32_t num_states, int32_t start) {
+  if (!e) return fail(-1, "engine is NULL");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  CtcDenGraph* g = nullptr;
+  int32_t* d_tab = nullptr;
+  float* d_w = nullptr;
+  if (weight) {
+    if (!next) return fail(-1, "tfk_ctc_den_set: next is NULL");
+    CHK(den_tables_check("tfk_ctc_den_set", weight, next, e->O, num_states, start));
+    g = new CtcDenGraph();
+    ctc_den_compile(weight, next, num_states, e->O, start, g);
+    hipError_t got = hipMalloc((void**)&d_tab, g->tab.size() * sizeof(int32_t));
+    if (got == hipSuccess) got = hipMalloc((void**)&d_w, g->logw.size() * sizeof(float));
+    if (got == hipSuccess) got = hipMemcpy(d_tab, g->tab.data(), g->tab.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (got == hipSuccess) got = hipMemcpy(d_w, g->logw.data(), g->logw.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (got == hipSuccess) got = hipStreamSynchronize(e->stream);  // a sweep may still be reading the model this one replaces
+    if (got != hipSuccess) {
+      if (d_tab) (void)hipFree(d_tab);
+      if (d_w) (void)hipFree(d_w);
+      delete g;
+      HIPCHK(got);
+    }
+  } else {
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  if (e->den_tab) (void)hipFree(e->den_tab);
+  if (e->den_logw) (void)hipFree(e->den_logw);
+  delete e->den;
+  e->den = g;
+  e->den_tab = d_tab;
+  e->den_logw = d_w;
+  return 0;
+}
+
+int tfk_ctc_den_info(tfk_engine* e, int32_t* num_states, int32_t* num_arcs, int32_t* num_groups, int32_t* residence) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (!e->den) return fail(-1, "tfk_ctc_den_info: no denominator graph is set (tfk_ctc_den_set)");
+  const CtcDenGraph& g = *e->den;
+  if (num_states) *num_states = g.S;
+  if (num_arcs) *num_arcs = g.A;
+  if (num_groups) *num_groups = g.K;
+  if (residence) *residence = ctc_den_residence(g.O, g.N, g.S, g.A, g.K);
+  return 0;
+}
+
+int tfk_ctc_mmi_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                       const int32_t* labels, const int32_t* lab_off, const float* weight_dev, const int32_t* next_dev,
+                       int32_t num_states, int32_t start, float lm_scale, float ctc_weight, float* utt_loss, float* logz,
+                       float* dlogits, int64_t ldd) {
+  hipStream_t st = (hipStream_t)stream;
+  if (U < 0) return fail(-1, "U = %d < 0", U);
+  if (!(lm_scale >= 0.f) || !std::isfinite(lm_scale)) return fail(-1, "CTC MMI: lm_scale %g is negative or not finite", (double)lm_scale);
+  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight))
+    return fail(-1, "CTC MMI: ctc_weight %g is negative or not finite", (double)ctc_weight);
+  if (!weight_dev || !next_dev) return fail(-1, "CTC MMI: no denominator graph (weight / next is NULL)");
+  if (num_states < 1) return fail(-1, "CTC MMI: num_states %d < 1", num_states);
+  if (const char* why = ctc_den_graph_limits(O, num_states, 0))
+    return fail(-1, "CTC MMI (%d states over %d outputs): %s", num_states, O, why);
+  if (U == 0) return 0;
+  if (T <= 0) return fail(-1, "CTC MMI: empty batch (T = %d)", T);
+  if (!seg || !lab_off || !utt_loss || !logz || (T > 0 && !logits)) return fail(-1, "logits / seg / lab_off / utt_loss / logz is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
+  // The shapes and the graph live on the device: they come back first (one synchronisation)
+  const size_t ng = (size_t)num_states * (size_t)O;
+  std::vector<int32_t> h_seg((size_t)U + 1), h_off((size_t)U + 1), h_next(ng);
+  std::vector<float> h_w(ng);
+  HIPCHK(hipMemcpyAsync(h_seg.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_off.data(), lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_w.data(), weight_dev, ng * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_next.data(), next_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  int max_labels = 0;
+  for (int u = 0; u < U; ++u) {
+    if (h_seg[u + 1] < h_seg[u]) return fail(-1, "CTC MMI: utterance %d has a negative length", u);
+    if (h_off[u + 1] < h_off[u]) return fail(-1, "CTC MMI: utterance %d has a negative reference length", u);
+    max_labels = std::max(max_labels, h_off[u + 1] - h_off[u]);
+  }
+  if (h_seg[0] != 0 || h_seg[U] != T) return fail(-1, "CTC MMI: seg = [%d, %d] is not [0, T = %d]", h_seg[0], h_seg[U], T);
+  if (h_off[0] != 0) return fail(-1, "CTC MMI: lab_off[0] = %d is not 0", h_off[0]);
+  if (max_labels > kCtcMaxLabels) return fail(-1, "CTC MMI: %d labels in one utterance (limit %d)", max_labels, kCtcMaxLabels);
+  const int total = h_off[U];
+  if (total > 0 && !labels) return fail(-1, "CTC MMI: labels is NULL");
+  std::vector<int32_t> h_lab((size_t)(total > 0 ? total : 1));
+  if (total > 0) {
+    HIPCHK(hipMemcpyAsync(h_lab.data(), labels, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < total; ++i)
+    if (h_lab[i] < 0 || h_lab[i] >= O - 1) return fail(-1, "CTC MMI: label %d outside [0, %d)", h_lab[i], O - 1);
+  CHK(den_tables_check("CTC MMI", h_w.data(), h_next.data(), O, num_states, start));
+  CtcDenGraph g;
+  ctc_den_compile(h_w.data(), h_next.data(), num_states, O, start, &g);
+  if (const char* why = ctc_den_limits(O, T, U, g.N))
+    return fail(-1, "CTC MMI (O %d, T %d, U %d, %d composed states): %s", O, T, U, g.N, why);
+  std::vector<double> gy((size_t)U);
+  for (int u = 0; u < U; ++u) gy[u] = ctc_den_walk(g, h_lab.data() + h_off[u], h_off[u + 1] - h_off[u]);
+  const bool train = dlogits != nullptr;
+  const int sext = ctc_state_stride(max_labels);
+  CtcDen d = {};
+  d.O = g.O; d.S = g.S; d.A = g.A; d.K = g.K; d.N = g.N; d.start = g.start;
+  d.ld = (int)ld; d.T = T; d.U = U; d.seg = seg; d.lm_scale = lm_scale; d.ctc_weight = ctc_weight;
+  // the call's own scratch, released in stream order:
+  // [G(y) U doubles | off T, offb T, logz U doubles | post T ld, g T ld, lp / ab / bb T sext, lse T, CTC losses U floats |
+  //  tab | logw | the denominator's lattices]
+  const size_t t = (size_t)(T > 0 ? T : 0), u = (size_t)U;
+  const size_t dbl = (2 * u + 2 * t) * sizeof(double);
+  const size_t flt = (2 * t * (size_t)ld + 3 * t * (size_t)sext + t + u + g.logw.size()) * sizeof(float);
+  const size_t ints = (g.tab.size() * sizeof(int32_t) + 15) & ~(size_t)15;
+  const size_t head = (dbl + flt + ints + 15) & ~(size_t)15;
+  unsigned char* scratch = nullptr;
+  HIPCHK(hipMallocAsync((void**)&scratch, head + ctc_den_scratch_bytes(d, train), st));
+  double* dp = reinterpret_cast<double*>(scratch);
+  double* d_gy = dp;
+  CtcBatch b;
+  b.logits = logits; b.ld = (int)ld; b.seg = seg; b.labels = labels; b.lab_off = lab_off;
+  b.U = U; b.T = T; b.O = O; b.sext = sext;
+  b.off = dp + u; b.offb = b.off + t; b.logz = b.offb + t;
+  float* fp = reinterpret_cast<float*>(b.logz + u);
+  b.post = fp;                  fp += t * (size_t)ld;
+  float* gbuf = fp;             fp += t * (size_t)ld;
+  b.lp = fp;                    fp += t * (size_t)sext;
+  b.ab = fp;                    fp += t * (size_t)sext;
+  b.bb = fp;                    fp += t * (size_t)sext;
+  b.lse = fp;                   fp += t;
+  b.utt_loss = fp;              fp += u;
+  float* d_logw = fp;           fp += g.logw.size();
+  int32_t* d_tab = reinterpret_cast<int32_t*>(fp);
+  hipError_t copied = hipMemcpyAsync(d_gy, gy.data(), u * sizeof(double), hipMemcpyHostToDevice, st);
+  if (copied == hipSuccess)
+    copied = hipMemcpyAsync(d_logw, g.logw.data(), g.logw.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (copied == hipSuccess)
+    copied = hipMemcpyAsync(d_tab, g.tab.data(), g.tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+  if (copied == hipSuccess) copied = hipStreamSynchronize(st);  // (the tables leave pageable host memory)
+  hipError_t launched = copied;
+  if (copied == hipSuccess) {
+    d.tab = d_tab; d.logw = d_logw; d.post = b.post; d.gy = d_gy; d.utt_loss = utt_loss;
+    ctc_den_carve(scratch + head, &d, train);
+    ctc_loss_grad(st, b, gbuf, train ? 1 : 0, Twin());
+    ctc_den_sweep(st, d, b, train, logz);
+    if (train) ctc_den_grad(st, d, gbuf, (int)ld, dlogits, (int)ldd, 0, T, Twin());
+    launched = hipGetLastError();
+  }
+  const hipError_t freed = hipFreeAsync(scratch, st);  // also when a copy or the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
 }
 
 // The optimiser step in three parts, so that a data-parallel host can run Adam on each span of parameters as soon

@@ -142,6 +142,28 @@ class CtcMwerMicroBatch(CtcMicroBatch):
         self.add_reference, self.ctc_weight = bool(add_reference), float(ctc_weight)
 
 
+class CtcMmiMicroBatch(CtcMicroBatch):
+    """A CTC micro-batch trained on MMI against a denominator graph (tfk_accumulate_ctc_mmi): -(log p_ctc(reference) +
+    lm_scale G(reference)) + log Z plus ctc_weight x the CTC loss.  graph: the GraphLM that is the denominator; the rank
+    that trains the micro-batch sets it on its engine (Engine.ctc_set_den uploads only when it changes)."""
+
+    def __init__(self, X, utt_lens, labels, label_lens, graph, context_width=None, cmvn=None, lm_scale=1.0, ctc_weight=0.0):
+        CtcMicroBatch.__init__(self, X, utt_lens, labels, label_lens, context_width, cmvn)
+        if graph is None:
+            raise ValueError("a CtcMmiMicroBatch needs its denominator graph")
+        self.graph, self.lm_scale, self.ctc_weight = graph, float(lm_scale), float(ctc_weight)
+
+
+def _accumulate_mmi(engine, mb, last, train):
+    engine.ctc_set_den(mb.graph)
+    if mb.context_width is not None:
+        engine.accumulate_ctc_mmi_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, lm_scale=mb.lm_scale,
+                                      ctc_weight=mb.ctc_weight, last=last, cmvn=mb.cmvn, train=train)
+    else:
+        engine.accumulate_ctc_mmi(mb.X, mb.utt_lens, mb.labels, mb.label_lens, lm_scale=mb.lm_scale,
+                                  ctc_weight=mb.ctc_weight, last=last, train=train)
+
+
 def _mwer_tables(engine, mb):
     """the pair tables of an MWER micro-batch: its own, or the N best of a search on `engine` (evaluation passes that leave
     the sums of an open step alone); padding paths -- beam score -inf -- are dropped, as _label_errors drops them"""
@@ -181,6 +203,8 @@ def _accumulate_mwer(engine, mb, last, train):
 def _accumulate(engine, mb, last):
     if isinstance(mb, CtcMwerMicroBatch):
         _accumulate_mwer(engine, mb, last, True)
+    elif isinstance(mb, CtcMmiMicroBatch):
+        _accumulate_mmi(engine, mb, last, True)
     elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, last=last,
@@ -198,6 +222,8 @@ def _accumulate(engine, mb, last):
 def _eval_accumulate(engine, mb):
     if isinstance(mb, CtcMwerMicroBatch):
         _accumulate_mwer(engine, mb, False, False)
+    elif isinstance(mb, CtcMmiMicroBatch):
+        _accumulate_mmi(engine, mb, False, False)
     elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, cmvn=mb.cmvn,

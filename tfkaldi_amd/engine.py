@@ -45,6 +45,7 @@ class Engine(object):
         self.batch_norm = bool(cfg.batch_norm)
         self._h = c_void_p()
         self._lm_table = None  # the NgramLM / GraphLM table tfk_ctc_lm_set / tfk_ctc_graph_set holds (ctc_set_lm)
+        self._den_table = None  # the GraphLM table tfk_ctc_den_set holds (ctc_set_den)
         self._state = None
         self._stream = None
         self._cb = None
@@ -680,6 +681,70 @@ class Engine(object):
                  label_lens.ctypes.data_as(c_void_p), hyp_counts.ctypes.data_as(c_void_p),
                  hyp_labels.ctypes.data_as(c_void_p), hyp_lens.ctypes.data_as(c_void_p), ctc_weight,
                  _lib.LAST_MICROBATCH if (last and train) else 0))
+
+    # ---- MMI against a denominator graph (CTC-CRF): the exact sum over every label sequence a grammar accepts ----
+    def ctc_set_den(self, graph):
+        """Make `graph` (a neuralNetworks/ctc_lm.GraphLM, or None to drop it) the engine's DENOMINATOR graph
+        (tfk_ctc_den_set): a model of its own beside the decoder's (ctc_set_lm); its final weights are always read, its
+        weight / label_bonus / end_of_sequence settings are not (the scale travels with accumulate_ctc_mmi).  Nothing is
+        compiled or uploaded when the same table object is already set.  A denominator from transcripts is
+        GraphLM.from_ngram(NgramLM.from_label_sequences(...)); graph.composed_states is the N the device limits to 65536, and
+        ctc_den_info() says where the sweeps of the graph in force keep their data."""
+        if graph is None:
+            if self._den_table is not None:
+                check(self.lib.tfk_ctc_den_set(self._h, c_void_p(None), c_void_p(None), 0, 0))
+                self._den_table = None
+            return
+        graph.check(self.O)
+        if self._den_table is graph.table:
+            return
+        # (a refused call leaves the old model in force on the device: _den_table keeps saying so)
+        check(self.lib.tfk_ctc_den_set(self._h, _ptr(graph.table), _ptr(graph.next), graph.num_states, graph.start))
+        self._den_table = graph.table
+
+    def ctc_den_info(self):
+        """what the compile of the denominator graph in force found (tfk_ctc_den_info): a dict of num_states, num_arcs,
+        num_groups, composed_states and residence -- "global", "lds" (the vector and the sums in LDS) or "lds+tables"""
+        from ctypes import c_int32
+        S, A, K, where = c_int32(), c_int32(), c_int32(), c_int32()
+        check(self.lib.tfk_ctc_den_info(self._h, byref(S), byref(A), byref(K), byref(where)))
+        return {"num_states": S.value, "num_arcs": A.value, "num_groups": K.value, "composed_states": S.value + A.value,
+                "residence": ("global", "lds", "lds+tables")[where.value]}
+
+    @staticmethod
+    def _mmi_args(lm_scale, ctc_weight):
+        lm_scale, ctc_weight = float(lm_scale), float(ctc_weight)
+        if not (np.isfinite(lm_scale) and lm_scale >= 0.0):
+            raise ValueError("lm_scale %r must be finite and >= 0" % (lm_scale,))
+        if not (np.isfinite(ctc_weight) and ctc_weight >= 0.0):
+            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
+        return lm_scale, ctc_weight
+
+    def accumulate_ctc_mmi(self, X, utt_lens, labels, label_lens, lm_scale=1.0, ctc_weight=0.0, last=False, train=True):
+        """One micro-batch of the MMI criterion (tfk_accumulate_ctc_mmi; the contract is stated in include/tfkaldi_hip.h):
+        -(log p_ctc(reference) + lm_scale G(reference)) + log Z, Z the exact sum over every label sequence the denominator
+        graph of ctc_set_den accepts, plus ctc_weight x the CTC loss.  Arguments as accumulate_ctc.  train=False:
+        evaluation-mode forward, loss only."""
+        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
+        lm_scale, ctc_weight = self._mmi_args(lm_scale, ctc_weight)
+        fn = self.lib.tfk_accumulate_ctc_mmi if train else self.lib.tfk_eval_accumulate_ctc_mmi
+        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p), lm_scale, ctc_weight,
+                 _lib.LAST_MICROBATCH if (last and train) else 0))
+
+    def eval_accumulate_ctc_mmi(self, X, utt_lens, labels, label_lens, lm_scale=1.0, ctc_weight=0.0):
+        self.accumulate_ctc_mmi(X, utt_lens, labels, label_lens, lm_scale, ctc_weight, train=False)
+
+    def accumulate_ctc_mmi_raw(self, raw, utt_lens, context_width, labels, label_lens, lm_scale=1.0, ctc_weight=0.0,
+                               last=False, cmvn=None, train=True):
+        """accumulate_ctc_mmi from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
+        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
+        lm_scale, ctc_weight = self._mmi_args(lm_scale, ctc_weight)
+        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
+        fn = self.lib.tfk_accumulate_ctc_mmi_raw if train else self.lib.tfk_eval_accumulate_ctc_mmi_raw
+        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
+                 label_lens.ctypes.data_as(c_void_p), lm_scale, ctc_weight, _lib.LAST_MICROBATCH if (last and train) else 0))
 
     # ---- the optimiser step in parts (data parallel: Adam per reduced span, see dataparallel.BucketReducer) ----
     def apply_begin(self):

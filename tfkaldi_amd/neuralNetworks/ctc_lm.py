@@ -146,6 +146,17 @@ class GraphLM(object):
     def num_labels(self):
         return self.num_classes - 1
 
+    @property
+    def num_arcs(self):
+        """A: the arcs that exist (the finite entries of the label columns)"""
+        return int(np.count_nonzero(self.table[:, :-1] > -np.inf))
+
+    @property
+    def composed_states(self):
+        """N = S + A: the states of the graph composed with the CTC topology, one per graph state and one per arc -- what a
+        DENOMINATOR graph costs per frame (tfk_ctc_den_set refuses N > 65536)"""
+        return self.num_states + self.num_arcs
+
     def check(self, num_classes):
         """raise unless the graph fits a model of num_classes outputs (labels + blank)"""
         if self.num_classes != int(num_classes):

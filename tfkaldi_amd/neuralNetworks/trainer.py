@@ -450,3 +450,46 @@ class CTCTrainer(Trainer):
         microbatches = self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
                                                add_reference, hyps)
         return self.dp.eval_step(self.engine, microbatches)
+
+    # ---- MMI against a denominator graph (CTC-CRF): the exact sum over every label sequence a grammar accepts ----
+    def _mmi_microbatches(self, inputs, targets, graph, lm_scale, ctc_weight):
+        from ..dataparallel import CtcMmiMicroBatch
+        if graph is None or getattr(graph, "next", None) is None:
+            raise ValueError("MMI needs a denominator graph: a ctc_lm.GraphLM")
+        for name, v in (("lm_scale", lm_scale), ("ctc_weight", ctc_weight)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError("%s %r must be finite and >= 0" % (name, v))
+        for u, ref in enumerate(targets):
+            ref = np.asarray(ref).reshape(-1)
+            s, at = graph._walk(ref)
+            if s is None:
+                raise ValueError("utterance %d: the denominator graph has no arc for label %d of its reference (position %d)"
+                                 % (u, int(ref[at]), at))
+            if not graph.table[s, -1] > -np.inf:
+                raise ValueError("utterance %d: its reference ends in state %d of the denominator graph, which is not final"
+                                 % (u, s))
+        return [CtcMmiMicroBatch(mb.X, mb.utt_lens, mb.labels, mb.label_lens, graph, context_width=mb.context_width,
+                                 cmvn=mb.cmvn, lm_scale=lm_scale, ctc_weight=ctc_weight)
+                for mb in self._microbatches(inputs, targets)]
+
+    def update_mmi(self, inputs, targets, graph, lm_scale=1.0, ctc_weight=0.0):
+        """One optimiser step on MAXIMUM MUTUAL INFORMATION against the denominator graph (tfk_accumulate_ctc_mmi; CTC-CRF):
+        per utterance -(log p_ctc(reference) + lm_scale G(reference)) + log Z, with Z the total likelihood of EVERY label
+        sequence `graph` (a ctc_lm.GraphLM; its final weights are always read) accepts, summed exactly on the device -- no
+        decode, no N-best list -- plus ctc_weight x the CTC loss.  The graph is set on the engine when it changes.  A
+        denominator from transcripts is GraphLM.from_ngram(NgramLM.from_label_sequences(...)); a lexicon is
+        GraphLM.from_lexicon(...).  A reference the graph rejects raises a ValueError that names the utterance before the
+        step starts.  Returns the step's loss per reference label, before the update."""
+        microbatches = self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight)
+        if not microbatches:
+            raise ValueError("CTCTrainer.update_mmi: the batch holds no frames (no micro-batch could be built from %d "
+                             "utterance(s))" % len(inputs))
+        loss = self.dp.train_step(self.engine, microbatches)
+        self._summarise(loss)
+        return loss
+
+    def evaluate_mmi(self, inputs, targets, graph, lm_scale=1.0, ctc_weight=0.0):
+        """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
+        if inputs is None or targets is None:
+            return None
+        return self.dp.eval_step(self.engine, self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight))

@@ -31,6 +31,11 @@ outputs, 50 words, a trie of 182 states) at the tests' size and at 16 utterances
 with label_topk = 8 -- the search with the lexicon graph (tfk_ctc_beam_graph_logits) beside the n-gram search (order 2 over
 the references) and the acoustic search at the same shapes: HIP-event time per call (median of 20, with the spread), that
 time per frame step, the graph search's time over the n-gram search's, and the label errors against the references.
+`--mmi` runs the MMI leg alone: one step on MMI against a denominator graph (tfk_accumulate_ctc_mmi, lm_scale 1, ctc_weight
+0.1) beside one plain CTC step on the same build and batch, for three denominators -- the order-2 and the order-3 n-gram graph
+of the batch's transcripts and a 50-word lexicon trie with a separator (its references are word sequences) -- the median of
+the timed steps with the spread, the profiler's rows of the numerator (softmax_xent) and of the two new kernels, the sweep's
+time per frame of the 800-frame chain against the composed states N, and the residence (LDS or global) each graph took.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -85,6 +90,11 @@ def main():
         bias[O - 1] = 2.0
         eng.set(_lib.BIASES, eng.L, bias)
         mwer_leg(eng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
+        eng.close()
+        return
+    if "--mmi" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        mmi_leg(eng, rng, X, utt, labels, np.asarray(lab), Tu)
         eng.close()
         return
     if "--topk-only" in sys.argv:
@@ -478,6 +488,66 @@ def mwer_leg(eng, X, utt, labels, lab, case):
               % ((case, N, int(np.sum(counts)), int(max(hn)), loss) + alone + (alone[0] / base[0],) + both + (both[0] / base[0],)
                  + (rows.get("ctc_mwer_sweep", 0.0), rows.get("ctc_mwer_sweep", 0.0) / max(base_rows.get("softmax_xent", 0.0), 1e-9),
                     rows.get("ctc_mwer_weights", 0.0), rows.get("ctc_mwer_grad", 0.0))))
+
+
+def mmi_leg(eng, rng, X, utt, labels, lab, Tu):
+    """the learning rate is set to zero first, so that every step sees the same model"""
+    from tfkaldi_amd.neuralNetworks.ctc_lm import GraphLM, NgramLM
+    for _ in range(40):
+        eng.halve_learning_rate()
+    O, U, K = eng.O, len(utt), 5
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    words, seen = [], set()
+    while len(words) < 50:  # 50 distinct words of 2 .. 6 characters; label O - 2 is the separator
+        w = tuple(rng.integers(0, O - 2, int(rng.integers(2, 7))).tolist())
+        if w not in seen:
+            seen.add(w)
+            words.append(np.array(w, np.int32))
+    lex_refs = []
+    for _ in range(U):
+        seq = []
+        while len(seq) < 95:
+            seq += words[int(rng.integers(0, 50))].tolist() + [O - 2]
+        lex_refs.append(np.array(seq[:-1], np.int32))
+    cases = [("order-2 n-gram of the transcripts", GraphLM.from_ngram(NgramLM.from_label_sequences(refs, O - 1, 2)), refs),
+             ("order-3 n-gram of the transcripts", GraphLM.from_ngram(NgramLM.from_label_sequences(refs, O - 1, 3)), refs),
+             ("50-word lexicon trie + separator", GraphLM.from_lexicon(words, O - 1, O - 2, word_logprob=np.full(50, -np.log(50.0))),
+              lex_refs)]
+
+    def ctc_step():
+        eng.accumulate_ctc(X, utt, labels, lab, last=True)
+        return eng.apply()
+    base = _median_ms(ctc_step, K=K)
+    eng.profile_begin()
+    for _ in range(K):
+        ctc_step()
+    base_rows = {s["name"]: s["total_ms"] / K for s in eng.profile_end()}
+    print("  mmi: yardstick, one plain CTC step (tfk_accumulate_ctc + tfk_apply), %d utterances x %d frames, %d outputs: median "
+          "%.3f ms (%.3f .. %.3f), its loss family (softmax, gather, both sweeps, gradient) %.3f ms"
+          % ((U, Tu, O) + base + (base_rows.get("softmax_xent", 0.0),)))
+    for name, graph, rr in cases:
+        lab_g = np.array([r.size for r in rr], np.int32)
+        labels_g = np.concatenate(rr).astype(np.int32)
+        eng.ctc_set_den(graph)
+        info = eng.ctc_den_info()  # (the library's own word on where the sweeps keep their data)
+
+        def step():
+            eng.accumulate_ctc_mmi(X, utt, labels_g, lab_g, lm_scale=1.0, ctc_weight=0.1, last=True)
+            return eng.apply()
+        loss = step()
+        med = _median_ms(step, warm=2, K=K)
+        eng.profile_begin()
+        for _ in range(K):
+            step()
+        rows = {s["name"]: s["total_ms"] / K for s in eng.profile_end()}
+        sweep, grad = rows.get("ctc_den_sweep", 0.0), rows.get("ctc_den_grad", 0.0)
+        print("  mmi %-34s: S %5d, arcs %5d, N %5d composed states, %d groups, residence: %s; loss/label %.4f; one MMI "
+              "step median %.3f ms (%.3f .. %.3f) = %.2f x the CTC step; kernels per step: numerator %.3f ms, ctc_den_sweep "
+              "%.3f ms = %.2f us per frame of the %d-frame chain (%.3f ns per frame and composed state), ctc_den_grad %.3f ms"
+              % ((name, graph.num_states, graph.num_arcs, graph.composed_states, info["num_groups"], info["residence"],
+                  loss) + med + (med[0] / base[0], rows.get("softmax_xent", 0.0), sweep, sweep * 1e3 / Tu, Tu,
+                                        sweep * 1e6 / Tu / graph.composed_states, grad)))
+    eng.ctc_set_den(None)
 
 
 def align_leg(eng, X, utt, labels, lab, case):
