@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 17
+#define TFK_ABI_VERSION 18
 
 typedef struct tfk_engine tfk_engine;
 
@@ -882,9 +882,37 @@ enum { /* debug tensors of the LAST accumulate / eval / posteriors call */
   TFK_DBG_DROPOUT_MASK = 2,/* [T, H] 0/1 keep mask of hidden layer `layer` (regenerated) */
   TFK_DBG_PREACT = 3,      /* [T, H] affine output z of hidden layer `layer` (what batch norm normalises) */
   TFK_DBG_BN_MEAN = 4,     /* row 0 of [T, H]: batch mean of z's columns as the backward pass reads it (training calls) */
-  TFK_DBG_BN_RSTD = 5      /* row 0 of [T, H]: 1 / sqrt(batch variance + eps) */
+  TFK_DBG_BN_RSTD = 5,     /* row 0 of [T, H]: 1 / sqrt(batch variance + eps) */
+  TFK_DBG_DPREACT = 6,     /* [T, H] dz of hidden layer `layer`, the gradient with respect to its affine output, as hidden_backward
+                            * leaves it.  Mixed precision stores dz as its bf16 twin ALONE (rounded from the kernel's registers;
+                            * both contractions that consume dz read the twin), so these are the twin's values, widened.  Kept only
+                            * under tfk_debug_capture; without it the call fails by name. */
+  TFK_DBG_TRAIN_LOGITS = 7 /* [T, O] the logits of a training call, which the loss then overwrites with dLogits in place; under
+                            * tfk_debug_capture only (one more device-to-device copy, behind the forward pass) */
 };
 int tfk_debug_fetch(tfk_engine* e, int what, int layer, float* host, size_t count);
+
+/* ABI 18: the bf16 operand twins as the contractions read them (tests and tools; TFK_DTYPE_BF16 only -- TFK_DTYPE_F32 keeps no
+ * twins, and the three-plane twins of TFK_DTYPE_F32X3 are refused by name).  `host` receives the raw bfloat16 bit patterns,
+ * unpadded (the twins' padding columns are not part of the fetch); `count` = rows x columns.  The call waits for everything the
+ * engine has in flight.
+ *   TFK_TWIN_INPUT    [T, F]  the twin of the input slot the last call read
+ *   TFK_TWIN_HIDDEN   [T, H]  the twin of the output of hidden layer `layer` (evaluated by the last call)
+ *   TFK_TWIN_DLOGITS  [T, O]  the twin of d loss / d logits; after a training call only
+ *   TFK_TWIN_WEIGHTS  [d_in, d_out] the shadow of the weight matrix of layer `layer` (0 .. L).  Refused while the shadow is not
+ *                     current (parameters written from outside, or an optimiser step that does not write it): the next pass
+ *                     rebuilds it.
+ *   TFK_TWIN_DPREACT  [T, H]  the twin of dz of hidden layer `layer`; under tfk_debug_capture only */
+enum { TFK_TWIN_INPUT = 0, TFK_TWIN_HIDDEN = 1, TFK_TWIN_DLOGITS = 2, TFK_TWIN_WEIGHTS = 3, TFK_TWIN_DPREACT = 4 };
+int tfk_debug_fetch_twin(tfk_engine* e, int what, int layer, uint16_t* host, size_t count);
+/* The backward pass keeps dz only in its two ping-pong twin buffers.  on != 0: every later NON-STACKED training pass enqueues
+ * device-to-device copies on the engine stream -- one behind the forward pass (the logits, which the loss overwrites in place:
+ * TFK_DBG_TRAIN_LOGITS) and one right behind each hidden layer's hidden_backward (the bf16 twin of dz, the only form in which
+ * mixed precision stores it: TFK_DBG_DPREACT / TFK_TWIN_DPREACT) -- into buffers allocated with the activations and released by
+ * tfk_destroy or by on == 0.  A stacked pass captures nothing.  TFK_DTYPE_BF16 only: TFK_DTYPE_F32X3 is refused by name (its
+ * fused dual launch never stores du or dz in fp32).  With capture off (the default) a pass enqueues exactly what it did
+ * before ABI 18. */
+int tfk_debug_capture(tfk_engine* e, int on);
 
 /* Stand-alone fp32 GEMM on device pointers (tests / tools): layout 0 NN, 1 NT, 2 TN (gemm_f32.h). */
 int tfk_gemm_f32(void* stream, int layout, const float* A, int lda, const float* B, int ldb, float* C, int ldc,

@@ -342,3 +342,277 @@ def reference_microbatches(num_utt, per_minibatch):
         idx = [i for i in range(k * U, (k + 1) * U) if i < num_utt]
         out.append(idx)
     return out
+
+
+# ---- fp32 reference MODEL of the batch-norm statistics (tests/test_bn_stats_model.py states what it is for) ----
+BN_EPS = float(np.float32(1e-3))  # the fp32 value the kernels add to the variance
+
+
+def stats64(z):
+    """float64 column mean, biased variance and rstd of the fp32 matrix z"""
+    z = np.asarray(z, dtype=np.float64)
+    mean = z.mean(axis=0)
+    var = ((z - mean) ** 2).mean(axis=0)
+    return mean, var, 1.0 / np.sqrt(var + BN_EPS)
+
+
+def _running_sum(x):
+    return np.add.accumulate(x, axis=0, dtype=np.float32)[-1]  # one fp32 accumulator per column, row after row
+
+
+def bn_stats_model(z, chunk_rows):
+    """fp32 (mean, biased variance, rstd) of the columns of z[T, H]: per chunk of chunk_rows rows a sequential two-pass
+    (mean, M2), the chunks merged one after the other (Chan et al.), every operation rounded to float32"""
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    T = z.shape[0]
+    f = np.float32
+    n = f(0)
+    mean = np.zeros(z.shape[1], dtype=f)
+    m2 = np.zeros(z.shape[1], dtype=f)
+    for r0 in range(0, T, chunk_rows):
+        part = z[r0:r0 + chunk_rows]
+        nk = f(part.shape[0])
+        mk = _running_sum(part) / nk
+        d = part - mk
+        qk = _running_sum(d * d)
+        tot = n + nk
+        delta = mk - mean
+        mean = mean + delta * (nk / tot)
+        m2 = m2 + qk + delta * delta * (n * nk / tot)
+        n = tot
+    var = m2 / f(T)
+    rstd = f(1) / np.sqrt(var + f(BN_EPS))
+    assert mean.dtype == var.dtype == rstd.dtype == f
+    return mean, var, rstd
+
+
+def bn_stat_bounds(z, chunks):
+    """The bound tests/test_gpu_dnn_edges.py holds the device's batch mean and rstd to: 4x the error of bn_stats_model against
+    float64 on the same z (mean relative to max |z| of its column, rstd relative; the worst column sets the figure; the better
+    of the candidate chunk heights), floored at one fp32 ulp of the reference value.  Returns the float64 (mean, var, rstd), the
+    columns' scale max |z|, the model's worst errors (e_mean relative to the scale, e_rstd relative) and (tol_mean, tol_rstd)."""
+    mean, var, rstd = stats64(z)
+    scale = np.maximum(np.abs(z).max(axis=0).astype(np.float64), 1e-30)
+    e_mean = e_rstd = np.inf
+    for c in chunks:
+        m, _, r = bn_stats_model(z, c)
+        e_mean = min(e_mean, float((np.abs(m - mean) / scale).max()))
+        e_rstd = min(e_rstd, float((np.abs(r - rstd) / rstd).max()))
+    tol_mean = np.maximum(4 * e_mean * scale, np.spacing(np.abs(mean).astype(np.float32)).astype(np.float64))
+    tol_rstd = np.maximum(4 * e_rstd * rstd, np.spacing(rstd.astype(np.float32)).astype(np.float64))
+    return (mean, var, rstd), scale, (e_mean, e_rstd), (tol_mean, tol_rstd)
+
+
+# ---- the mixed-precision step, link by link on the implementation's OWN operands ----
+# A whole-network comparison in bf16 mode cannot be sharp: an operand within fp32 round-off of a bf16 rounding boundary rounds
+# the other way in the implementation, moves its frame by ~5e-4, batch norm spreads that to every frame, and one layer later a
+# large share of the operands round "at random" (tests/test_bf16_links_host.py shows it on the CPU).  bf16_links is to that
+# cascade what relu_active is to the ReLU kink: every link of the chain is restated in float64 on the values the
+# implementation itself stored -- the bf16 twins the contractions read, the fp32 tensors everything else reads -- so both sides
+# start from bit-identical numbers and each tolerance is an fp32 round-off bound of ONE operation.
+GEMM_RTOL, GEMM_ATOL = 4e-7, 1e-6   # fp32 accumulation of exact products: tests/test_gpu_gemm_bf16.py
+ACT_RTOL, ACT_ATOL = 1e-4, 2e-5     # a layer output from its pre-activation: tests/test_gpu_dnn_edges.py
+SUM_RTOL, SUM_ATOL = 2e-4, 2e-5     # a gradient sum: tests/test_gpu_engine_parity.py (_check_grads)
+ULP32 = 2.0 ** -24
+LINK_ULPS = 8                       # the "small multiple" of 2^-24 of the element-wise fp32 operations of link B2
+
+
+def _contract(a, b, add=None):
+    """(want, tol) of the fp32-accumulated product of two matrices of bf16 values (+ an fp32 term `add`: a bias or the sum
+    accumulated so far): |err| <= 4e-7 * (sum_k |a_k b_k| + |add|) + 1e-6"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    want, mag = a.dot(b), np.abs(a).dot(np.abs(b))
+    if add is not None:
+        want, mag = want + add, mag + np.abs(add)
+    return want, GEMM_RTOL * mag + GEMM_ATOL
+
+
+def _sum_rule(want):
+    return SUM_RTOL * np.abs(want) + SUM_ATOL * max(float(np.abs(want).max()) if want.size else 0.0, 1e-3)
+
+
+def xent_criterion(y):
+    """cross-entropy: dLogits = softmax - onehot of the logits handed in; rtol 1e-4 + atol 2e-6 (tests/test_gpu_engine_parity.py)"""
+    y = np.asarray(y).astype(np.int64)
+
+    def crit(logits):
+        _, prob = OracleDNN._xent(logits, y)
+        prob[np.arange(len(y)), y] -= 1.0
+        return prob, 1e-4 * np.abs(prob) + 2e-6
+    return crit
+
+
+def ctc_criterion(utt_len, labels, label_len):
+    """the CTC loss: d loss / d logits of oracle/ctc_oracle.py on the logits handed in; rtol 1e-4 + atol 2e-5 below 200 frames,
+    2e-4 from there (tests/test_gpu_ctc.py)"""
+    def crit(logits):
+        from oracle.ctc_oracle import ctc_batch
+        _, dlog, _ = ctc_batch(logits, utt_len, labels, label_len, fast=True)
+        return dlog, 1e-4 * np.abs(dlog) + (2e-5 if logits.shape[0] < 200 else 2e-4)
+    return crit
+
+
+def bf16_links(net, taps, criterion, stat_chunks=(64, 128), tol_scale=1.0):
+    """Every link of one mixed-precision training micro-batch, restated in float64 on the implementation's own operands.
+
+    net       an OracleDNN holding the implementation's fp32 parameters (W, b, beta) and the chain (nonlin, bn, l2, keep)
+    taps      what the implementation stored, fp32 tensors and bf16 twins alike as arrays of their exact values:
+                X, Xb [T, F];  per evaluated hidden layer z, a, ab [T, H], with batch norm mean, rstd [H], with dropout masks;
+                logits (training mode, before the loss), dlogits, dlogb [T, O];  per active layer dzb [T, H] (mixed
+                precision stores dz as its twin alone: the kernel rounds it from its registers);
+                Wb[l] the weight twins;  G the gradient sums after the micro-batch, G0 those before it (absent: zero);
+                nact the active depth (layer-wise growth; absent: all layers).  An "operand" below is always a twin.
+    criterion logits -> (want dLogits, tolerance): xent_criterion / ctc_criterion, or the caller's own (MMI)
+    Returns (links, got): links a list of (name, want, tol) in float64, got the tapped array of every name.
+
+      F1  z_l = in . W_l + b_l on the operands; the contraction bound 4e-7 * (sum_k |a_k w_k| + |b|) + 1e-6
+      F2  mean_l, rstd_l against the float64 statistics of the tapped z_l (bn_stat_bounds)
+      F3  a_l against nonlinearity, L2 norm and dropout applied to the tapped z_l, mean_l, rstd_l and beta; rtol 1e-4 + atol 2e-5
+      F4  logits = a_{L-1} . W_L + b_L, as F1
+      TW  every twin that has an fp32 tensor beside it (Xb, ab_l, dlogb, Wb_l) equals round_bf16 of it, bit for bit (tolerance 0)
+      LOSS dLogits against the criterion on the tapped logits
+      B1  G[W_l] = G0 + in^T . dz_l on the operands (contraction bound, K = T, |G0| added to the sum); G[b_l] = G0 + the column
+          sums of this function's dz_l (the implementation sums its fp32 dz in registers and stores none: the rule plus the
+          column sums of B2's fp32 tolerance) and G[beta_l] = G0 + the column sums of this function's du_l, both under the
+          gradient-sum rule rtol 2e-4 + atol 2e-5 max |G| (the bias of a batch-normed layer, whose true gradient is zero so that
+          max |G| says nothing about the summands: the smaller of _check_grads' rule for it, 1e-4 max(1, max |G[W_l]|), and the
+          sum rule plus 8 x 2^-24 x sum |dz|, the round-off of an fp32 sum of T terms in any order up to T = 2^21)
+      B2  the twin dzb_l from the operands dz_{l+1}, W_{l+1} and the tapped a_l, z_l, mean_l, rstd_l, masks.  No fp32 dz exists
+          to compare the twin with, but rounding to nearest is monotone: an fp32 dz within tol of `want` has its twin in
+          [round_bf16(want - tol), round_bf16(want + tol)], tol the fp32 tolerance derived below.  Both ends are the same bf16
+          value -- the check is bit for bit -- unless want lies within tol of a rounding boundary, where the two neighbours
+          pass; the link is given as that interval's midpoint and half-width.  A truncated twin or one moved to a
+          neighbouring value fails it.
+      tol_scale multiplies every fp32 tolerance (B2's before the rounding): bf16_links(..., tol_scale=0.25) holds the
+      implementation to a quarter of every bound, the head-room check of tests/test_bf16_links_host.py.
+
+    The tolerance of B2, derived (nothing in it is measured on an implementation).  The implementation keeps no du, so the
+    link spans the contraction t = dz_{l+1} . W_{l+1}^T and the element-wise chain behind it.
+      (1) t carries the contraction bound e_t = 4e-7 * sum_k |dz_k w_k| + 1e-6, element by element.
+      (2) du = t * (mask / keep) * act'(v), v the tapped layer output un-scaled (the very fp32 value the implementation takes
+          the derivative from, so act' itself differs only by the round-off of evaluating it: relu exact, v (1 - v) and
+          1 - v^2 at most 2 ulp of ONE, not of act' -- 1 - v^2 cancels).  |act'| <= 1, so
+          e_du = e_t * (mask / keep) * |act'| + LINK_ULPS * 2^-24 * |t| * (mask / keep)
+          covers that, the product's two roundings and the scale.  (L2 norm active, s > 1: the row map dv = dw / s - v * 2 (dw .
+          v) / (H s^2) is linear in dw; e and the magnitude go through its absolute-value form in the same way.)
+      (3) batch norm backward is linear in du: dz = rstd * (du - mean(du) - xhat * mean(du * xhat)).  An error e_du >= 0 on du moves
+          dz by at most  rstd * (e_du + mean(e_du) + |xhat| * mean(e_du * |xhat|))  -- the absolute-value form of the map.
+      (4) the map's own fp32 evaluation (xhat, two products, an fma, the two column means): every operation is exact to 2^-24 of
+          its result and there are fewer than LINK_ULPS of them in a row, so it adds at most
+          LINK_ULPS * 2^-24 * rstd * (|du| + mean(|du|) + |xhat| * mean(|du * xhat|)),
+          the same absolute-value form applied to the MAGNITUDES; the means are sums of T terms whose partial sums the mean of
+          the magnitudes bounds.
+      Without batch norm dz = du and the tolerance is e_du."""
+    f64 = lambda x: np.asarray(x, dtype=np.float64)
+    L, H, keep = net.L, net.H, net.keep
+    T = taps["X"].shape[0]
+    nfw, nact = len(taps["z"]), taps.get("nact", net.L)
+    G, G0 = taps["G"], taps.get("G0") or {k: np.zeros_like(f64(v)) for k, v in taps["G"].items()}
+    Wb = [f64(w) for w in taps["Wb"]]
+    links, got = [], {}
+
+    def link(name, tapped, want, tol):
+        want = f64(want)
+        links.append((name, want, np.broadcast_to(f64(tol) * tol_scale, want.shape)))
+        got[name] = f64(tapped)
+
+    # twins, bit for bit
+    link("TW Xb", taps["Xb"], round_bf16(taps["X"]), 0.0)
+    for l in range(nfw):
+        link("TW ab%d" % l, taps["ab"][l], round_bf16(taps["a"][l]), 0.0)
+    link("TW dlogb", taps["dlogb"], round_bf16(taps["dlogits"]), 0.0)
+    for l in range(L + 1):
+        link("TW Wb%d" % l, Wb[l], round_bf16(net.W[l]), 0.0)
+
+    # forward
+    xhat, vs, ss = [None] * nfw, [None] * nfw, [None] * nfw
+    for l in range(nfw):
+        inb = f64(taps["Xb"] if l == 0 else taps["ab"][l - 1])
+        want, tol = _contract(inb, Wb[l], net.b[l])
+        link("F1 z%d" % l, taps["z"][l], want, tol)
+        z = f64(taps["z"][l])
+        u = z
+        if net.bn:
+            (mean, _, rstd), _, _, (tol_mean, tol_rstd) = bn_stat_bounds(taps["z"][l], stat_chunks)
+            link("F2 mean%d" % l, taps["mean"][l], mean, tol_mean)
+            link("F2 rstd%d" % l, taps["rstd"][l], rstd, tol_rstd)
+            xhat[l] = (z - f64(taps["mean"][l])) * f64(taps["rstd"][l])
+            u = xhat[l] + net.beta[l]
+        v = _nonlin(u, net.nonlin)
+        w = v
+        if net.l2:
+            ss[l] = (v ** 2).mean(axis=1, keepdims=True)
+            w = np.where(ss[l] > 1, v / ss[l], v)
+        if net.dropout:
+            w = w * f64(taps["masks"][l]) / keep
+        vs[l] = v
+        link("F3 a%d" % l, taps["a"][l], w, ACT_RTOL * np.abs(w) + ACT_ATOL)
+    want, tol = _contract(taps["ab"][nact - 1], Wb[L], net.b[L])
+    link("F4 logits", taps["logits"], want, tol)
+
+    # loss
+    want, tol = criterion(f64(taps["logits"]))
+    link("LOSS dlogits", taps["dlogits"], want, tol)
+
+    # backward, from the top
+    def sums(key, summands, dead=None, slack=0.0):
+        want = G0[key] + f64(summands).sum(axis=0)
+        tol = _sum_rule(want) + slack
+        if dead is not None:
+            tol = np.minimum(1e-4 * max(1.0, float(np.abs(G["W" + key[1:]]).max())),
+                             tol + LINK_ULPS * ULP32 * np.abs(f64(summands)).sum(axis=0))
+        link("B1 G[%s]" % key, G[key], want, tol)
+
+    want, tol = _contract(f64(taps["ab"][nact - 1]).T, taps["dlogb"], G0["W%d" % L])
+    link("B1 G[W%d]" % L, G["W%d" % L], want, tol)
+    sums("b%d" % L, taps["dlogits"])
+    up, w_up = f64(taps["dlogb"]), Wb[L]
+    for l in range(L - 1, nact - 1, -1):  # above the active depth: no gradient
+        for k in ("W%d" % l, "b%d" % l) + (("beta%d" % l,) if net.bn else ()):
+            link("B1 G[%s] inactive" % k, G[k], G0[k], 0.0)
+    for l in range(nact - 1, -1, -1):
+        t, e = _contract(up, w_up.T)
+        a = f64(taps["a"][l])
+        scale = f64(taps["masks"][l]) / keep if net.dropout else 1.0
+        dw, e, mag = t * scale, e * scale, np.abs(t) * scale
+        if net.l2:
+            v, s = vs[l], ss[l]
+            lin = lambda d, vv: np.where(s > 1, d / s + vv * (2.0 * (d * vv).sum(axis=1, keepdims=True) / (H * s * s)), d)
+            dv = np.where(s > 1, dw / s - v * (2.0 * (dw * v).sum(axis=1, keepdims=True) / (H * s * s)), dw)
+            e, mag = lin(e, np.abs(v)), lin(mag, np.abs(v))
+            dact = (a > 0).astype(np.float64) if net.nonlin == "relu" else _nonlin_grad(v, net.nonlin)
+        else:
+            dv = dw
+            dact = (a > 0).astype(np.float64) if net.nonlin == "relu" else _nonlin_grad(a * keep, net.nonlin)
+        du = dv * dact
+        e_du = e * np.abs(dact) + LINK_ULPS * ULP32 * mag
+        if net.bn:
+            x, r = xhat[l], f64(taps["rstd"][l])
+            want = r * (du - du.mean(axis=0) - x * (du * x).mean(axis=0))
+            ax, adu = np.abs(x), np.abs(du)
+            tol = (r * (e_du + e_du.mean(axis=0) + ax * (e_du * ax).mean(axis=0))
+                   + LINK_ULPS * ULP32 * r * (adu + adu.mean(axis=0) + ax * (adu * ax).mean(axis=0)))
+            sums("beta%d" % l, du)
+        else:
+            want, tol = du, e_du
+        tol = np.broadcast_to(tol, want.shape) * tol_scale
+        lo, hi = round_bf16(want - tol), round_bf16(want + tol)
+        links.append(("B2 dzb%d" % l, (lo + hi) / 2, (hi - lo) / 2))
+        got["B2 dzb%d" % l] = f64(taps["dzb"][l])
+        sums("b%d" % l, want, dead=True if net.bn else None, slack=tol.sum(axis=0) / tol_scale)
+        inb = f64(taps["Xb"] if l == 0 else taps["ab"][l - 1])
+        want, tol = _contract(inb.T, taps["dzb"][l], G0["W%d" % l])
+        link("B1 G[W%d]" % l, G["W%d" % l], want, tol)
+        up, w_up = f64(taps["dzb"][l]), Wb[l]
+    return links, got
+
+
+def link_ratios(links, got):
+    """{name: worst err / tol} of bf16_links' result; a link of tolerance 0 (bit for bit) counts 0 when equal and inf when not"""
+    out = {}
+    for name, want, tol in links:
+        err = np.abs(got[name] - want)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(err == 0, 0.0, err / tol)
+        out[name] = float(ratio.max()) if ratio.size else 0.0
+    return out

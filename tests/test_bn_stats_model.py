@@ -27,7 +27,8 @@ How (ii) is measured: on the WORST offset column.  Which way the roundings of th
 import numpy as np
 import pytest
 
-BN_EPS = float(np.float32(1e-3))  # the fp32 value the kernels add to the variance
+from oracle.dnn_oracle import BN_EPS, _running_sum, bn_stats_model, stats64  # noqa: F401 (the model lives with the oracle: the link checker bounds with it too)
+
 OFFSET, F, H = 30.0, 20, 130
 CONSTANT_COL = 128                # first column of the second 128-column block
 ROWS = [2, 129, 2177, 4225]
@@ -42,44 +43,6 @@ def offset_layer(rng, d_in, d_out, x_std, constant_col=None):
     if constant_col is not None:
         W[:, constant_col] = 0.0
     return W, b
-
-
-def stats64(z):
-    """float64 column mean, biased variance and rstd of the fp32 matrix z"""
-    z = np.asarray(z, dtype=np.float64)
-    mean = z.mean(axis=0)
-    var = ((z - mean) ** 2).mean(axis=0)
-    return mean, var, 1.0 / np.sqrt(var + BN_EPS)
-
-
-def _running_sum(x):
-    return np.add.accumulate(x, axis=0, dtype=np.float32)[-1]  # one fp32 accumulator per column, row after row
-
-
-def bn_stats_model(z, chunk_rows):
-    """fp32 (mean, biased variance, rstd) of the columns of z[T, H]: per chunk of chunk_rows rows a sequential two-pass
-    (mean, M2), the chunks merged one after the other (Chan et al.), every operation rounded to float32"""
-    z = np.ascontiguousarray(z, dtype=np.float32)
-    T = z.shape[0]
-    f = np.float32
-    n = f(0)
-    mean = np.zeros(z.shape[1], dtype=f)
-    m2 = np.zeros(z.shape[1], dtype=f)
-    for r0 in range(0, T, chunk_rows):
-        part = z[r0:r0 + chunk_rows]
-        nk = f(part.shape[0])
-        mk = _running_sum(part) / nk
-        d = part - mk
-        qk = _running_sum(d * d)
-        tot = n + nk
-        delta = mk - mean
-        mean = mean + delta * (nk / tot)
-        m2 = m2 + qk + delta * delta * (n * nk / tot)
-        n = tot
-    var = m2 / f(T)
-    rstd = f(1) / np.sqrt(var + f(BN_EPS))
-    assert mean.dtype == var.dtype == rstd.dtype == f
-    return mean, var, rstd
 
 
 def one_pass_rstd(z):

@@ -52,6 +52,7 @@ import numpy as np
 import pytest
 
 from oracle.dnn_oracle import OracleDNN, _nonlin
+from oracle.dnn_oracle import bn_stat_bounds as _stat_bounds  # (the link checker, tests/test_gpu_bf16_links.py, bounds F2 with it too)
 from test_bn_stats_model import BN_EPS, CONSTANT_COL, bn_stats_model, offset_layer, stats64
 from test_gpu_engine_parity import _check_grads
 from util import assert_close, batch, copy_oracle_to_engine, engine_grads, engine_params, oracle_kwargs, randomize
@@ -294,21 +295,6 @@ def _model_chunks(dtype, chain, T):
         rs = min((T + 31) // 32, 256)
         return [(T + rs - 1) // rs]
     return [128] if dtype == "float32" else [64, 128]
-
-
-def _stat_bounds(z, chunks):
-    """float64 (mean, var, rstd) of the columns of z; the model's worst errors (mean relative to max |z| of the column, rstd
-    relative); the per-column bounds on the device's mean and rstd"""
-    mean, var, rstd = stats64(z)
-    scale = np.maximum(np.abs(z).max(axis=0).astype(np.float64), 1e-30)
-    e_mean = e_rstd = np.inf
-    for c in chunks:
-        m, _, r = bn_stats_model(z, c)
-        e_mean = min(e_mean, float((np.abs(m - mean) / scale).max()))
-        e_rstd = min(e_rstd, float((np.abs(r - rstd) / rstd).max()))
-    tol_mean = np.maximum(4 * e_mean * scale, np.spacing(np.abs(mean).astype(np.float32)).astype(np.float64))
-    tol_rstd = np.maximum(4 * e_rstd * rstd, np.spacing(rstd.astype(np.float32)).astype(np.float64))
-    return (mean, var, rstd), scale, (e_mean, e_rstd), (tol_mean, tol_rstd)
 
 
 def _within(name, got, want, tol):

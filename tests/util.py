@@ -97,3 +97,47 @@ def assert_close(name, got, want, rtol, atol):
         i = np.unravel_index(np.argmax(err - tol), err.shape)
         raise AssertionError("%s: |%.9g - %.9g| = %.3g > %.3g at %s (worst of %d / %d violations)" % (
             name, got[i], want[i], err[i], tol[i], i, int((err > tol).sum()), err.size))
+
+
+# ---- the mixed-precision step link by link (oracle/dnn_oracle.py: bf16_links) on an engine's own operands ----
+def engine_link_taps(eng, net, X, G0=None):
+    """What bf16_links reads, fetched from a bf16 engine run under debug_capture after a training call on X; `net` holds the
+    engine's parameters and active depth.  G0: engine_grads before the call (None: the step's first micro-batch)."""
+    from tfkaldi_amd import _lib
+    T, L = X.shape[0], eng.L
+    nact = net.num_active()
+    nfw = L if (net.layerwise and net.bn) else nact
+    f, tw = eng.debug_fetch, eng.debug_fetch_twin
+    tp = dict(X=np.ascontiguousarray(X, dtype=np.float32), Xb=tw(_lib.TWIN_INPUT, 0, T), nact=nact, G0=G0, G=engine_grads(eng))
+    tp["z"] = [f(_lib.DBG_PREACT, l, T) for l in range(nfw)]
+    tp["a"] = [f(_lib.DBG_HIDDEN, l, T) for l in range(nfw)]
+    tp["ab"] = [tw(_lib.TWIN_HIDDEN, l, T) for l in range(nfw)]
+    if net.bn:
+        tp["mean"] = [f(_lib.DBG_BN_MEAN, l, T)[0] for l in range(nfw)]
+        tp["rstd"] = [f(_lib.DBG_BN_RSTD, l, T)[0] for l in range(nfw)]
+    tp["logits"], tp["dlogits"] = f(_lib.DBG_TRAIN_LOGITS, 0, T), f(_lib.DBG_LOGITS, 0, T)
+    tp["dlogb"] = tw(_lib.TWIN_DLOGITS, 0, T)
+    tp["dzb"] = [tw(_lib.TWIN_DPREACT, l, T) for l in range(nact)]
+    tp["Wb"] = [tw(_lib.TWIN_WEIGHTS, l) for l in range(L + 1)]
+    if net.dropout:  # (last: regenerating a mask uses the backward pass's scratch)
+        tp["masks"] = [f(_lib.DBG_DROPOUT_MASK, l, T).astype(np.float64) for l in range(nfw)]
+    return tp
+
+
+def assert_links(label, net, taps, criterion, stat_chunks=(64, 128), tol_scale=1.0):
+    """every link of the step within its tolerance; prints one line per link kind with the worst err / tol and returns them"""
+    from oracle.dnn_oracle import bf16_links, link_ratios
+    links, got = bf16_links(net, taps, criterion, stat_chunks, tol_scale)
+    ratios = link_ratios(links, got)
+    exact = [float((tol == 0).mean()) for name, _, tol in links if name.startswith("B2")]
+    kinds = {}
+    for name, r in ratios.items():
+        kind = name.split()[0] + " " + "".join(c for c in name.split()[1] if not c.isdigit())
+        if r >= kinds.get(kind, ("", -1.0))[1]:
+            kinds[kind] = (name, r)
+    for kind, (name, r) in kinds.items():
+        note = " -- 1 = an end of the rounding interval; bit for bit on %.1f %% of the elements" % (100 * min(exact)) if kind.startswith("B2") else ""
+        print("bf16-links %-34s %-12s worst err/tol %.3f (%s)%s" % (label, kind, r, name, note))
+    bad = sorted((n, r) for n, r in ratios.items() if not r <= 1)
+    assert not bad, "%s: links out of bound: %s" % (label, ", ".join("%s %.3g" % b for b in bad))
+    return ratios

@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -49,7 +49,8 @@ SLOT_PARAM, SLOT_GRAD, SLOT_ADAM_M, SLOT_ADAM_V = range(4)
 (GLOBAL_STEP, LEARNING_RATE_FACT, INITIALISED_LAYERS, ADAM_STEPS, BATCH_LOSS, NUM_FRAMES,
  LEARNING_RATE) = range(7)
 DEVICE_PTRS, LAST_MICROBATCH, LOG_DIV_PRIOR, RAW_LOGITS, RAW_DEVICE, CTC_LM_EOS, CTC_LM = 1, 2, 4, 8, 16, 32, 64
-DBG_LOGITS, DBG_HIDDEN, DBG_DROPOUT_MASK, DBG_PREACT, DBG_BN_MEAN, DBG_BN_RSTD = range(6)
+DBG_LOGITS, DBG_HIDDEN, DBG_DROPOUT_MASK, DBG_PREACT, DBG_BN_MEAN, DBG_BN_RSTD, DBG_DPREACT, DBG_TRAIN_LOGITS = range(8)
+TWIN_INPUT, TWIN_HIDDEN, TWIN_DLOGITS, TWIN_WEIGHTS, TWIN_DPREACT = range(5)  # TFK_TWIN_* (tfk_debug_fetch_twin)
 GEMM_NN, GEMM_NT, GEMM_TN = range(3)
 EPI_BIAS, EPI_ACCUM, EPI_RELU = 1, 2, 4
 EXCHANGE = {"sharded": 0, "allreduce": 1}  # TFK_EXCHANGE_*
@@ -248,6 +249,8 @@ SYMBOLS = {
     "tfk_profile_begin": (c_int, [_E]),
     "tfk_profile_end": (c_int, [_E, POINTER(TfkKernelStat), c_int, POINTER(c_int)]),
     "tfk_debug_fetch": (c_int, [_E, c_int, c_int, c_void_p, c_size_t]),
+    "tfk_debug_fetch_twin": (c_int, [_E, c_int, c_int, c_void_p, c_size_t]),
+    "tfk_debug_capture": (c_int, [_E, c_int]),
     "tfk_gemm_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                              c_int, c_void_p, c_int, c_int]),
     "tfk_gemm_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,

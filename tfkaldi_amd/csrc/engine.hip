@@ -302,6 +302,16 @@ struct tfk_engine {
   int last_T = 0, last_nfw = 0;
   uint32_t last_call = 0;
   const float* last_in = nullptr;
+  int last_train = 0;
+  // tfk_debug_capture: per hidden layer a copy of dz as hidden_backward leaves it -- in mixed precision that is the bf16 twin
+  // alone (hb_apply_kernel rounds dz from its registers and stores no fp32 copy) -- which the backward pass otherwise keeps
+  // only in the ping-pong buffers dAb.  Off (the default): no buffer, not one extra call.
+  bool dbg_capture = false;
+  std::vector<bf16_t*> dbg_dzb;
+  float* dbg_logits = nullptr;  // the training-mode logits, copied before the loss turns them into dLogits in place
+  bool dbg_valid = false;     // the buffers hold the pass `dbg_call`, layers [0, dbg_nact)
+  uint32_t dbg_call = 0;
+  int dbg_nact = 0;
 
   // profiling
   bool profiling = false;
@@ -664,6 +674,20 @@ int run_gemm_dual(tfk_engine* e, const float* dz, int ld_dz, const float* W, int
   return 0;
 }
 
+// the per-layer dz copies of tfk_debug_capture
+void free_capture(tfk_engine* e, bool async) {
+  for (auto& p : e->dbg_dzb) { dev_free(e, p, async); p = nullptr; }
+  e->dbg_dzb.clear();
+  dev_free(e, e->dbg_logits, async); e->dbg_logits = nullptr;
+  e->dbg_valid = false;
+}
+int alloc_capture(tfk_engine* e, int cap) {
+  e->dbg_dzb.assign(e->L, nullptr);
+  CHK(dev_alloc(e, (void**)&e->dbg_logits, (size_t)cap * e->ldO * sizeof(float), true));
+  for (int l = 0; l < e->L; ++l) CHK(dev_alloc(e, (void**)&e->dbg_dzb[l], (size_t)cap * e->ldHb * sizeof(bf16_t), true));
+  return 0;
+}
+
 void free_activations(tfk_engine* e, bool async = false) {
   auto fr = [&](float*& p) { dev_free(e, p, async); p = nullptr; };
   for (int s = 0; s < 2; ++s) {
@@ -689,6 +713,7 @@ void free_activations(tfk_engine* e, bool async = false) {
   for (auto& p : e->v) fr(p);
   for (auto& p : e->rowscale) fr(p);
   fr(e->logits); fr(e->post); fr(e->row_loss); fr(e->ws); fr(e->ws_bwd); fr(e->ws_stats);
+  free_capture(e, async);
   e->cap = 0;
 }
 
@@ -770,6 +795,7 @@ int reserve(tfk_engine* e, int T) {
   CHK(grow_zero(e, &e->ws_stats, (size_t)2 * ((cap + 63) / 64) * e->ldH));
   e->ws_bwd_stride = (size_t)3 * kMaxRowSplits * ldmax;
   CHK(grow_zero(e, &e->ws_bwd, e->ws_bwd_stride * (L + 1)));
+  if (e->dbg_capture) CHK(alloc_capture(e, cap));
   // the copy stream writes the new input slots: not before their allocation + zero fill in engine-stream order
   HIPCHK(hipEventRecord(e->ev_grow, e->stream));
   HIPCHK(hipStreamWaitEvent(e->copy_stream, e->ev_grow, 0));
@@ -1088,6 +1114,10 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
   float* G = e->p_grad();
   const int acc = e->grads_fresh ? 0 : 1;
   const int epi_w = acc ? EPI_ACCUM : 0;
+  const bool capture = e->dbg_capture && !st && !e->dbg_dzb.empty();
+  e->dbg_valid = capture;
+  e->dbg_call = call;
+  e->dbg_nact = nact;
   if (!acc)  // layers above the active depth are not visited below: their (logically zero) G must be zero
     for (int l = nact; l < L; ++l) {
       const LayerLayout& q = e->lay[l];
@@ -1231,6 +1261,8 @@ int backward(tfk_engine* e, const float* Xd, int ldx, int T, int nact, uint32_t 
                       bnb_done ? e->bnb_words : nullptr, bnb_done);
       fin_layer(fuse_hb ? chunks_eff : rs, rs);
     }
+    if (capture)  // tfk_debug_capture: dz_l leaves the ping-pong buffer before the layer after next overwrites it
+      HIPCHK(hipMemcpyAsync(e->dbg_dzb[l], e->dAb[pp], (size_t)T * e->ldHb * sizeof(bf16_t), hipMemcpyDeviceToDevice, e->stream));
     const float* in = l == 0 ? Xd : e->a[l - 1];
     const int ld_in = l == 0 ? ldx : ldH;
     bool fused = false;
@@ -1986,6 +2018,7 @@ int stage_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int
 // what tfk_debug_fetch reads back
 void remember_pass(tfk_engine* e, int T, int nfw, uint32_t call, const float* in) {
   e->last_T = T; e->last_nfw = nfw; e->last_call = call; e->last_in = in;
+  e->last_train = 0;
 }
 
 // One micro-batch -- or, with `st`, one stacked pass of st->k micro-batches (train only) -- through staging, forward, loss and
@@ -2003,6 +2036,8 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
   // fetched by update_gradients_op (trainer.py:164-169) even for layers the tf.case does not select.
   const int nfw = (train && e->cfg.layerwise_init && e->cfg.batch_norm) ? e->L : p.nact;
   CHK(forward(e, p.Xd, p.ld, T, train, p.nact, nfw, p.call, st));
+  if (train && e->dbg_capture && !st && e->dbg_logits)  // tfk_debug_capture: the loss overwrites the logits with dLogits
+    HIPCHK(hipMemcpyAsync(e->dbg_logits, e->logits, (size_t)T * e->ldO * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
   if (ctc) {
     CHK(ctc->mwer ? ctc_mwer_loss(e, *ctc, T, train) : ctc->mmi ? ctc_mmi_loss(e, *ctc, T, train) : ctc_loss(e, *ctc, T, train));
   } else {
@@ -2047,6 +2082,7 @@ int run_pass(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int T
   HIPCHK(hipGetLastError());
   CHK(finish_slot(e, flags, p.slot_before));
   remember_pass(e, T, nfw, p.call, p.Xd);
+  e->last_train = train;
   return 0;
 }
 int train_or_eval(tfk_engine* e, const float* X, int64_t ldx, const int32_t* y, int32_t T, int flags, int train,
@@ -3935,12 +3971,79 @@ int tfk_profile_end(tfk_engine* e, tfk_kernel_stat* stats, int capacity, int* co
   return 0;
 }
 
+// the dz copies of tfk_debug_capture hold hidden layer `layer` of the last call
+static int captured(const tfk_engine* e, int layer) {
+  if (!e->dbg_capture) return fail(-1, "dz of a hidden layer is kept only under tfk_debug_capture (capture is off)");
+  if (!e->dbg_valid || e->dbg_call != e->last_call || !e->last_train)
+    return fail(-1, "no captured dz: the last call was not a non-stacked training pass run under tfk_debug_capture");
+  if (layer < 0 || layer >= e->dbg_nact) return fail(-1, "layer %d received no gradient in the last call (active depth %d)", layer, e->dbg_nact);
+  return 0;
+}
+
+int tfk_debug_capture(tfk_engine* e, int on) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (e->x3) return fail(-1, "tfk_debug_capture: the emulated-fp32 mode (three-plane twins) is not supported: its fused dual launch never stores du or dz in fp32");
+  if (!e->bf16) return fail(-1, "tfk_debug_capture: bf16 mode only (compute_dtype bfloat16)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if ((on != 0) == e->dbg_capture) return 0;
+  e->dbg_capture = on != 0;
+  if (!on) {
+    free_capture(e, /*async=*/true);
+    return 0;
+  }
+  if (e->cap > 0) CHK(alloc_capture(e, e->cap));
+  return 0;
+}
+
+int tfk_debug_fetch_twin(tfk_engine* e, int what, int layer, uint16_t* host, size_t count) {
+  if (!e || !host) return fail(-1, "NULL argument");
+  if (e->x3) return fail(-1, "tfk_debug_fetch_twin: the three-plane twins of the emulated-fp32 mode are not supported");
+  if (!e->bf16) return fail(-1, "tfk_debug_fetch_twin: bf16 mode only (the fp32 modes keep no bf16 twins)");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  CHK(sync_streams(e));
+  const bf16_t* src = nullptr;
+  int rows = e->last_T, cols = 0, ld = 0;
+  if (what == TFK_TWIN_WEIGHTS) {
+    if (layer < 0 || layer > e->L) return fail(-1, "layer %d out of range", layer);
+    if (e->shadow_dirty) return fail(-1, "the weight shadow is not current: the next pass rebuilds it from the fp32 parameters");
+    src = e->Wb + e->wb_off[layer]; rows = e->lay[layer].d_in; cols = e->lay[layer].d_out; ld = e->wb_ld[layer];
+  } else {
+    if (rows <= 0) return fail(-1, "no previous call to fetch from");
+    if (what == TFK_TWIN_INPUT) {
+      const int s = e->last_in == e->dX[0] ? 0 : e->last_in == e->dX[1] ? 1 : -1;
+      if (s < 0) return fail(-1, "the last call's input is not one of the engine's slots");
+      src = e->Xb[s]; cols = e->F; ld = e->ldFb;
+    } else if (what == TFK_TWIN_DLOGITS) {
+      if (!e->last_train) return fail(-1, "the dLogits twin is written by training calls only");
+      src = e->logb; cols = e->O; ld = e->ldOb;
+    } else if (what == TFK_TWIN_HIDDEN) {
+      if (layer < 0 || layer >= e->L) return fail(-1, "layer %d out of range", layer);
+      if (layer >= e->last_nfw) return fail(-1, "layer %d was not evaluated by the last call", layer);
+      src = e->ab[layer]; cols = e->H; ld = e->ldHb;
+    } else if (what == TFK_TWIN_DPREACT) {
+      CHK(captured(e, layer));
+      src = e->dbg_dzb[layer]; cols = e->H; ld = e->ldHb;
+    } else {
+      return fail(-1, "unknown twin %d", what);
+    }
+  }
+  if (count != (size_t)rows * cols) return fail(-1, "count %zu != %d x %d", count, rows, cols);
+  HIPCHK(hipMemcpy2D(host, (size_t)cols * 2, src, (size_t)ld * 2, (size_t)cols * 2, rows, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int tfk_debug_fetch(tfk_engine* e, int what, int layer, float* host, size_t count) {
   if (!e || !host) return fail(-1, "NULL argument");
   HIPCHK(hipSetDevice(e->cfg.device));
   CHK(sync_streams(e));
   const int T = e->last_T;
   if (T <= 0) return fail(-1, "no previous call to fetch from");
+  if (what == TFK_DBG_TRAIN_LOGITS) {
+    CHK(captured(e, 0));
+    if (count != (size_t)T * e->O) return fail(-1, "count %zu != %d x %d", count, T, e->O);
+    HIPCHK(hipMemcpy2D(host, (size_t)e->O * 4, e->dbg_logits, (size_t)e->ldO * 4, (size_t)e->O * 4, T, hipMemcpyDeviceToHost));
+    return 0;
+  }
   if (what == TFK_DBG_LOGITS) {
     if (count != (size_t)T * e->O) return fail(-1, "count %zu != %d x %d", count, T, e->O);
     HIPCHK(hipMemcpy2D(host, (size_t)e->O * 4, e->logits, (size_t)e->ldO * 4, (size_t)e->O * 4, T, hipMemcpyDeviceToHost));
@@ -3960,6 +4063,16 @@ int tfk_debug_fetch(tfk_engine* e, int what, int layer, float* host, size_t coun
     } else {
       memset(host, 0, count * sizeof(float));
       HIPCHK(hipMemcpy(host, what == TFK_DBG_BN_MEAN ? e->mean[layer] : e->rstd[layer], (size_t)e->H * 4, hipMemcpyDeviceToHost));
+    }
+    return 0;
+  }
+  if (what == TFK_DBG_DPREACT) {
+    CHK(captured(e, layer));  // (mixed precision keeps dz as its bf16 twin alone: those values, widened)
+    std::vector<uint16_t> bits(count);
+    HIPCHK(hipMemcpy2D(bits.data(), (size_t)e->H * 2, e->dbg_dzb[layer], (size_t)e->ldHb * 2, (size_t)e->H * 2, T, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i) {
+      const uint32_t u = (uint32_t)bits[i] << 16;
+      memcpy(host + i, &u, sizeof(float));
     }
     return 0;
   }

@@ -919,7 +919,25 @@ class Engine(object):
                      flops=stats[i].flops, bytes=stats[i].bytes) for i in range(min(n.value, 32))]
 
     def debug_fetch(self, what, layer, T):
-        cols = self.O if what == _lib.DBG_LOGITS else self.H
+        cols = self.O if what in (_lib.DBG_LOGITS, _lib.DBG_TRAIN_LOGITS) else self.H
         out = np.empty((T, cols), dtype=np.float32)
         check(self.lib.tfk_debug_fetch(self._h, what, layer, out.ctypes.data_as(c_void_p), out.size))
         return out
+
+    def debug_capture(self, on=True):
+        """tfk_debug_capture: the later non-stacked training passes keep the training logits (DBG_TRAIN_LOGITS; the loss
+        overwrites them in place) and every hidden layer's dz as its bf16 twin, the only form mixed precision stores it in
+        (TWIN_DPREACT; DBG_DPREACT returns the same values widened).  bf16 mode.  Off by default: a pass then enqueues nothing
+        extra."""
+        check(self.lib.tfk_debug_capture(self._h, int(bool(on))))
+
+    def debug_fetch_twin(self, what, layer=0, T=None):
+        """tfk_debug_fetch_twin: a bf16 operand twin as the contractions read it (bf16 mode), as a float32 array that holds
+        exactly the bf16 values.  T: rows of the last call (not needed for TWIN_WEIGHTS)."""
+        if what == _lib.TWIN_WEIGHTS:
+            shape = (self.F if layer == 0 else self.H, self.O if layer == self.L else self.H)
+        else:
+            shape = (T, {_lib.TWIN_INPUT: self.F, _lib.TWIN_DLOGITS: self.O}.get(what, self.H))
+        bits = np.empty(shape, dtype=np.uint16)
+        check(self.lib.tfk_debug_fetch_twin(self._h, what, layer, bits.ctypes.data_as(c_void_p), bits.size))
+        return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
