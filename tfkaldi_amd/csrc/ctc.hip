@@ -595,6 +595,31 @@ __device__ __forceinline__ void beam_for_run(int cpt, F f) {
     }
 }
 
+// One wave's half of a radix pass: of the 256 bins of hist (the highest digit first) the one that holds the `need`-th key
+// -> sel[0], the rank still wanted inside that bin -> sel[1], the bin's count -> sel[2]; hist is left cleared for the next pass.
+__device__ __forceinline__ void radix_pick_bin(uint32_t* hist, int* sel, int need, int lane) {
+  const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
+  const int s = (int)(h.x + h.y + h.z + h.w);
+  int incl = s;  // this lane's bins and every higher one
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_down(incl, o);
+    if (lane + o < 64) incl += v;
+  }
+  int above = incl - s;
+  const uint32_t hv[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const int c = (int)hv[q];
+    if (need > above && need <= above + c) {
+      sel[0] = 4 * lane + q;
+      sel[1] = need - above;
+      sel[2] = c;
+    }
+    above += c;
+  }
+  reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // The `need`-th largest of the non-zero keys keyf(k), k in [k0, k1) over the block's threads (need <= their number):
 // returns it; *take = how many candidates EQUAL to it belong to the best `need`, *have = how many there are.
 template <class F>
@@ -610,28 +635,7 @@ __device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, in
         atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
-    if (tid < 64) {
-      const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
-      const int s = (int)(h.x + h.y + h.z + h.w);
-      int incl = s;  // this lane's bins and every higher one
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_down(incl, o);
-        if (lane + o < 64) incl += v;
-      }
-      int above = incl - s;
-      const uint32_t hv[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-      for (int q = 3; q >= 0; --q) {
-        const int c = (int)hv[q];
-        if (need > above && need <= above + c) {
-          sel[0] = 4 * lane + q;
-          sel[1] = need - above;
-          sel[2] = c;
-        }
-        above += c;
-      }
-      reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    if (tid < 64) radix_pick_bin(hist, sel, need, lane);
     __syncthreads();
     prefix |= (uint32_t)sel[0] << shift;
     need = sel[1];
@@ -640,6 +644,34 @@ __device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, in
   *take = need;
   *have = cnt;
   return prefix;
+}
+
+// the model of a search as the kernels receive it: table = the n-gram table [C, O], or the graph's weight [S, O] with
+// next [S, O] and start; eos = the end term counts.  The launchers build it once from CtcLm (beam_model).
+struct BeamModel { const float* table; int C; float weight, bonus; int eos; const int32_t* next; int start; };
+
+// The start of both searches: the beam is {(): (0, -inf)}, the block's LDS state cleared.  The caller's barrier follows.
+// (It is the one part of the two kernels that is written once.  Shared bodies for phases B to E and for the epilogue were
+// built and measured -- profiles/ctc_beam_refactor_ab.txt: every output stayed the parent's bit for bit, but each of them,
+// the epilogue included, changes how the compiler lays out the frame loop, and the pruned kernel ran up to 2.6 % slower.  With
+// this body alone all six instantiations compile to the parent's instruction streams.)
+template <int LM, class Side>
+__device__ __forceinline__ void beam_start(Side& b, int C, int gstart, uint32_t* hist, unsigned long long* childmask,
+                                           int* path, int* s_nb, int* s_ndead) {
+  const int tid = threadIdx.x;
+  hist[tid] = 0u;
+  if (tid < kCtcBeamMaxWidth) {
+    childmask[tid] = 0ull;
+    path[tid] = -1;
+  }
+  if (tid == 0) {
+    b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
+    b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
+    if constexpr (LM == kBeamGraph) { b.g[0] = 0.f; b.ctx[0] = gstart; }
+    else if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
+    *s_nb = 1;
+    *s_ndead = 0;
+  }
 }
 
 // LM: the search with a dense n-gram table lm [C, O] (the contract: tfk_ctc_beam_lm in tfkaldi_hip.h).  A frame's table
@@ -683,20 +715,7 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   unsigned long long* tab = trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
   const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)O - 1u) / (unsigned)O);  // k / O for k < 2^13
 
-  hist[tid] = 0u;
-  if (tid < kCtcBeamMaxWidth) {
-    childmask[tid] = 0ull;
-    path[tid] = -1;
-  }
-  if (tid == 0) {  // the beam starts as {(): (0, -inf)}
-    Side& b = beam[0];
-    b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
-    b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
-    if constexpr (LM == kBeamGraph) { b.g[0] = 0.f; b.ctx[0] = gstart; }
-    else if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
-    s_nb = 1;
-    s_ndead = 0;
-  }
+  beam_start<LM>(beam[0], C, gstart, hist, childmask, path, &s_nb, &s_ndead);
   int cur = 0;
   double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
   float z_next = (wave == 0 && lane < O && Tn > 0) ? logits[(size_t)r0 * ld + lane] : 0.f;
@@ -937,6 +956,9 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
 // ctc_beam_kernel over nb * (K + 1) candidates: slot i's candidate q < K extends by the frame's q-th kept label, q == K stays.
 // It is a sibling, not a third instantiation of that body: a class there is a 6-bit column of lp[] / childmask / the trie key,
 // here a label is a position q in the frame's list plus a 16-bit class, and the existing code objects stay what they were.
+// The two share the __device__ helpers, the start of the beam (beam_start) and the bin scan of a radix pass (radix_pick_bin,
+// also the pre-pass's); the frame step and the epilogue are written in each, because every shared form of them that was
+// tried moved the compiled frame loop and the pruned kernel's time (the comment at beam_start).
 
 // ONE WAVE PER ROW (a block is one wave, so __syncthreads is a wave barrier).  The row is read from HBM once; the later
 // passes (sum, the radix passes, the compaction) find it in the cache.  For O <= 64 lane c holds class c and mx / se are formed
@@ -969,27 +991,9 @@ ctc_row_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, uint
       if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
-    {
-      const uint4 h = reinterpret_cast<const uint4*>(hist)[lane];  // bins 4 lane .. 4 lane + 3
-      const int s = (int)(h.x + h.y + h.z + h.w);
-      int incl = s;  // this lane's bins and every higher one
-      for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_down(incl, o);
-        if (lane + o < 64) incl += v;
-      }
-      int above = incl - s;
-      const uint32_t hv[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-      for (int q = 3; q >= 0; --q) {
-        const int c = (int)hv[q];
-        if (need > above && need <= above + c) {
-          sel[0] = 4 * lane + q;
-          sel[1] = need - above;
-        }
-        above += c;
-      }
-      reinterpret_cast<uint4*>(hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    // (the helper also leaves the bin's count in sel[2], one LDS store per pass that this kernel does not read: accepted, so
+    // that the scan is one function without a switch; sel has 4 entries)
+    radix_pick_bin(hist, sel, need, lane);
     __syncthreads();
     prefix |= (uint32_t)sel[0] << shift;
     need = sel[1];  // (the next pass writes sel behind its own barrier)
@@ -1084,20 +1088,7 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
   const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)K1 - 1u) / (unsigned)K1);  // k / K1 for k < 2^13
   const uint32_t* prow = pre + (size_t)r0 * kCtcTopkRowWords;
 
-  hist[tid] = 0u;
-  if (tid < kCtcBeamMaxWidth) {
-    childmask[tid] = 0ull;
-    path[tid] = -1;
-  }
-  if (tid == 0) {  // the beam starts as {(): (0, -inf)}
-    Side& b = beam[0];
-    b.pb[0] = 0.f; b.pnb[0] = NEG; b.tot[0] = 0.f;
-    b.node[0] = kBeamRoot; b.parent[0] = -2; b.last[0] = -1; b.len[0] = 0; b.src[0] = -1;
-    if constexpr (LM == kBeamGraph) { b.g[0] = 0.f; b.ctx[0] = gstart; }
-    else if constexpr (LM) { b.g[0] = 0.f; b.ctx[0] = C - 1; }  // every position before the start is the digit O - 1
-    s_nb = 1;
-    s_ndead = 0;
-  }
+  beam_start<LM>(beam[0], C, gstart, hist, childmask, path, &s_nb, &s_ndead);
   int cur = 0;
   double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
   // wave 0: the next frame's list, in registers until phase E; every thread: the next frame's lsum
@@ -2123,22 +2114,26 @@ int ctc_lm_contexts(int O, int order) {
   return C;
 }
 
+// which instantiation a search is, and the model arguments its kernel receives (no model: no table, one context)
+static int beam_kind(const CtcLm* lm) { return !lm ? kBeamAm : lm->next ? kBeamGraph : kBeamNgram; }
+static BeamModel beam_model(const CtcLm* lm, int O) {
+  if (!lm) return {nullptr, 1, 0.f, 0.f, 0, nullptr, 0};
+  if (lm->next) return {lm->table, lm->num_states, lm->weight, lm->bonus, (int)lm->eos, lm->next, lm->start};
+  return {lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus, (int)lm->eos, nullptr, 0};
+}
+
 void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
                      int top_paths, unsigned long long* trie, int32_t* hyp, int32_t* hyp_len, float* score, const CtcLm* lm,
                      float* am_score) {
   if (U <= 0) return;
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
-  if (lm && lm->next)
-    hipLaunchKernelGGL(ctc_beam_kernel<kBeamGraph>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths,
-                       trie, hyp, hyp_len, score, lm->table, lm->num_states, lm->weight, lm->bonus, (int)lm->eos, am_score,
-                       lm->next, lm->start);
-  else if (lm)
-    hipLaunchKernelGGL(ctc_beam_kernel<kBeamNgram>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths,
-                       trie, hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus, (int)lm->eos,
-                       am_score, (const int32_t*)nullptr, 0);
-  else
-    hipLaunchKernelGGL(ctc_beam_kernel<kBeamAm>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie,
-                       hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, (float*)nullptr, (const int32_t*)nullptr, 0);
+  const int kind = beam_kind(lm);
+  const BeamModel m = beam_model(lm, O);
+  // (am_score: NULL without a model, the value this launch has always passed; the acoustic kernel never reads the argument)
+  hipLaunchKernelGGL(kind == kBeamGraph ? ctc_beam_kernel<kBeamGraph>
+                     : kind == kBeamNgram ? ctc_beam_kernel<kBeamNgram> : ctc_beam_kernel<kBeamAm>,
+                     dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie, hyp, hyp_len, score,
+                     m.table, m.C, m.weight, m.bonus, m.eos, lm ? am_score : nullptr, m.next, m.start);
 }
 
 size_t ctc_beam_topk_scratch_words(int T) { return (size_t)(T > 0 ? T : 0) * kCtcTopkRowWords; }
@@ -2170,18 +2165,12 @@ void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int
   if (U <= 0) return;
   const int K = min(label_topk, O - 1);
   (void)hipMemsetAsync(trie, 0xff, ctc_beam_scratch_words(T, U, W) * sizeof(unsigned long long), s);
-  if (lm && lm->next)
-    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamGraph>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
-                       top_paths, trie, hyp, hyp_len, score, lm->table, lm->num_states, lm->weight, lm->bonus, (int)lm->eos,
-                       am_score, lm->next, lm->start);
-  else if (lm)
-    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamNgram>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
-                       top_paths, trie, hyp, hyp_len, score, lm->table, ctc_lm_contexts(O, lm->order), lm->weight, lm->bonus,
-                       (int)lm->eos, am_score, (const int32_t*)nullptr, 0);
-  else
-    hipLaunchKernelGGL(ctc_beam_topk_kernel<kBeamAm>, dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W,
-                       top_paths, trie, hyp, hyp_len, score, (const float*)nullptr, 1, 0.f, 0.f, 0, am_score,
-                       (const int32_t*)nullptr, 0);
+  const int kind = beam_kind(lm);
+  const BeamModel m = beam_model(lm, O);
+  hipLaunchKernelGGL(kind == kBeamGraph ? ctc_beam_topk_kernel<kBeamGraph>
+                     : kind == kBeamNgram ? ctc_beam_topk_kernel<kBeamNgram> : ctc_beam_topk_kernel<kBeamAm>,
+                     dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W, top_paths, trie, hyp, hyp_len,
+                     score, m.table, m.C, m.weight, m.bonus, m.eos, am_score, m.next, m.start);
 }
 
 // scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]
