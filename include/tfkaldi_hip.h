@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 18
+#define TFK_ABI_VERSION 19
 
 typedef struct tfk_engine tfk_engine;
 
@@ -512,6 +512,85 @@ int tfk_ctc_score_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T,
  * outside [0, O) is clamped). */
 int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                          const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off, float* score);
+/* (ABI 19) CTC ALIGNMENT WITH WILDCARD GAPS, and KEYWORD SPOTTING: a transcript that covers only part of a recording
+ * (untranscribed speech, music or noise before and after it, a missing stretch in the middle), a known phrase to be found in a
+ * long file, a list of keywords searched in a set of utterances.  torchaudio's forced_align has its "star" token for this; CTC
+ * segmentation (Kuerzinger et al. 2020) and CTC keyword spotting are the same lattice with free stretches.  This comment is the
+ * contract.
+ * Lattice.  For an utterance of Tn frames with logits z [Tn, O], labels l_0 ... l_{S-1} and gap flags w_0 ... w_S:
+ *   - States, classes and transitions are those of tfk_ctc_align: n = 2S + 1 states, start in state 0 or 1, end in n - 1 or
+ *     n - 2, steps of 0, 1 or 2; a step of 2 goes only into a label state whose label differs from the label two states back.
+ *   - Gap g is the even state 2g.  Gap 0 lies before the first label, gap S after the last.
+ * Emissions.
+ *   - Every label state emits z[t, class], as tfk_ctc_align does.
+ *   - A gap with w_g = 0 emits z[t, blank], as tfk_ctc_align does.
+ *   - A gap with w_g = 1 is a wildcard: it emits rowmax[t] = max_c z[t, c], the best class of the frame, blank included.
+ *   - A wildcard gap may therefore hold anything, including nothing where CTC lets the blank be skipped.  Between two equal
+ *     labels it still takes at least one frame.
+ * Result and tie rule.
+ *   - The result is the valid path that maximises the sum of emissions.
+ *   - The tie rule is word for word that of tfk_ctc_align: stay before +1 before +2, a later candidate wins only if it is
+ *     strictly larger, and at the end n - 1 wins unless n - 2 is strictly larger.
+ *   - The recursion runs on raw logits, re-centred on its maximum, with the sum of the shifts kept in double.
+ *   - The wildcard emission is the row maximum and not the row log-sum-exp.  Integer logits therefore still make every fp32
+ *     intermediate exact, the tie rule stays a testable function of the input, and the score is the log-probability of one
+ *     real frame labelling.
+ * Outputs.
+ *   - ali[T]: the position j of the label a frame emits; -1 for a frame in any gap, blank or wildcard; -2 on every row of an
+ *     utterance without a valid path.
+ *   - score[U]: sum_t (emission_t - logsumexp(z[t, :])); sums are kept in double and rounded to float once.  -inf without a path.
+ *   - free_score[U]: sum_t (rowmax[t] - logsumexp(z[t, :])), the log-probability of the unconstrained best path,
+ *     tfk_ctc_greedy's path (written for every utterance, with or without a path).  score <= free always; score - free is what
+ *     the pattern costs against saying whatever fits best; score - free = 0 means the pattern lies on the best path.
+ *   - No flag set (or wild == NULL): ali and score equal tfk_ctc_align's bit for bit.
+ *   - Zero-frame utterance: free 0, and score 0 if S == 0, else -inf.
+ *   - Errors are the same as tfk_ctc_align's, plus a NULL free_score and a wild value other than 0 or 1: the message names the
+ *     utterance and the gap.
+ * Layout of wild: uint8, S_u + 1 flags per utterance, back to back; utterance u's flags start at lab_off[u] + u (lab_off = the
+ * running sum of label_len).  NULL means all zero.
+ * Host pointers.  Evaluation mode; parameters, accumulators and statistics are not touched (same rules as tfk_ctc_greedy); the
+ * engine stays usable after every refused call.  flags: 0. */
+int tfk_ctc_align_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                       const int32_t* labels, const int32_t* label_len, const uint8_t* wild, int32_t* ali, float* score,
+                       float* free_score, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_align_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                           int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                           const uint8_t* wild, int32_t* ali, float* score, float* free_score, int flags);
+/* (ABI 19) Tests / tools: the alignment alone on logits [T, ld] of O classes, DEVICE pointers (wild included), tables as
+ * tfk_ctc_align_logits takes them; ali [T] (rows outside [seg[0], seg[U]) are not written), score [U], free_score [U].  Labels
+ * and flags are not validated (a label outside [0, O) is clamped, any non-zero flag is a wildcard). */
+int tfk_ctc_align_wild_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
+                              int32_t U, const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int32_t* ali,
+                              float* score, float* free_score);
+/* (ABI 19) KEYWORD SPOTTING: many patterns per utterance in ONE forward pass, in the pair layout of tfk_ctc_score: hyp_count[U]
+ * patterns of utterance u (>= 0, 0 allowed anywhere), P = their sum <= 2^20 = 1048576, pairs ordered by utterance, then by
+ * pattern; label_len[P] and labels back to back in pair order, at most 511 labels per pattern.  wild holds S_p + 1 flags per
+ * PAIR; pair p's flags start at lab_off[p] + p (NULL: all zero).
+ * score[P], start[P], end[P]: for every pair exactly what tfk_ctc_align_wild returns for that utterance and pattern -- score
+ * bit for bit, start = the first frame (counted inside the utterance) that emits a label and end = one past the last frame that
+ * emits a label, on the same path under the same tie rule.  S == 0: start = end = 0.  No path: score -inf, start = end = -1.
+ * free_score[U] as tfk_ctc_align_wild.  No back-pointers are stored (with 2^20 pairs they cannot be): the start frame travels
+ * with the state value through the recursion -- set when a path enters state 1 from state 0 or starts in state 1, otherwise
+ * inherited from the predecessor the tie rule picked -- and the end frame is read at state n - 1 (the frame at which it was
+ * entered from n - 2; Tn if the path ends in n - 2).  P == 0 is valid and writes only free_score.
+ * Errors (the engine stays usable): NULL pointers, T <= 0, a negative count or length, a pattern of more than 511 labels, a label
+ * outside [0, output_dim - 1), a wild value other than 0 or 1 (utterance, pattern, pair and gap are named), P > 1048576.  Host
+ * pointers.  Evaluation mode, as tfk_ctc_greedy.  flags: 0. */
+int tfk_ctc_spot(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                 const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float* score,
+                 int32_t* start, int32_t* end, float* free_score, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_posteriors_raw; flags 0 or TFK_RAW_DEVICE). */
+int tfk_ctc_spot_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                     int32_t context_width, const float* cmvn, const int32_t* hyp_count, const int32_t* labels,
+                     const int32_t* label_len, const uint8_t* wild, float* score, int32_t* start, int32_t* end,
+                     float* free_score, int flags);
+/* (ABI 19) Tests / tools: the search alone on logits [T, ld] of O classes, DEVICE pointers (wild included), tables as
+ * tfk_ctc_score_logits takes them (pair_utt[P], lab_off[P + 1]); score / start / end [P], free_score [U].  Labels and flags are
+ * not validated (a label outside [0, O) is clamped, any non-zero flag is a wildcard). */
+int tfk_ctc_spot_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
+                        const uint8_t* wild, float* score, int32_t* start, int32_t* end, float* free_score);
 /* (ABI 15) Training on the EXPECTED NUMBER OF LABEL ERRORS over an N-best list (MWER; Prabhavalkar et al. 2018, Shannon 2017)
  * instead of -- or on top of -- the CTC likelihood.  Train-mode forward of the flat utterance-major frames X [T, ldx] of U
  * utterances (utt_len[U], sum = T) as tfk_accumulate_ctc; ref_labels / ref_len[U] = the references, laid out as

@@ -144,6 +144,27 @@ const char* ctc_score_limits(int O, int T, int U, int P, int max_labels);
 void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
                const int32_t* pair_utt, int P, const int32_t* labels, const int32_t* lab_off, int max_labels, void* scratch,
                float* score);
+// Alignment with WILDCARD GAPS (the contract is the comment at tfk_ctc_align_wild in tfkaldi_hip.h): ctc_viterbi_align's
+// lattice, transitions and tie rule; gap g of an utterance (the even state 2g, g in [0, S]) whose flag
+// wild[lab_off[u] + u + g] is non-zero emits rowmax[t] = max_c z[t, c] instead of z[t, blank].  wild == NULL: no flag set,
+// and ali / score are ctc_viterbi_align's bit for bit.  ali: -1 for a frame in any gap.  free_score[u] =
+// sum_t (rowmax[t] - logsumexp(z[t, :])) in double, rounded once (0 for a zero-frame utterance; written for every utterance,
+// with or without a path).  scratch: ctc_align_wild_scratch_bytes(T, max_labels) bytes, 16-byte aligned.  Limits:
+// ctc_align_limits.
+size_t ctc_align_wild_scratch_bytes(int T, int max_labels);
+void ctc_viterbi_align_wild(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+                            const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int max_labels,
+                            void* scratch, int32_t* ali, float* score, float* free_score);
+// Keyword spotting (the contract is the comment at tfk_ctc_spot in tfkaldi_hip.h): for every (utterance, pattern) pair, laid
+// out as ctc_score's pairs, the score of ctc_viterbi_align_wild's path of that pattern on that utterance -- the same bits --
+// and its span: start[p] = the first frame that emits a label, end[p] = one past the last; S == 0: 0 and 0; no path: -inf, -1,
+// -1.  Nothing is stored per frame: the start frame travels with the state values.  The flags of pair p are
+// wild[lab_off[p] + p + g].  free_score [U] as above; P == 0 writes only that.  scratch: ctc_spot_scratch_bytes(T) bytes.
+// Limits: ctc_score_limits.
+size_t ctc_spot_scratch_bytes(int T);
+void ctc_spot(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, const int32_t* pair_utt,
+              int P, const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int max_labels, void* scratch,
+              float* score, int32_t* start, int32_t* end, float* free_score);
 // Expected label errors over an N-best list (MWER; Prabhavalkar et al. 2018) and their gradient w.r.t. the logits (the contract
 // is the comment at tfk_accumulate_ctc_mwer in tfkaldi_hip.h).  Per utterance u with hypotheses y_i (pairs ufirst[u] ..
 // ufirst[u + 1]), s_i = log p(y_i | z) as ctc_score defines it, e_i = their Levenshtein distance to the reference:

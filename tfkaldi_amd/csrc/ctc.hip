@@ -14,6 +14,10 @@
 //                    (ctc_row_lse supplies the rows' log-sum-exps for the score)
 //   ctc_score        N-best rescoring, ONE WAVE PER (utterance, hypothesis) PAIR: the forward sweep again, gathering the
 //                    logits itself as ctc_viterbi does and storing nothing per frame; out: log p(labels | x) per pair
+//   ctc_viterbi_wild alignment with WILDCARD GAPS, one wave per utterance: ctc_viterbi's twin whose flagged gap states emit
+//                    the row maximum (ctc_row_max_lse supplies it beside the log-sum-exp, ctc_free_score sums the two)
+//   ctc_spot         keyword spotting, ONE WAVE PER (utterance, pattern) PAIR: the same recursion storing nothing per frame,
+//                    the path's start frame travelling beside every state value; out: score, start, end per pair
 // Log space, fp32, with a large finite "minus infinity" so that no inf - inf can arise.
 #include "ctc.h"
 
@@ -1639,6 +1643,378 @@ ctc_score_kernel(const float* __restrict__ logits, int ld, int O, const int32_t*
   if (lane == 0) score[p] = log_z_rel > -1e29f ? (float)(off + (double)log_z_rel) : -INFINITY;
 }
 
+// ---- alignment with wildcard gaps and keyword spotting (the contract is stated in ctc.h and at tfk_ctc_align_wild) ----
+//
+// The lattice of ctc_viterbi_kernel with one change: a GAP (an even state) whose flag is set emits the frame's largest logit
+// instead of the blank's.  No transition, tie or shift changes, so these are twins of ctc_viterbi_kernel / ctc_score_kernel
+// with their own text: the tuned loops above stay as they are.
+
+// one wave per row: rowmax[t] = largest logit of row t, lse[t] = its log-sum-exp (the expression of ctc_row_lse_kernel)
+__global__ void __launch_bounds__(256)
+ctc_row_max_lse_kernel(const float* __restrict__ logits, int ld, int O, int T, float* __restrict__ rowmax,
+                       float* __restrict__ lse) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= T) return;
+  const float* z = logits + (size_t)row * ld;
+  float mx = -INFINITY;
+  for (int c = lane; c < O; c += 64) mx = fmaxf(mx, z[c]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float se = 0.f;
+  for (int c = lane; c < O; c += 64) se += expf(z[c] - mx);
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+  if (lane == 0) {
+    rowmax[row] = mx;
+    lse[row] = mx + logf(se);
+  }
+}
+
+// one wave per utterance: free[u] = sum_t (rowmax[t] - lse[t]) in double, the log-probability of the per-frame best path
+__global__ void __launch_bounds__(64)
+ctc_free_score_kernel(const int32_t* __restrict__ seg, const float* __restrict__ rowmax, const float* __restrict__ lse,
+                      float* __restrict__ free_score) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  double fs = 0.0;
+  for (int f = lane; f < Tn; f += 64) fs += (double)rowmax[r0 + f] - (double)lse[r0 + f];
+  for (int o = 32; o > 0; o >>= 1) fs += __shfl_xor(fs, o);
+  if (lane == 0) free_score[u] = (float)fs;
+}
+
+// the emission of a gap state: the row maximum where mask is all ones, the blank's logit where it is zero (v_bfi_b32)
+__device__ __forceinline__ float wild_pick(uint32_t mask, float rowmax, float blank) {
+  return __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, rowmax) & mask) | (__builtin_bit_cast(uint32_t, blank) & ~mask));
+}
+__device__ __forceinline__ int lane_prev_int(int v, int fill, int lane) {
+  const int r = __builtin_amdgcn_update_dpp(0, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+  return lane == 0 ? fill : r;
+}
+
+// ONE WAVE PER UTTERANCE: ctc_viterbi_kernel's two chains (the PFD ring, the re-centring, the 2-bit back-pointer units, the
+// LDS-staged back-trace) with the emission select, decided before the frame loop: a lane's states are R / 2 (gap, label)
+// couples; the ring holds per row the label states' logits, the blank's logit and the row maximum (both wave-uniform), and
+// a per-couple mask picks the gap's emission from those two.
+// wild: the flags of utterance u are wild[lab_off[u] + u + g], g in [0, S]; NULL: none set.
+template <int R>
+__global__ void __launch_bounds__(64)
+ctc_viterbi_wild_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg,
+                        const int32_t* __restrict__ labels, const int32_t* __restrict__ lab_off,
+                        const uint8_t* __restrict__ wild, const float* __restrict__ rowmax, const float* __restrict__ lse,
+                        unsigned char* __restrict__ bp, int32_t* __restrict__ ali, float* __restrict__ score) {
+  typedef typename BpUnit<R>::type Unit;
+  constexpr int kRowBytes = bp_row_bytes(R);
+  constexpr int NV = kRowBytes / 16;
+  __shared__ uint4 stage[64 * NV];
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int l0 = lab_off[u], S = lab_off[u + 1] - l0, n = 2 * S + 1;
+  if (Tn <= 0) {
+    if (lane == 0) score[u] = S == 0 ? 0.f : -INFINITY;
+    return;
+  }
+  const int s0 = lane * R;
+  const float* zu = logits + (size_t)r0 * ld;
+  const float* mu = rowmax + r0;
+  constexpr int H = R / 2;  // the lane's R states are H (gap, label) couples: s0 is even
+  int lo[H];        // class of the couple's label state
+  uint32_t wm[H];   // all ones where the couple's gap is a wildcard
+  bool skip_in[H];  // the label state may be entered by a step of 2
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    const int s = s0 + 2 * k, j = s >> 1;
+    const bool lab = s + 1 < n;
+    lo[k] = lab ? min(max(labels[l0 + j], 0), O - 1) : O - 1;  // (clamped: a bad label must not become a bad address)
+    wm[k] = (wild && s < n && wild[(size_t)l0 + u + j] != 0) ? ~0u : 0u;
+    skip_in[k] = lab && j >= 1 && labels[l0 + j] != labels[l0 + j - 1];
+  }
+  Unit* bpu = reinterpret_cast<Unit*>(bp + (size_t)r0 * kRowBytes) + lane;
+  constexpr int PFD = 8;
+  float pre[PFD][H], prb[PFD], prm[PFD];  // a row in flight: the label states' logits, the blank's, the row maximum
+  double off = 0.0;
+  float a[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) a[r] = NEG;
+  if (lane == 0) {
+    a[0] = wild_pick(wm[0], mu[0], zu[O - 1]);
+    if (n > 1) a[1] = zu[lo[0]];
+  }
+  bpu[0] = (Unit)0;
+#pragma unroll
+  for (int j = 0; j < PFD; ++j) {
+    const int row = min(1 + j, Tn - 1);
+    const float* zr = zu + (size_t)row * ld;
+    prb[j] = zr[O - 1];
+    prm[j] = mu[row];
+#pragma unroll
+    for (int k = 0; k < H; ++k) pre[j][k] = zr[lo[k]];
+  }
+  for (int t0 = 1; t0 < Tn; t0 += PFD) {
+#pragma unroll
+    for (int j = 0; j < PFD; ++j) {
+      const int t = t0 + j;
+      const bool live = t < Tn;
+      const int nrow = min(t + PFD, Tn - 1);
+      float cur[R];
+      {
+        const float* zr = zu + (size_t)nrow * ld;
+        const float cb = prb[j], cm = prm[j];
+        prb[j] = zr[O - 1];
+        prm[j] = mu[nrow];
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+          cur[2 * k] = wild_pick(wm[k], cm, cb);
+          cur[2 * k + 1] = pre[j][k];
+          pre[j][k] = zr[lo[k]];
+        }
+      }
+      const float up1 = lane_prev(a[R - 1], NEG, lane), up2 = lane_prev(a[R - 2], NEG, lane);
+      float na[R];
+      uint32_t code = 0u;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float p1 = r >= 1 ? a[r - 1] : up1;
+        const float p2 = r >= 2 ? a[r - 2] : (r == 1 ? up1 : up2);
+        float best = a[r];
+        uint32_t d = 0u;
+        if (p1 > best) { best = p1; d = 1u; }
+        if ((r & 1) && skip_in[r >> 1] && p2 > best) { best = p2; d = 2u; }
+        const float v = (s0 + r < n) ? best + cur[r] : NEG;
+        na[r] = live ? v : a[r];
+        code |= d << (2 * r);
+      }
+      if (j == PFD - 1) {  // compile-time: re-centre the state vector on its maximum
+        float m = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) m = fmaxf(m, na[r]);
+        m = wave_max(m);
+        if (live && m > -1e29f) {
+          off += (double)m;
+#pragma unroll
+          for (int r = 0; r < R; ++r) na[r] = fmaxf(na[r] - m, NEG);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) a[r] = na[r];
+      if (live) bpu[(size_t)t * (kRowBytes / sizeof(Unit))] = (Unit)code;
+    }
+  }
+  // the end state: n - 1 unless n - 2 is strictly larger
+  float e1 = -INFINITY, e2 = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (s0 + r == n - 1) e1 = a[r];
+    if (s0 + r == n - 2) e2 = a[r];
+  }
+  e1 = wave_max(e1);
+  e2 = wave_max(e2);
+  int s = e2 > e1 ? n - 2 : n - 1;
+  const float vend = fmaxf(e1, e2);
+  if (!(vend > -1e29f)) {  // too short for its labels: no path
+    for (int f = lane; f < Tn; f += 64) ali[r0 + f] = -2;
+    if (lane == 0) score[u] = -INFINITY;
+    return;
+  }
+  double ls = 0.0;
+  for (int f = lane; f < Tn; f += 64) ls += (double)lse[r0 + f];
+  for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+  if (lane == 0) score[u] = (float)((off + (double)vend) - ls);
+
+  __threadfence();  // the back-pointers this wave stored, read back by other lanes
+  const uint4* g = reinterpret_cast<const uint4*>(bp + (size_t)r0 * kRowBytes);
+  const int words = Tn * NV;
+  uint4 nxt[NV];
+  const int nblk = (Tn + 63) >> 6;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int w = (nblk - 1) * 64 * NV + i * 64 + lane;
+    nxt[i] = w < words ? g[w] : make_uint4(0u, 0u, 0u, 0u);
+  }
+  const uint32_t* rows = reinterpret_cast<const uint32_t*>(stage);
+  for (int b = nblk - 1; b >= 0; --b) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) stage[i * 64 + lane] = nxt[i];
+    if (b > 0) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) nxt[i] = g[(b - 1) * 64 * NV + i * 64 + lane];
+    }
+    __syncthreads();
+    const int f0 = 64 * b, cnt = min(64, Tn - f0);
+    int mine = 0;
+    for (int j = cnt - 1; j >= 0; --j) {
+      if (lane == j) mine = s;
+      const int bit = R == 2 ? 8 * (s >> 1) + 2 * (s & 1) : 2 * s;
+      const uint32_t w = rows[j * (kRowBytes / 4) + (bit >> 5)];
+      s = max(s - (int)((w >> (bit & 31)) & 3u), 0);
+    }
+    if (lane < cnt) ali[r0 + f0 + lane] = (mine & 1) ? mine >> 1 : -1;  // (a gap frame, blank or wildcard: -1)
+  }
+}
+
+// ONE WAVE PER (utterance, pattern) PAIR: the same max-plus recursion with nothing stored per frame, as ctc_score_kernel
+// stores nothing.  Beside every state value travels the START FRAME of the path that reaches it: set when the path enters
+// state 1 from state 0 (or starts there), inherited from the predecessor the tie rule picks, shifted between lanes as the
+// values are.  The end frame is read at state n - 1: a gap state keeps the frame at which it was last entered from the label
+// before it (a label state needs none: its path's last label frame is the current one).  The arithmetic
+// -- raw logits, the re-centring every PFD steps, the sums in double -- is ctc_viterbi_wild_kernel's expression for
+// expression, so score equals its score bit for bit and (start, end) are its path's.
+// wild: the flags of pair p are wild[lab_off[p] + p + g]; NULL: none set.
+template <int R>
+__global__ void __launch_bounds__(64)
+ctc_spot_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U,
+                const int32_t* __restrict__ pair_utt, const int32_t* __restrict__ labels,
+                const int32_t* __restrict__ lab_off, const uint8_t* __restrict__ wild, const float* __restrict__ rowmax,
+                const float* __restrict__ lse, float* __restrict__ score, int32_t* __restrict__ start,
+                int32_t* __restrict__ end) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int u = min(max(pair_utt[p], 0), U - 1);  // (clamped: a bad index must not become a bad address)
+  const int r0 = seg[u], Tn = seg[u + 1] - r0;
+  const int l0 = lab_off[p], S = lab_off[p + 1] - l0, n = 2 * S + 1;
+  if (Tn <= 0) {  // an utterance without frames: only the empty pattern has a path (the empty one)
+    if (lane == 0) {
+      score[p] = S == 0 ? 0.f : -INFINITY;
+      start[p] = end[p] = S == 0 ? 0 : -1;
+    }
+    return;
+  }
+  if (S < 0 || n > 64 * R) {  // not this launch's register tile (the launcher's max_labels rules it out)
+    if (lane == 0) {
+      score[p] = __builtin_nanf("");
+      start[p] = end[p] = -1;
+    }
+    return;
+  }
+  const int s0 = lane * R;
+  const float* zu = logits + (size_t)r0 * ld;
+  const float* mu = rowmax + r0;
+  constexpr int H = R / 2;  // the lane's R states are H (gap, label) couples: s0 is even
+  int lo[H];        // class of the couple's label state
+  uint32_t wm[H];   // all ones where the couple's gap is a wildcard
+  bool skip_in[H];  // the label state may be entered by a step of 2
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    const int s = s0 + 2 * k, j = s >> 1;
+    const bool lab = s + 1 < n;
+    lo[k] = lab ? min(max(labels[l0 + j], 0), O - 1) : O - 1;  // (clamped: a bad label must not become a bad address)
+    wm[k] = (wild && s < n && wild[(size_t)l0 + p + j] != 0) ? ~0u : 0u;
+    skip_in[k] = lab && j >= 1 && labels[l0 + j] != labels[l0 + j - 1];
+  }
+  constexpr int PFD = 8;
+  float pre[PFD][H], prb[PFD], prm[PFD];
+  double off = 0.0;
+  float a[R];
+  int st[R];  // start frame of the best path into the state (state 0: unused)
+  int en[H];  // per gap state: one past the last label frame of the best path into it = the frame it was entered at
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    a[r] = NEG;
+    st[r] = 0;
+    en[r >> 1] = 0;
+  }
+  if (lane == 0) {
+    a[0] = wild_pick(wm[0], mu[0], zu[O - 1]);
+    if (n > 1) a[1] = zu[lo[0]];
+  }
+#pragma unroll
+  for (int j = 0; j < PFD; ++j) {
+    const int row = min(1 + j, Tn - 1);
+    const float* zr = zu + (size_t)row * ld;
+    prb[j] = zr[O - 1];
+    prm[j] = mu[row];
+#pragma unroll
+    for (int k = 0; k < H; ++k) pre[j][k] = zr[lo[k]];
+  }
+  for (int t0 = 1; t0 < Tn; t0 += PFD) {
+#pragma unroll
+    for (int j = 0; j < PFD; ++j) {
+      const int t = t0 + j;
+      const bool live = t < Tn;
+      const int nrow = min(t + PFD, Tn - 1);
+      float cur[R];
+      {
+        const float* zr = zu + (size_t)nrow * ld;
+        const float cb = prb[j], cm = prm[j];
+        prb[j] = zr[O - 1];
+        prm[j] = mu[nrow];
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+          cur[2 * k] = wild_pick(wm[k], cm, cb);
+          cur[2 * k + 1] = pre[j][k];
+          pre[j][k] = zr[lo[k]];
+        }
+      }
+      const float up1 = lane_prev(a[R - 1], NEG, lane), up2 = lane_prev(a[R - 2], NEG, lane);
+      const int us1 = lane_prev_int(st[R - 1], 0, lane), us2 = lane_prev_int(st[R - 2], 0, lane);
+      float na[R];
+      int ns[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float p1 = r >= 1 ? a[r - 1] : up1;
+        const float p2 = r >= 2 ? a[r - 2] : (r == 1 ? up1 : up2);
+        const int q1 = r == 1 ? (lane == 0 ? t : st[0]) : (r >= 1 ? st[r - 1] : us1);  // state 0 -> 1: the path starts here
+        const int q2 = r >= 2 ? st[r - 2] : (r == 1 ? us1 : us2);
+        float best = a[r];
+        int bs = st[r];
+        bool from1 = false;
+        if (p1 > best) { best = p1; bs = q1; from1 = true; }
+        if ((r & 1) && skip_in[r >> 1] && p2 > best) { best = p2; bs = q2; from1 = false; }
+        const float v = (s0 + r < n) ? best + cur[r] : NEG;
+        na[r] = live ? v : a[r];
+        ns[r] = live ? bs : st[r];
+        if (!(r & 1) && live && from1) en[r >> 1] = t;  // (a gap is entered from the label before it, whose last frame is t - 1)
+      }
+      if (j == PFD - 1) {  // compile-time: re-centre the state vector on its maximum
+        float m = NEG;
+#pragma unroll
+        for (int r = 0; r < R; ++r) m = fmaxf(m, na[r]);
+        m = wave_max(m);
+        if (live && m > -1e29f) {
+          off += (double)m;
+#pragma unroll
+          for (int r = 0; r < R; ++r) na[r] = fmaxf(na[r] - m, NEG);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        a[r] = na[r];
+        st[r] = ns[r];
+      }
+    }
+  }
+  // the end state: n - 1 unless n - 2 is strictly larger
+  float e1 = -INFINITY, e2 = -INFINITY;
+  int b1 = -1, b2 = -1, f1 = -1;  // start frames of n - 1 / n - 2, end frame of n - 1: from the lanes that own them
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (s0 + r == n - 1) { e1 = a[r]; b1 = st[r]; f1 = en[r >> 1]; }
+    if (s0 + r == n - 2) { e2 = a[r]; b2 = st[r]; }
+  }
+  e1 = wave_max(e1);
+  e2 = wave_max(e2);
+  for (int o = 32; o > 0; o >>= 1) {
+    b1 = max(b1, __shfl_xor(b1, o));
+    b2 = max(b2, __shfl_xor(b2, o));
+    f1 = max(f1, __shfl_xor(f1, o));
+  }
+  const bool last_label = e2 > e1;
+  const float vend = fmaxf(e1, e2);
+  if (!(vend > -1e29f)) {  // too short for its labels: no path
+    if (lane == 0) {
+      score[p] = -INFINITY;
+      start[p] = end[p] = -1;
+    }
+    return;
+  }
+  double ls = 0.0;
+  for (int f = lane; f < Tn; f += 64) ls += (double)lse[r0 + f];
+  for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+  if (lane == 0) {
+    score[p] = (float)((off + (double)vend) - ls);
+    start[p] = S == 0 ? 0 : (last_label ? b2 : b1);
+    end[p] = S == 0 ? 0 : (last_label ? Tn : f1);
+  }
+}
+
 // ---- expected label errors over an N-best list (MWER; the contract is stated in ctc.h and at tfk_accumulate_ctc_mwer) ----
 //
 // Every (utterance, hypothesis) pair -- and, under ctc_weight > 0, every (utterance, reference) -- is one "utterance" of a
@@ -2227,6 +2603,60 @@ void ctc_score(hipStream_t s, const float* logits, int ld, int O, int T, const i
     case 8: hipLaunchKernelGGL(ctc_score_kernel<8>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
     default: hipLaunchKernelGGL(ctc_score_kernel<16>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, lse, score); break;
   }
+}
+
+// scratch of ctc_viterbi_align_wild: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats | row maxima T floats]
+size_t ctc_align_wild_scratch_bytes(int T, int max_labels) {
+  return (size_t)(T > 0 ? T : 0) * ((size_t)bp_row_bytes(regs_for(max_labels)) + 2 * sizeof(float));
+}
+
+void ctc_viterbi_align_wild(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U,
+                            const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int max_labels,
+                            void* scratch, int32_t* ali, float* score, float* free_score) {
+  if (U <= 0) return;
+  const int R = regs_for(max_labels);
+  const size_t rows = (size_t)(T > 0 ? T : 0);
+  unsigned char* bp = static_cast<unsigned char*>(scratch);
+  float* lse = reinterpret_cast<float*>(bp + rows * bp_row_bytes(R));
+  float* mx = lse + rows;
+  if (T > 0)
+    hipLaunchKernelGGL(ctc_row_max_lse_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, mx, lse);
+  hipLaunchKernelGGL(ctc_free_score_kernel, dim3(U), dim3(64), 0, s, seg, mx, lse, free_score);
+#define TFK_WILD(RR) \
+  hipLaunchKernelGGL(ctc_viterbi_wild_kernel<RR>, dim3(U), dim3(64), 0, s, logits, ld, O, seg, labels, lab_off, wild, mx, lse, \
+                     bp, ali, score)
+  switch (R) {
+    case 2: TFK_WILD(2); break;
+    case 4: TFK_WILD(4); break;
+    case 8: TFK_WILD(8); break;
+    default: TFK_WILD(16); break;
+  }
+#undef TFK_WILD
+}
+
+// scratch of ctc_spot: [row log-sum-exps T floats | row maxima T floats]
+size_t ctc_spot_scratch_bytes(int T) { return (size_t)(T > 0 ? T : 0) * 2 * sizeof(float); }
+
+void ctc_spot(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, const int32_t* pair_utt,
+              int P, const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int max_labels, void* scratch,
+              float* score, int32_t* start, int32_t* end, float* free_score) {
+  if (U <= 0) return;
+  float* lse = static_cast<float*>(scratch);
+  float* mx = lse + (size_t)(T > 0 ? T : 0);
+  if (T > 0)
+    hipLaunchKernelGGL(ctc_row_max_lse_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, logits, ld, O, T, mx, lse);
+  hipLaunchKernelGGL(ctc_free_score_kernel, dim3(U), dim3(64), 0, s, seg, mx, lse, free_score);
+  if (P <= 0) return;
+#define TFK_SPOT(RR) \
+  hipLaunchKernelGGL(ctc_spot_kernel<RR>, dim3(P), dim3(64), 0, s, logits, ld, O, seg, U, pair_utt, labels, lab_off, wild, mx, \
+                     lse, score, start, end)
+  switch (regs_for(max_labels)) {
+    case 2: TFK_SPOT(2); break;
+    case 4: TFK_SPOT(4); break;
+    case 8: TFK_SPOT(8); break;
+    default: TFK_SPOT(16); break;
+  }
+#undef TFK_SPOT
 }
 
 const char* ctc_mwer_limits(int O, int64_t ld, int T, int U, int P, int max_labels, int64_t PR) {

@@ -68,7 +68,7 @@ enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
   KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
   KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_CTC_MWER_SWEEP, KF_CTC_MWER_WEIGHTS, KF_CTC_MWER_GRAD,
-  KF_CTC_DEN_SWEEP, KF_CTC_DEN_GRAD, KF_COUNT
+  KF_CTC_DEN_SWEEP, KF_CTC_DEN_GRAD, KF_CTC_ALIGN_WILD, KF_CTC_SPOT, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
@@ -78,7 +78,8 @@ const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)
                                      "ctc_beam_search",         "ctc_align",        "ctc_beam_search_lm",
                                      "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score",
                                      "ctc_mwer_sweep",          "ctc_mwer_weights", "ctc_mwer_grad",
-                                     "ctc_den_sweep",           "ctc_den_grad"};
+                                     "ctc_den_sweep",           "ctc_den_grad",     "ctc_align_wild",
+                                     "ctc_spot"};
 
 struct ProfRec {
   int family;
@@ -3656,6 +3657,253 @@ int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t 
   const size_t bytes = ctc_score_scratch_bytes(T);
   HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
   ctc_score((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, max_labels, scratch, score);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+// The small tables of tfk_ctc_align_wild / tfk_ctc_spot in e->ctc_pair: [tab `words` words | labels `total` words | flags
+// `nflags` bytes], through the pinned staging of tfk_ctc_score's pair tables (guarded by its own event).
+static int stage_pair_tables(tfk_engine* e, const int32_t* tab, size_t words, const int32_t* labels, size_t total,
+                             const uint8_t* flags, size_t nflags) {
+  const size_t flag_words = (nflags + 3) / 4, all = words + total + flag_words;
+  CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, all > 0 ? all : 1));
+  if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
+  CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, all, /*slack=*/true, /*sync=*/false));
+  if (words > 0) memcpy(e->h_pair, tab, words * sizeof(int32_t));
+  if (total > 0) memcpy(e->h_pair + words, labels, total * sizeof(int32_t));
+  if (flag_words > 0) {
+    e->h_pair[all - 1] = 0;
+    memcpy(e->h_pair + words + total, flags, nflags);
+  }
+  if (all > 0) HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, all * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
+  return 0;
+}
+// Alignment with wildcard gaps (the contract: tfkaldi_hip.h at tfk_ctc_align_wild): ctc_align_impl's recipe -- its checks, the
+// evaluation-mode forward, ctc_viterbi_align_wild on the logits in HBM -- plus the flags, which are checked here (the
+// utterance and the gap are named) and staged as the pair tables of tfk_ctc_score are; T + 2U words go back to the host.
+static int ctc_align_wild_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                               const int32_t* labels, const int32_t* label_len, const uint8_t* wild, int32_t* ali,
+                               float* score, float* free_score, int flags, const RawSpec* raw) {
+  CHK(decode_args(e, "tfk_ctc_align_wild", X, T, flags, raw));
+  if (!ali || !score || !free_score) return fail(-1, "ali / score / free_score is NULL");
+  if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC align: utt_len / label_len is NULL or no utterances");
+  size_t nflags = 0;
+  {
+    int64_t first = 0;
+    for (int u = 0; u < U; ++u) {
+      const int32_t n = label_len[u];
+      if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
+      if (n > kCtcMaxLabels) return fail(-1, "CTC align: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
+      if (n > 0 && !labels) return fail(-1, "CTC align: labels is NULL");
+      for (int32_t i = 0; i < n; ++i)
+        if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
+          return fail(-1, "CTC align: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
+      if (wild)
+        for (int32_t g = 0; g <= n; ++g)
+          if (wild[first + u + g] > 1)
+            return fail(-1, "CTC align: utterance %d, gap %d: wild is %d, not 0 or 1", u, g, (int)wild[first + u + g]);
+      first += n;
+    }
+    nflags = wild ? (size_t)first + (size_t)U : 0;
+  }
+  const size_t back = (size_t)T + 2 * (size_t)U;  // [ali | score | free]
+  int max_labels = 0;
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, labels, label_len}, true, back, 0, back, &max_labels, [&]() -> int {
+    if (const char* why = ctc_align_limits(e->O, T, U, max_labels)) return fail(-1, "CTC align (T %d, U %d): %s", T, U, why);
+    CHK(grow(e, &e->ctc_bp, &e->ctc_cap_bp, ctc_align_wild_scratch_bytes(T, max_labels)));
+    return wild ? stage_pair_tables(e, nullptr, 0, nullptr, 0, wild, nflags) : 0;
+  }, [&] {
+    ProfScope ps(e, KF_CTC_ALIGN_WILD, 0,
+                 4.0 * T * e->O + 2.0 * (double)ctc_align_wild_scratch_bytes(T, max_labels) + 4.0 * T + (double)nflags);
+    ctc_viterbi_align_wild(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, e->ctc_lab, e->ctc_lab_off,
+                           wild ? reinterpret_cast<const uint8_t*>(e->ctc_pair) : nullptr, max_labels, e->ctc_bp, e->ctc_dec,
+                           reinterpret_cast<float*>(e->ctc_dec + T), reinterpret_cast<float*>(e->ctc_dec + T + U));
+  }));
+  memcpy(ali, e->h_dec, (size_t)T * sizeof(int32_t));
+  memcpy(score, e->h_dec + T, (size_t)U * sizeof(float));
+  memcpy(free_score, e->h_dec + T + U, (size_t)U * sizeof(float));
+  return 0;
+}
+
+int tfk_ctc_align_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                       const int32_t* labels, const int32_t* label_len, const uint8_t* wild, int32_t* ali, float* score,
+                       float* free_score, int flags) {
+  return ctc_align_wild_impl(e, X, ldx, T, utt_len, U, labels, label_len, wild, ali, score, free_score, flags, nullptr);
+}
+int tfk_ctc_align_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                           int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                           const uint8_t* wild, int32_t* ali, float* score, float* free_score, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_align_wild_impl(e, raw, ldraw, T, utt_len, U, labels, label_len, wild, ali, score, free_score, flags, &r);
+}
+int tfk_ctc_align_wild_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
+                              int32_t U, const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int32_t* ali,
+                              float* score, float* free_score) {
+  if (U < 0) return fail(-1, "U = %d < 0", U);
+  if (U == 0) return 0;
+  if (!seg || !lab_off || !score || !free_score || (T > 0 && (!logits || !ali)))
+    return fail(-1, "logits / seg / lab_off / ali / score / free_score is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  std::vector<int32_t> h(2 * ((size_t)U + 1));  // (the two offset tables come back first, as tfk_ctc_align_logits)
+  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  int max_labels = 0;
+  for (int u = 0; u < U; ++u) {
+    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
+    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
+    max_labels = n > max_labels ? n : max_labels;
+  }
+  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC align: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
+  if (h[U + 1] < 0) return fail(-1, "CTC align: lab_off[0] = %d < 0", h[U + 1]);
+  if (const char* why = ctc_align_limits(O, T, U, max_labels)) return fail(-1, "CTC align (O %d, T %d, U %d): %s", O, T, U, why);
+  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC align: labels is NULL");
+  void* scratch = nullptr;  // the call's own scratch, released in stream order
+  const size_t bytes = ctc_align_wild_scratch_bytes(T, max_labels);
+  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
+  ctc_viterbi_align_wild((hipStream_t)stream, logits, (int)ld, O, T, seg, U, labels, lab_off, wild, max_labels, scratch, ali,
+                         score, free_score);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+// Keyword spotting (the contract: tfkaldi_hip.h at tfk_ctc_spot): ctc_score_impl's recipe -- the pair tables built and checked
+// on the host, staged behind the forward's own tables -- with the flags behind the labels; 3P + U words go back to the host.
+static int ctc_spot_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                         const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const uint8_t* wild,
+                         float* score, int32_t* start, int32_t* end, float* free_score, int flags, const RawSpec* raw) {
+  CHK(decode_args(e, "tfk_ctc_spot", X, T, flags, raw));
+  if (U <= 0 || !utt_len || !hyp_count) return fail(-1, "CTC spot: utt_len / hyp_count is NULL or no utterances");
+  if (!free_score) return fail(-1, "CTC spot: free_score is NULL");
+  int64_t P64 = 0;
+  for (int u = 0; u < U; ++u) {
+    if (hyp_count[u] < 0) return fail(-1, "CTC spot: utterance %d has a negative pattern count", u);
+    if (utt_len[u] < 0) return fail(-1, "CTC spot: utterance %d has a negative length", u);
+    P64 += hyp_count[u];
+    if (P64 > kCtcScoreMaxPairs) return fail(-1, "CTC spot: more than %d (utterance, pattern) pairs in one call", kCtcScoreMaxPairs);
+  }
+  const int P = (int)P64;
+  if (P > 0 && (!label_len || !score || !start || !end)) return fail(-1, "CTC spot: label_len / score / start / end is NULL");
+  std::vector<int32_t> tab(2 * (size_t)P + 1);  // [pair_utt | lab_off]
+  int32_t* pair_utt = tab.data();
+  int32_t* lab_off = pair_utt + P;
+  int max_pat = 0;
+  {
+    int p = 0;
+    int64_t first = 0;
+    lab_off[0] = 0;
+    for (int u = 0; u < U; ++u)
+      for (int k = 0; k < hyp_count[u]; ++k, ++p) {
+        const int32_t n = label_len[p];
+        if (n < 0) return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d) has a negative length", u, k, p);
+        if (n > kCtcMaxLabels)
+          return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d) has %d labels (limit %d)", u, k, p, n, kCtcMaxLabels);
+        if (n > 0 && !labels) return fail(-1, "CTC spot: labels is NULL");
+        for (int32_t i = 0; i < n; ++i)
+          if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
+            return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d): label %d outside [0, %d)", u, k, p,
+                        labels[first + i], e->O - 1);
+        if (wild)
+          for (int32_t g = 0; g <= n; ++g)
+            if (wild[first + p + g] > 1)
+              return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d), gap %d: wild is %d, not 0 or 1", u, k, p, g,
+                          (int)wild[first + p + g]);
+        first += n;
+        if (first > 0x7fffffff - kCtcScoreMaxPairs) return fail(-1, "CTC spot: too many labels in one call");
+        pair_utt[p] = u;
+        lab_off[p + 1] = (int32_t)first;
+        max_pat = n > max_pat ? n : max_pat;
+      }
+  }
+  if (const char* why = ctc_score_limits(e->O, T, U, P, max_pat)) return fail(-1, "CTC spot (T %d, U %d, P %d): %s", T, U, P, why);
+  const size_t total = (size_t)lab_off[P], tab_words = 2 * (size_t)P + 1, nflags = wild ? total + (size_t)P : 0;
+  const size_t back = 3 * (size_t)P + (size_t)U;  // [score | start | end | free]
+  int unused = 0;
+  CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, nullptr, nullptr}, false, back, 0, back, &unused, [&]() -> int {
+    CHK(grow(e, &e->ctc_sc, &e->ctc_cap_sc, ctc_spot_scratch_bytes(T)));
+    return stage_pair_tables(e, tab.data(), tab_words, labels, total, wild, nflags);
+  }, [&] {
+    const int32_t* d_utt = e->ctc_pair;
+    const int32_t* d_off = d_utt + P;
+    const int32_t* d_lab = e->ctc_pair + tab_words;
+    const uint8_t* d_wild = wild ? reinterpret_cast<const uint8_t*>(d_lab + total) : nullptr;
+    // (the rows are read once per pair, mostly from the cache: the waves of an utterance's patterns share them)
+    ProfScope ps(e, KF_CTC_SPOT, 0, 4.0 * T * e->O + 16.0 * T + 4.0 * (double)total + (double)nflags + 12.0 * P + 4.0 * U);
+    ctc_spot(e->stream, e->logits, e->ldO, e->O, T, e->ctc_seg, U, d_utt, P, d_lab, d_off, d_wild, max_pat, e->ctc_sc,
+             reinterpret_cast<float*>(e->ctc_dec), e->ctc_dec + P, e->ctc_dec + 2 * (size_t)P,
+             reinterpret_cast<float*>(e->ctc_dec + 3 * (size_t)P));
+  }));
+  if (P > 0) {
+    memcpy(score, e->h_dec, (size_t)P * sizeof(float));
+    memcpy(start, e->h_dec + P, (size_t)P * sizeof(int32_t));
+    memcpy(end, e->h_dec + 2 * (size_t)P, (size_t)P * sizeof(int32_t));
+  }
+  memcpy(free_score, e->h_dec + 3 * (size_t)P, (size_t)U * sizeof(float));
+  return 0;
+}
+
+int tfk_ctc_spot(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                 const int32_t* hyp_count, const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float* score,
+                 int32_t* start, int32_t* end, float* free_score, int flags) {
+  return ctc_spot_impl(e, X, ldx, T, utt_len, U, hyp_count, labels, label_len, wild, score, start, end, free_score, flags,
+                       nullptr);
+}
+int tfk_ctc_spot_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                     int32_t context_width, const float* cmvn, const int32_t* hyp_count, const int32_t* labels,
+                     const int32_t* label_len, const uint8_t* wild, float* score, int32_t* start, int32_t* end,
+                     float* free_score, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_spot_impl(e, raw, ldraw, T, utt_len, U, hyp_count, labels, label_len, wild, score, start, end, free_score, flags,
+                       &r);
+}
+int tfk_ctc_spot_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
+                        const uint8_t* wild, float* score, int32_t* start, int32_t* end, float* free_score) {
+  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
+  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC spot: more than %d (utterance, pattern) pairs in one call", kCtcScoreMaxPairs);
+  if (U == 0) return P == 0 ? 0 : fail(-1, "CTC spot: %d pairs and no utterance", P);
+  if (!seg || !free_score || (T > 0 && !logits)) return fail(-1, "logits / seg / free_score is NULL");
+  if (P > 0 && (!pair_utt || !lab_off || !score || !start || !end))
+    return fail(-1, "pair_utt / lab_off / score / start / end is NULL");
+  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  // the small tables come back first (one synchronisation), as tfk_ctc_score_logits
+  std::vector<int32_t> h((size_t)U + 1 + 2 * (size_t)P + 1, 0);
+  int32_t* h_utt = h.data() + U + 1;
+  int32_t* h_off = h_utt + P;
+  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  if (P > 0) {
+    HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  }
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int u = 0; u < U; ++u)
+    if (h[u + 1] < h[u]) return fail(-1, "CTC spot: utterance %d has a negative length", u);
+  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC spot: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
+  int max_labels = 0;
+  for (int p = 0; p < P; ++p) {
+    const int32_t n = h_off[p + 1] - h_off[p];
+    if (n < 0) return fail(-1, "CTC spot: pair %d has a negative length", p);
+    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC spot: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
+    max_labels = n > max_labels ? n : max_labels;
+  }
+  if (h_off[0] < 0) return fail(-1, "CTC spot: lab_off[0] = %d < 0", h_off[0]);
+  if (const char* why = ctc_score_limits(O, T, U, P, max_labels))
+    return fail(-1, "CTC spot (O %d, T %d, U %d, P %d): %s", O, T, U, P, why);
+  if (h_off[P] > h_off[0] && !labels) return fail(-1, "CTC spot: labels is NULL");
+  void* scratch = nullptr;  // the call's own scratch, released in stream order
+  const size_t bytes = ctc_spot_scratch_bytes(T);
+  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
+  ctc_spot((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, wild, max_labels, scratch, score,
+           start, end, free_score);
   const hipError_t launched = hipGetLastError();
   const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
   HIPCHK(launched);

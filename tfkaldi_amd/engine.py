@@ -601,6 +601,93 @@ class Engine(object):
         return self._score(self.lib.tfk_ctc_score_raw, raw, utt_lens, hyp_counts, labels, label_lens, ref_labels, ref_lens,
                            raw=(context_width, cmvn))
 
+    # ---- CTC alignment with wildcard gaps and keyword spotting: gap states that may emit the frame's best class ----
+    @staticmethod
+    def _wild(wild, label_lens, what):
+        """the flags of tfk_ctc_align_wild / tfk_ctc_spot: None, or uint8 with label_lens[i] + 1 values per sequence"""
+        if wild is None:
+            return None
+        wild = np.ascontiguousarray(wild).reshape(-1)
+        if wild.dtype == np.bool_:
+            wild = wild.astype(np.uint8)
+        if wild.dtype != np.uint8:
+            raise ValueError("%s: wild is %s, expected uint8 or bool" % (what, wild.dtype))
+        need = int(label_lens.sum(dtype=np.int64)) + label_lens.size
+        if wild.size != need:
+            raise ValueError("%s: %d gap flags for %d sequences of %d labels (one more than labels each: %d)"
+                             % (what, wild.size, label_lens.size, need - label_lens.size, need))
+        return wild
+
+    def _align_wild(self, fn, frames, utt_lens, labels, label_lens, wild, raw=None):
+        utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, False, "alignment")
+        wild = self._wild(wild, label_lens, "alignment")
+
+        def outputs(rows, U):  # (wild rides in front: an array the entry reads.  No frames: as _align, and free = 0)
+            score = np.empty(U, dtype=np.float32) if rows else np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32)
+            return wild, np.empty(rows, dtype=np.int32), score, np.zeros(U, dtype=np.float32)
+
+        def result(lens, _, ali, score, free):
+            starts = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            return [ali[s:s + n].copy() if sc > -np.inf else None for s, n, sc in zip(starts, lens, score)], score, free
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, raw=raw)
+
+    def ctc_align_wild(self, X, utt_lens, labels, label_lens, wild=None):
+        """ctc_align with WILDCARD GAPS (tfk_ctc_align_wild; the contract is stated in include/tfkaldi_hip.h): `wild` holds
+        label_lens[u] + 1 flags per utterance, back to back (uint8 or bool; None: none set) -- flag g of an utterance lets
+        the gap before label g (gap S: after the last label) emit the frame's best class instead of the blank, so that
+        stretch may hold anything.  Returns (alis, scores, free): as ctc_align (-1 for a frame in any gap), and free float32
+        [U], the log-probability of the unconstrained best path; scores <= free, and scores - free is what the pattern costs."""
+        return self._align_wild(self.lib.tfk_ctc_align_wild, X, utt_lens, labels, label_lens, wild)
+
+    def ctc_align_wild_raw(self, raw, utt_lens, context_width, labels, label_lens, wild=None, cmvn=None):
+        """ctc_align_wild on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        return self._align_wild(self.lib.tfk_ctc_align_wild_raw, raw, utt_lens, labels, label_lens, wild,
+                                raw=(context_width, cmvn))
+
+    def _spot(self, fn, frames, utt_lens, pat_counts, labels, label_lens, wild, raw=None):
+        utt_lens = self._refs(utt_lens, None, None, True, "patterns")[0]
+        pat_counts = np.ascontiguousarray(pat_counts, dtype=np.int32).reshape(-1)
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        label_lens = np.ascontiguousarray(label_lens, dtype=np.int32).reshape(-1)
+        if pat_counts.size != utt_lens.size or np.any(pat_counts < 0):
+            raise ValueError("patterns: %d counts (smallest %d) for %d utterances"
+                             % (pat_counts.size, int(pat_counts.min()) if pat_counts.size else 0, utt_lens.size))
+        P = int(pat_counts.sum(dtype=np.int64))
+        if label_lens.size != P or np.any(label_lens < 0) or int(label_lens.sum(dtype=np.int64)) != labels.size:
+            raise ValueError("patterns: %d label counts (sum %d) for %d pairs and %d labels"
+                             % (label_lens.size, int(label_lens.sum(dtype=np.int64)), P, labels.size))
+        wild = self._wild(wild, label_lens, "patterns")
+        cuts = np.cumsum(pat_counts, dtype=np.int64)[:-1]
+
+        def outputs(rows, U):  # (no frames: only the empty pattern has a path, the empty one)
+            if rows:
+                return (wild, np.empty(P, dtype=np.float32), np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32),
+                        np.empty(U, dtype=np.float32))
+            span = np.where(label_lens == 0, 0, -1).astype(np.int32)
+            return (wild, np.where(label_lens == 0, 0.0, -np.inf).astype(np.float32), span, span.copy(),
+                    np.zeros(U, dtype=np.float32))
+
+        def result(lens, _, score, start, end, free):
+            return np.split(score, cuts), np.split(start, cuts), np.split(end, cuts), free
+        return self._decode(fn, frames, utt_lens, (labels, label_lens), outputs, result, (_ptr(pat_counts),), raw)
+
+    def ctc_spot(self, X, utt_lens, pat_counts, labels, label_lens, wild=None):
+        """Keyword spotting over the utterances X [sum(utt_lens), F] (tfk_ctc_spot; the contract is stated in
+        include/tfkaldi_hip.h): pat_counts[u] patterns per utterance (0 is allowed), labels back to back in pair order (by
+        utterance, then by pattern), label_lens per pair, at most 511 labels each; `wild` label_lens[p] + 1 flags per PAIR, as
+        ctc_align_wild takes them per utterance.  Returns (scores, starts, ends, free): per utterance a float32 array of its
+        patterns' scores and int32 arrays of the first frame that emits a label and one past the last -- for every pair what
+        ctc_align_wild gives for that utterance and pattern (-inf, -1, -1 without a path; 0, 0 for an empty pattern) -- and
+        free float32 [U]."""
+        return self._spot(self.lib.tfk_ctc_spot, X, utt_lens, pat_counts, labels, label_lens, wild)
+
+    def ctc_spot_raw(self, raw, utt_lens, context_width, pat_counts, labels, label_lens, wild=None, cmvn=None):
+        """ctc_spot on UNSPLICED frames (CMVN + splice on the device, as posteriors_raw); `raw` may be a float32 CUDA
+        tensor (TFK_RAW_DEVICE)"""
+        return self._spot(self.lib.tfk_ctc_spot_raw, raw, utt_lens, pat_counts, labels, label_lens, wild,
+                          raw=(context_width, cmvn))
+
     # ---- CTC loss (SURVEY 8f-4): frames [T, F] of U utterances + their label sequences ----
     def _ctc_args(self, X, utt_lens, labels, label_lens):
         X = _f32(X)

@@ -182,6 +182,64 @@ class Decoder(object):
         targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
         return self._ctc("ctc_align", utterances, np.concatenate(targets), [t.size for t in targets])
 
+    @staticmethod
+    def _gap_flags(wild, seqs):
+        """the gap flags of `seqs` (int label arrays) back to back, len(s) + 1 per sequence, as uint8 -- or None.  wild:
+        "ends" (the gap before the first and after the last label), "all", None, or one boolean array per sequence."""
+        if wild is None:
+            return None
+        if isinstance(wild, str):
+            if wild not in ("ends", "all"):
+                raise ValueError('wild is %r: expected "ends", "all", None or one flag array per sequence' % (wild,))
+            flags = [np.ones(s.size + 1, dtype=np.uint8) for s in seqs]
+            if wild == "ends":
+                for f in flags:
+                    f[1:-1] = 0
+        else:
+            if len(wild) != len(seqs):
+                raise ValueError("%d flag arrays for %d label sequences" % (len(wild), len(seqs)))
+            flags = [np.asarray(f).astype(bool).astype(np.uint8).reshape(-1) for f in wild]
+            for f, s in zip(flags, seqs):
+                if f.size != s.size + 1:
+                    raise ValueError("%d gap flags for %d labels: a sequence of S labels has S + 1 gaps" % (f.size, s.size))
+        return np.concatenate(flags) if flags else np.zeros(0, dtype=np.uint8)
+
+    def ctc_align_wild(self, utterances, targets, wild="ends"):
+        """ctc_align for transcripts that cover only PART of a recording (tfk_ctc_align_wild; the contract is stated in
+        include/tfkaldi_hip.h): a gap of the label sequence -- before the first label, between two labels, after the last --
+        whose flag is set is a wildcard that may hold anything (it emits the frame's best class).  wild: "ends" (untranscribed
+        material before and after the transcript), "all", None (ctc_align's result), or one boolean array of
+        len(targets[u]) + 1 flags per utterance.  Returns (alis, scores, free): as ctc_align, -1 for a frame in any gap (None
+        for an utterance without a path), and free float32 [U], the log-probability of the unconstrained best path:
+        scores - free <= 0 is what the transcript costs against it.  ctc_segments works on alis unchanged."""
+        if len(utterances) != len(targets):
+            raise ValueError("%d utterances, %d label sequences" % (len(utterances), len(targets)))
+        if len(utterances) == 0:
+            return [], np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.float32)
+        targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        return self._ctc("ctc_align_wild", utterances, np.concatenate(targets), [t.size for t in targets],
+                         wild=self._gap_flags(wild, targets))
+
+    def ctc_spot(self, utterances, patterns, wild="ends"):
+        """Keyword spotting with a CTC model (tfk_ctc_spot; the contract is stated in include/tfkaldi_hip.h): every one of
+        the K `patterns` (int label arrays) is searched in every utterance, U x K pairs in ONE forward pass.  wild as
+        ctc_align_wild, per pattern ("ends": the keyword may lie anywhere in the utterance).  Returns (scores [U, K] float32,
+        starts [U, K] int32, ends [U, K] int32, free [U] float32): for every pair what ctc_align_wild gives for that utterance
+        and pattern -- the score of the best path, the first frame that emits a label and one past the last (-inf, -1, -1
+        without a path; 0, 0 for an empty pattern).  scores - free[:, None] <= 0 ranks the hits: 0 means the pattern lies on
+        the model's best path."""
+        patterns = [np.asarray(p, dtype=np.int32).reshape(-1) for p in patterns]
+        U, K = len(utterances), len(patterns)
+        flags = self._gap_flags(wild, patterns)
+        if U == 0:
+            return (np.zeros((0, K), dtype=np.float32), np.zeros((0, K), dtype=np.int32), np.zeros((0, K), dtype=np.int32),
+                    np.zeros(0, dtype=np.float32))
+        labels = np.tile(np.concatenate(patterns), U) if K else np.zeros(0, dtype=np.int32)
+        scores, starts, ends, free = self._ctc("ctc_spot", utterances, [K] * U, labels, [p.size for p in patterns] * U,
+                                               wild=None if flags is None else np.tile(flags, U))
+        return (np.asarray(scores, dtype=np.float32).reshape(U, K), np.asarray(starts, dtype=np.int32).reshape(U, K),
+                np.asarray(ends, dtype=np.int32).reshape(U, K), free)
+
     def ctc_score(self, utterances, hyps, refs=None):
         """N-best rescoring of a CTC model (tfk_ctc_score; the contract is stated in include/tfkaldi_hip.h): every utterance
         in ONE forward pass, then for every hypothesis hyps[u][n] (a list of int label arrays per utterance, possibly empty)

@@ -36,6 +36,12 @@ time per frame step, the graph search's time over the n-gram search's, and the l
 of the batch's transcripts and a 50-word lexicon trie with a separator (its references are word sequences) -- the median of
 the timed steps with the spread, the profiler's rows of the numerator (softmax_xent) and of the two new kernels, the sweep's
 time per frame of the 800-frame chain against the composed states N, and the residence (LDS or global) each graph took.
+`--spot` runs the wildcard leg alone (its output is kept in profiles/ctc_spot_bench.txt): alignment with both ends wild
+(tfk_ctc_align_wild) beside tfk_ctc_align on the same batch, and keyword spotting (tfk_ctc_spot) for 10 and 1000 patterns of 3
+to 12 labels per utterance, and for 10 patterns of 130 to 250 and of 260 to 500 labels (the two largest register tiles), beside
+tfk_ctc_score on the same pairs -- ms per call, the profiler family's time, that time per
+frame step, and the two ratios (wild alignment to plain alignment, spot to score: each compares two kernels with the same
+dependent chain of Tn steps).
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -74,6 +80,14 @@ def main():
     if "--align-only" in sys.argv:
         eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
         align_leg(eng, X, utt, labels, np.asarray(lab), "random output weights")
+        eng.close()
+        return
+    if "--spot" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        bias = np.zeros(O, np.float32)
+        bias[O - 1] = 2.0
+        eng.set(_lib.BIASES, eng.L, bias)
+        spot_leg(eng, rng, X, utt, labels, np.asarray(lab), "blank bias 2.0")
         eng.close()
         return
     if "--score-only" in sys.argv:
@@ -578,6 +592,40 @@ def align_leg(eng, X, utt, labels, lab, case):
           "float64| score %.1e"
           % (case, ms, kern, kern * 1e3 / max(utt), int(np.mean(lab)), 100.0 * emitting, float(np.mean(scores)), len(utt),
              host, same, len(utt), diff))
+
+
+def spot_leg(eng, rng, X, utt, labels, lab, case):
+    """wild alignment beside plain alignment, spotting beside rescoring, on the same batch and the same pairs"""
+    U, O, Tn = len(utt), eng.O, max(utt)
+    ends = np.concatenate([np.array([1] + [0] * (n - 1) + [1], np.uint8) if n else np.ones(1, np.uint8) for n in lab])
+    plain = lambda: eng.ctc_align(X, utt, labels, lab)
+    wild = lambda: eng.ctc_align_wild(X, utt, labels, lab, ends)
+    p_ms, p_kern = _kernel_ms(eng, plain, ("ctc_align",), K=20)
+    w_ms, w_kern = _kernel_ms(eng, wild, ("ctc_align_wild",), K=20)
+    a, w = plain(), wild()
+    print("  spot (%s): %d utterances of %d frames, %d labels each: tfk_ctc_align %8.3f ms/call, ctc_align kernels %8.3f ms "
+          "(%.3f us per frame step); tfk_ctc_align_wild (ends wild) %8.3f ms/call, ctc_align_wild kernels %8.3f ms (%.3f us per "
+          "frame step); ratio wild alignment / plain alignment %.3f (kernels), %.3f (calls); mean score plain %.2f, wild %.2f, "
+          "free %.2f; %.0f %% / %.0f %% of the frames emit a label"
+          % (case, U, Tn, int(np.mean(lab)), p_ms, p_kern, p_kern * 1e3 / Tn, w_ms, w_kern, w_kern * 1e3 / Tn, w_kern / p_kern,
+             w_ms / p_ms, float(np.mean(a[1])), float(np.mean(w[1])), float(np.mean(w[2])),
+             100.0 * np.mean([np.mean(x >= 0) for x in a[0]]), 100.0 * np.mean([np.mean(x >= 0) for x in w[0]])))
+    # 3 to 12 labels: the smallest register tile; 130 to 250 and 260 to 500 labels: the two largest (R = 8 and 16)
+    for K, lo, hi in ((10, 3, 12), (1000, 3, 12), (10, 130, 250), (10, 260, 500)):
+        pats = [rng.integers(0, O - 1, size=int(rng.integers(lo, hi + 1))).astype(np.int32) for _ in range(U * K)]
+        counts, pl, pn = [K] * U, np.concatenate(pats), np.array([p.size for p in pats], np.int32)
+        flags = np.concatenate([np.array([1] + [0] * (n - 1) + [1], np.uint8) for n in pn])
+        score = lambda: eng.ctc_score(X, utt, counts, pl, pn)
+        spot = lambda: eng.ctc_spot(X, utt, counts, pl, pn, flags)
+        s_ms, s_kern = _kernel_ms(eng, score, ("ctc_score",))
+        k_ms, k_kern = _kernel_ms(eng, spot, ("ctc_spot",))
+        got = spot()
+        hits = np.concatenate(got[0]) - np.repeat(got[3], K)
+        print("  spot (%s) %4d patterns per utterance: %d pairs of %d to %d labels; tfk_ctc_score %8.3f ms/call, ctc_score kernels "
+              "%8.3f ms (%.3f us per frame step); tfk_ctc_spot (ends wild) %8.3f ms/call, ctc_spot kernels %8.3f ms (%.3f us per "
+              "frame step); ratio spot / score %.3f (kernels), %.3f (calls); score - free: best %.2f, median %.2f"
+              % (case, K, U * K, lo, hi, s_ms, s_kern, s_kern * 1e3 / Tn, k_ms, k_kern, k_kern * 1e3 / Tn, k_kern / s_kern, k_ms / s_ms,
+                 float(hits.max()), float(np.median(hits))))
 
 
 if __name__ == "__main__":
