@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 19
+#define TFK_ABI_VERSION 20
 
 typedef struct tfk_engine tfk_engine;
 
@@ -591,6 +591,62 @@ int tfk_ctc_spot_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
 int tfk_ctc_spot_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                         const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
                         const uint8_t* wild, float* score, int32_t* start, int32_t* end, float* free_score);
+/* (ABI 20) CTC TRAINING ON PARTIAL TRANSCRIPTS: the CTC loss over the lattice of tfk_ctc_align_wild, under the sum instead of
+ * the max.  A flagged gap of the label sequence absorbs any frames at no cost, or at a chosen cost per frame: W-CTC (Cai et
+ * al. 2022) and the star token of STC (Pratap et al. 2022).  tfk_accumulate_ctc on a transcript with untranscribed audio
+ * before, after or inside it forces those frames onto blanks or the neighbouring labels and teaches deletions; this does not.
+ * This comment is the contract.
+ * Lattice.  For an utterance of Tn frames with logits z [Tn, O], labels l_0 ... l_{S-1} and gap flags w_0 ... w_S:
+ *   - States, start, end and transitions are exactly those of tfk_accumulate_ctc and tfk_ctc_align_wild: n = 2S + 1 states,
+ *     start in state 0 or 1, end in n - 1 or n - 2, steps of 0, 1 or 2; a step of 2 goes only into a label state whose label
+ *     differs from the label two states back.
+ *   - Gap g is the even state 2g, g in [0, S].  Two equal labels with a wildcard gap between them still need one frame in it.
+ * Emissions, in the probability domain, with p_t = softmax(z_t):
+ *   - a label state emits p_t(label);
+ *   - a gap with w_g = 0 emits p_t(blank);
+ *   - a gap with w_g = 1 emits exp(-penalty).  penalty is finite and >= 0; at 0 the emission is sum_c p_t(c) = 1, "any
+ *     class".  (The STC recipe anneals it.)
+ * Loss.  loss_u = -log of the sum, over all paths through the lattice, of the product of the path's emissions.
+ *   - This is the VALUE OF THE LATTICE, not a probability: a frame labelling that several lattice paths reach through a
+ *     wildcard (a frame of class l_0 may sit in the wildcard gap before l_0 or in l_0's own state) is counted once per PATH,
+ *     as W-CTC and STC count it.  The loss can therefore be NEGATIVE: [wild, a, wild] on T frames that put all mass on `a`
+ *     has T (T + 1) / 2 paths of value 1 and a loss of -log(T (T + 1) / 2).
+ *   - Feasibility is that of the plain loss (the transitions are the same): an utterance too short for its labels gives +inf
+ *     and a zero gradient; a zero-frame utterance gives 0 if S == 0, else +inf.
+ * Gradient.  dL/dz[t, c] = softmax(z_t)[c] * (1 - W_t) - occ[t, c], with W_t = the posterior mass of the wildcard states at
+ * frame t and occ = the posteriors of the other states folded onto their classes (a wildcard's emission does not depend on
+ * z).  Every row sums to zero.  The per-frame division of the posteriors by their sum -- applied, as in the plain loss, where
+ * that sum is within 1e-2 of one -- is over ALL states, wildcards included.  W_t is summed in a fixed order: two calls give
+ * the same bits.
+ * Bookkeeping.  batch_loss += sum_u loss_u, num_frames += number of reference labels (as every CTC criterion here), then
+ * backward as tfk_accumulate.  TFK_LAST_MICROBATCH, TFK_DEVICE_PTRS, the bf16 twin and the set-aside of an open step's sums
+ * during evaluation as for tfk_accumulate_ctc.
+ * Layout of wild: that of tfk_ctc_align_wild -- uint8, S_u + 1 flags per utterance, utterance u's flags start at
+ * lab_off[u] + u, host pointer, NULL means all zero.  With NULL or all-zero flags batch_loss, num_frames and dLogits are
+ * tfk_accumulate_ctc's bit for bit, at any penalty.
+ * Errors (non-zero; the accumulators are untouched and the engine stays usable; all checked before the pass starts):
+ * everything tfk_accumulate_ctc refuses; a flag other than 0 or 1 (the message names the utterance and the gap); a negative
+ * or non-finite penalty (the message names `penalty`). */
+int tfk_accumulate_ctc_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                            const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float penalty, int flags);
+int tfk_eval_accumulate_ctc_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                 const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float penalty, int flags);
+/* The same on UNSPLICED frames (device-side CMVN + splice as tfk_accumulate_ctc_raw; TFK_RAW_DEVICE allowed). */
+int tfk_accumulate_ctc_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                                int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                                const uint8_t* wild, float penalty, int flags);
+int tfk_eval_accumulate_ctc_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                     int32_t U, int32_t context_width, const float* cmvn, const int32_t* labels,
+                                     const int32_t* label_len, const uint8_t* wild, float penalty, int flags);
+/* (ABI 20) Tests / tools: the criterion alone on logits [T, ld] of O classes (T > 0), DEVICE pointers (wild included), tables
+ * as tfk_ctc_align_wild_logits takes them.  Out: utt_loss [U] and -- unless dlogits is NULL, which asks for utt_loss only --
+ * rows [seg[0], seg[U]) of dlogits [T, ldd] = dL/dz as above, columns [O, ldd) written as zero; rows outside are not written.
+ * dlogits may be the logits themselves (then ldd == ld).  Stream-ordered on `stream` after the two offset tables have come
+ * back (one synchronisation), with the call's own scratch from the stream's memory pool.  Labels, flags and penalty are not
+ * validated (any non-zero flag is a wildcard). */
+int tfk_ctc_wild_loss_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                             const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, float penalty, float* utt_loss,
+                             float* dlogits, int64_t ldd);
 /* (ABI 15) Training on the EXPECTED NUMBER OF LABEL ERRORS over an N-best list (MWER; Prabhavalkar et al. 2018, Shannon 2017)
  * instead of -- or on top of -- the CTC likelihood.  Train-mode forward of the flat utterance-major frames X [T, ldx] of U
  * utterances (utt_len[U], sum = T) as tfk_accumulate_ctc; ref_labels / ref_len[U] = the references, laid out as

@@ -30,6 +30,11 @@ struct CtcBatch {
   double* offb;            // [T]     scratch: the same for the backward variables
   double* logz;            // [U]     scratch: log p(labels) in double
   float* utt_loss;         // [U] out: -log p, +inf for an utterance too short for its labels
+  // Wildcard gaps (the contract is the comment at tfk_accumulate_ctc_wild in tfkaldi_hip.h): gap g of utterance u (the even
+  // state 2g) whose flag wild[lab_off[u] + u + g] is non-zero emits exp(-wild_cost) instead of p_t(blank).  NULL: no flag
+  // set, and every value is the plain loss's bit for bit (MWER's pair-level batches and MMI's numerator leave it so).
+  const uint8_t* wild = nullptr;
+  float wild_cost = 0.f;
 };
 
 // Longest label sequence the wave-per-utterance recursion handles (64 lanes x 16 states).
@@ -39,7 +44,13 @@ int ctc_state_stride(int max_labels);
 
 // with_grad: dlogits [T, ld] <- softmax - state posteriors folded onto the classes (zero rows for utterances with an
 // infinite loss); tw: bf16 twin of dlogits (mixed-precision mode).  Without with_grad only utt_loss is produced.
+// With b.wild the loss is the value of the lattice with wildcard gaps and dlogits <- softmax * (1 - W_t) - the posteriors of
+// the label and blank-gap states folded onto the classes, W_t = the posterior mass of the frame's wildcard states.
 void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_grad, Twin tw);
+// The same for a batch whose utterances cover only rows [row0, row0 + rows) of the T rows, with dlogits of its own row stride
+// ldd >= O: only those rows of dlogits are written, columns [O, ldd) as zero; no twin.  What tfk_ctc_wild_loss_logits calls.
+// dlogits may be the logits themselves when ldd == b.ld (the gradient reads post, never the logits).
+void ctc_loss_grad_rows(hipStream_t s, const CtcBatch& b, float* dlogits, int ldd, int row0, int rows, int with_grad);
 
 // scalars[0] (+)= sum of the utterance losses, scalars[1] (+)= number of labels (trainer.py:126-133 counts TARGET
 // lengths), scalars[2] (+)= 1

@@ -1,14 +1,16 @@
 // CTC loss and its gradient w.r.t. the logits, gfx950 (wave64).  See ctc.h for what it restates.
 //
 //   ctc_softmax      one block per frame: softmax row (kept for the gradient) and its log-sum-exp
-//   ctc_gather       log p_t(state) for the 2S+1 states of the frame's utterance, contiguous per frame
+//   ctc_gather       log p_t(state) for the 2S+1 states of the frame's utterance, contiguous per frame; a WILDCARD gap
+//                    (CtcBatch::wild) gets -wild_cost instead -- the sweeps below read this table and stay as they are
 //   ctc_alpha_beta   ONE WAVE PER UTTERANCE: every lane owns R consecutive states in registers, the s-1 / s-2
 //                    neighbours of a lane's first states come from the previous lane by DPP wave shifts -- the time
 //                    recursion runs without LDS and without barriers.  The forward sweep (alpha, loss) and the
 //                    backward sweep (beta) of an utterance are two independent waves of one launch
 //   ctc_grad         one wave per frame: state posteriors from alpha, beta and log Z, folded onto the classes in
 //                    LABEL ORDER (repeated labels
-//                    and the S+1 blanks are summed in a fixed order, so the result is bitwise reproducible)
+//                    and the S+1 blanks are summed in a fixed order, so the result is bitwise reproducible); with
+//                    wildcard gaps their posterior mass W_t scales the softmax row by 1 - W_t and pulls on no class
 //   ctc_viterbi      forced alignment, ONE WAVE PER UTTERANCE: the max-plus twin of the forward sweep on the raw logits
 //                    with 2-bit back-pointers, then the backtrace over back-pointer rows staged 64 frames at a time in LDS
 //                    (ctc_row_lse supplies the rows' log-sum-exps for the score)
@@ -101,6 +103,8 @@ ctc_softmax_kernel(const float* __restrict__ logits, int O, int ld, float* __res
   if (threadIdx.x == 0) lse[row] = mx + logf(se);
 }
 
+// WILD: b.wild is set (the plain instantiation is the kernel as it was before the wildcards came)
+template <bool WILD>
 __global__ void __launch_bounds__(256)
 ctc_gather_kernel(CtcBatch b) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,6 +116,8 @@ ctc_gather_kernel(CtcBatch b) {
   if (s < n) {
     const int k = (s & 1) ? b.labels[l0 + (s >> 1)] : b.O - 1;
     v = b.logits[(size_t)t * b.ld + k] - b.lse[t];
+    // a wildcard gap emits exp(-wild_cost) whatever the frame holds (a finite value: no new inf arithmetic downstream)
+    if (WILD && !(s & 1) && b.wild[l0 + u + (s >> 1)]) v = -b.wild_cost;
   }
   b.lp[idx] = v;
 }
@@ -292,11 +298,17 @@ ctc_alpha_beta_kernel(CtcBatch b) {
 //   gamma_t(s) = exp((alpha~ + beta~ - lp) + (off_alpha(t) + off_beta(t) - log Z))
 // (the exponent is summed in double and rounded once), then divided by its sum over the frame's states where
 // that sum is one up to round-off
-__global__ void __launch_bounds__(64)
-ctc_grad_kernel(CtcBatch b, float* __restrict__ dlogits, Twin tw) {
+// WILD (b.wild is set): a wildcard gap's emission does not depend on the logits, so its posterior pulls on no class and the
+// softmax row keeps only the mass of the other states: row <- softmax * (1 - W_t) - the label and blank-gap posteriors, with
+// W_t = the posteriors of the frame's wildcard gaps, summed beside the blank sum in the same fixed order.  With no flag set
+// W_t = 0.f, softmax * 1.f is exact and the blank sum adds the same terms: the plain kernel's bits.
+// A flag array that is NULL counts as all zero.  dlogits has row stride ldd, columns [b.ld, ldd) are written as zero.
+// One body for the two kernels below; ctc_grad_kernel's compiled form is the one it had before the wildcards came.
+template <bool WILD>
+__device__ __forceinline__ void ctc_grad_frame(const CtcBatch& b, float* __restrict__ dlogits, int ldd, int t, const Twin& tw) {
   extern __shared__ float row[];
   float* g = row + b.ld;
-  const int t = blockIdx.x, lane = threadIdx.x;
+  const int lane = threadIdx.x;
   const int u = utt_of(b.seg, b.U, t);
   const int l0 = b.lab_off[u], S = b.lab_off[u + 1] - l0, n = 2 * S + 1;
   const bool live = b.utt_loss[u] < INFINITY;
@@ -329,17 +341,41 @@ ctc_grad_kernel(CtcBatch b, float* __restrict__ dlogits, Twin tw) {
   }
   __syncthreads();
   float blank = 0.f;
-  for (int s = 2 * lane; s < n; s += 128) blank += g[s];
-  for (int o = 32; o > 0; o >>= 1) blank += __shfl_xor(blank, o);
+  if constexpr (WILD) {
+    const uint8_t* w = b.wild ? b.wild + l0 + u : nullptr;
+    float wsum = 0.f;
+    for (int s = 2 * lane; s < n; s += 128) {
+      const bool f = w && w[s >> 1] != 0;
+      blank += f ? 0.f : g[s];
+      wsum += f ? g[s] : 0.f;
+    }
+    for (int o = 32; o > 0; o >>= 1) blank += __shfl_xor(blank, o);
+    for (int o = 32; o > 0; o >>= 1) wsum += __shfl_xor(wsum, o);
+    const float keep = 1.f - wsum;
+    for (int c = lane; c < b.ld; c += 64) row[c] *= keep;  // (the elements this lane loaded itself)
+    __syncthreads();
+  } else {
+    for (int s = 2 * lane; s < n; s += 128) blank += g[s];
+    for (int o = 32; o > 0; o >>= 1) blank += __shfl_xor(blank, o);
+  }
   if (lane == 0 && live) {
     row[b.O - 1] -= blank;
     for (int j = 0; j < S; ++j) row[b.labels[l0 + j]] -= g[2 * j + 1];  // label order: deterministic for repeats
   }
   __syncthreads();
-  float* dr = dlogits + (size_t)t * b.ld;
-  for (int c = lane; c < b.ld; c += 64) dr[c] = row[c];
+  float* dr = dlogits + (size_t)t * ldd;
+  for (int c = lane; c < ldd; c += 64) dr[c] = c < b.ld ? row[c] : 0.f;
   if (tw.p)
     for (int c = lane; c < b.ld; c += 64) twin_put(tw, (size_t)t, c, row[c]);
+}
+__global__ void __launch_bounds__(64)
+ctc_grad_kernel(CtcBatch b, float* __restrict__ dlogits, Twin tw) {
+  ctc_grad_frame<false>(b, dlogits, b.ld, blockIdx.x, tw);
+}
+// the launch covers rows [row0, row0 + gridDim.x)
+__global__ void __launch_bounds__(64)
+ctc_grad_wild_kernel(CtcBatch b, float* __restrict__ dlogits, int ldd, int row0, Twin tw) {
+  ctc_grad_frame<true>(b, dlogits, ldd, row0 + blockIdx.x, tw);
 }
 
 __global__ void __launch_bounds__(256)
@@ -2446,11 +2482,12 @@ ctc_den_grad_kernel(CtcDen d, const float* g, int ldg, int row0, float* dlogits,
 
 int ctc_state_stride(int max_labels) { return 64 * regs_for(max_labels); }
 
-void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_grad, Twin tw) {
+static void loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int ldd, int row0, int rows, int with_grad, Twin tw) {
   if (b.T <= 0 || b.U <= 0) return;
   hipLaunchKernelGGL(ctc_softmax_kernel, dim3(b.T), dim3(256), 0, s, b.logits, b.O, b.ld, b.post, b.lse);
   const size_t n = (size_t)b.T * b.sext;
-  hipLaunchKernelGGL(ctc_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b);
+  if (b.wild) hipLaunchKernelGGL(ctc_gather_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b);
+  else hipLaunchKernelGGL(ctc_gather_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b);
   const dim3 grid(b.U, with_grad ? 2 : 1);
   switch (b.sext / 64) {
     case 2: hipLaunchKernelGGL(ctc_alpha_beta_kernel<2>, grid, dim3(64), 0, s, b); break;
@@ -2458,8 +2495,20 @@ void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_gr
     case 8: hipLaunchKernelGGL(ctc_alpha_beta_kernel<8>, grid, dim3(64), 0, s, b); break;
     default: hipLaunchKernelGGL(ctc_alpha_beta_kernel<16>, grid, dim3(64), 0, s, b); break;
   }
-  if (with_grad)
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(b.T), dim3(64), (size_t)(b.ld + b.sext) * sizeof(float), s, b, dlogits, tw);
+  if (!with_grad || rows <= 0) return;
+  const size_t lds = (size_t)(b.ld + b.sext) * sizeof(float);
+  if (b.wild || ldd != b.ld || row0 != 0 || rows != b.T)
+    hipLaunchKernelGGL(ctc_grad_wild_kernel, dim3(rows), dim3(64), lds, s, b, dlogits, ldd, row0, tw);
+  else
+    hipLaunchKernelGGL(ctc_grad_kernel, dim3(b.T), dim3(64), lds, s, b, dlogits, tw);
+}
+
+void ctc_loss_grad(hipStream_t s, const CtcBatch& b, float* dlogits, int with_grad, Twin tw) {
+  loss_grad(s, b, dlogits, b.ld, 0, b.T, with_grad, tw);
+}
+
+void ctc_loss_grad_rows(hipStream_t s, const CtcBatch& b, float* dlogits, int ldd, int row0, int rows, int with_grad) {
+  loss_grad(s, b, dlogits, ldd, row0, rows, with_grad, Twin());
 }
 
 void ctc_loss_reduce(hipStream_t s, const float* utt_loss, const int32_t* lab_off, int U, float* scalars,

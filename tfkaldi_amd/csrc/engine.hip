@@ -195,6 +195,8 @@ struct tfk_engine {
   // CTC loss (tfk_accumulate_ctc): device copies of the utterance / label offsets and the state workspaces,
   // grown on demand
   int32_t *ctc_seg = nullptr, *ctc_lab_off = nullptr, *ctc_lab = nullptr;
+  uint8_t* ctc_wild = nullptr;  // the gap flags of tfk_accumulate_ctc_wild, staged behind the labels
+  size_t ctc_cap_wild = 0;
   float *ctc_lp = nullptr, *ctc_ab = nullptr, *ctc_bb = nullptr, *ctc_utt_loss = nullptr, *ctc_lse = nullptr;
   double *ctc_off = nullptr, *ctc_offb = nullptr, *ctc_logz = nullptr;
   size_t ctc_cap_bb = 0, ctc_cap_offb = 0, ctc_cap_logz = 0;
@@ -1540,6 +1542,8 @@ struct CtcSpec {  // CTC loss instead of the frame-level cross-entropy
   const int32_t* label_len;  // [U]
   const MwerSpec* mwer = nullptr;  // the MWER criterion: labels / label_len are the references
   const struct MmiSpec* mmi = nullptr;  // the MMI criterion against the engine's denominator graph
+  const uint8_t* wild = nullptr;  // wildcard gaps (tfk_accumulate_ctc_wild): label_len[u] + 1 flags per utterance; NULL: none
+  float wild_cost = 0.f;          // what a frame in a wildcard gap costs
 };
 struct MmiSpec {
   float lm_scale, ctc_weight;
@@ -1570,9 +1574,9 @@ int grow_pinned(tfk_engine* e, Tp** p, size_t* cap, size_t need, bool slack, boo
   return 0;
 }
 // Validate the utterance / label tables of a CTC batch and stage (seg, lab_off, labels) in e->ctc_seg / ctc_lab_off /
-// ctc_lab on the engine's stream.  Labels follow tf.nn.ctc_loss: values in [0, O - 1) (the blank is the LAST class), at most
-// kCtcMaxLabels per utterance.  label_len may be NULL only when !need_labels (no references: every label count is 0).
-// Returns the longest label sequence in *max_labels_out.
+// ctc_lab (and, with c.wild, the gap flags in e->ctc_wild) on the engine's stream.  Labels follow tf.nn.ctc_loss: values in
+// [0, O - 1) (the blank is the LAST class), at most kCtcMaxLabels per utterance.  label_len may be NULL only when
+// !need_labels (no references: every label count is 0).  Returns the longest label sequence in *max_labels_out.
 int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max_labels_out) {
   if (c.U <= 0 || !c.utt_len || (need_labels && !c.label_len)) return fail(-1, "CTC: no utterances");
   std::vector<int32_t> seg(c.U + 1, 0), off(c.U + 1, 0);
@@ -1593,11 +1597,13 @@ int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max
   CHK(grow(e, &e->ctc_seg, &e->ctc_cap_seg, (size_t)c.U + 1));
   CHK(grow(e, &e->ctc_lab_off, &e->ctc_cap_off, (size_t)c.U + 1));
   CHK(grow(e, &e->ctc_lab, &e->ctc_cap_lab, (size_t)(total > 0 ? total : 1)));
+  const size_t nflags = c.wild ? (size_t)total + (size_t)c.U : 0, flag_words = (nflags + 3) / 4;
+  if (c.wild) CHK(grow(e, &e->ctc_wild, &e->ctc_cap_wild, 4 * flag_words));
   {
     // The three small tables go through pinned staging, two buffers used in turn: the host never waits for the
     // stream here (the event guards the buffer's use two micro-batches ago).
     const int k = e->ctc_stage_slot ^= 1;
-    const size_t need = 2 * ((size_t)c.U + 1) + (size_t)total;
+    const size_t need = 2 * ((size_t)c.U + 1) + (size_t)total + flag_words;
     if (!e->ctc_staged[k]) HIPCHK(hipEventCreateWithFlags(&e->ctc_staged[k], hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(e->ctc_staged[k]));
     CHK(grow_pinned(e, &e->h_ctc[k], &e->h_ctc_cap[k], need, /*slack=*/true, /*sync=*/false));  // (the event above guards it)
@@ -1611,6 +1617,10 @@ int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max
     if (total > 0)
       HIPCHK(hipMemcpyAsync(e->ctc_lab, h + 2 * (c.U + 1), (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice,
                             e->stream));
+    if (c.wild) {
+      memcpy(h + 2 * (c.U + 1) + total, c.wild, nflags);
+      HIPCHK(hipMemcpyAsync(e->ctc_wild, h + 2 * (c.U + 1) + total, nflags, hipMemcpyHostToDevice, e->stream));
+    }
     HIPCHK(hipEventRecord(e->ctc_staged[k], e->stream));
   }
   *max_labels_out = max_labels;
@@ -1639,6 +1649,7 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   b.U = c.U; b.T = T; b.O = e->O; b.sext = sext;
   b.lp = e->ctc_lp; b.ab = e->ctc_ab; b.bb = e->ctc_bb; b.utt_loss = e->ctc_utt_loss;
   b.off = e->ctc_off; b.offb = e->ctc_offb; b.logz = e->ctc_logz;
+  if (c.wild) { b.wild = e->ctc_wild; b.wild_cost = c.wild_cost; }
   {
     ProfScope ps(e, KF_SOFTMAX_XENT, 0, 8.0 * T * e->O + 16.0 * T * sext);
     Twin tw;
@@ -2264,7 +2275,8 @@ int tfk_destroy(tfk_engine* e) {
   if (e->Wb && e->own_wb) hipFree(e->Wb);
   if (e->d_checksum) hipFree(e->d_checksum);
   if (e->ws_splitk) hipFree(e->ws_splitk);
-  for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_lp, (void*)e->ctc_ab,
+  for (void* p : {(void*)e->ctc_seg, (void*)e->ctc_lab_off, (void*)e->ctc_lab, (void*)e->ctc_wild, (void*)e->ctc_lp,
+                  (void*)e->ctc_ab,
                   (void*)e->ctc_utt_loss, (void*)e->ctc_lse, (void*)e->ctc_off, (void*)e->ctc_bb, (void*)e->ctc_offb,
                   (void*)e->ctc_logz, (void*)e->ctc_dec, (void*)e->ctc_trie, (void*)e->ctc_bp, (void*)e->ctc_lm,
                   (void*)e->ctc_pre, (void*)e->ctc_sc, (void*)e->ctc_pair, (void*)e->ctc_mw, (void*)e->ctc_graph_next,
@@ -2510,6 +2522,63 @@ int tfk_eval_accumulate_ctc_raw(tfk_engine* e, const float* raw, int64_t ldraw, 
   CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   const CtcSpec c = {utt_len, U, labels, label_len};
   return train_or_eval(e, raw, ldraw, nullptr, T, flags & ~TFK_LAST_MICROBATCH, 0, &r, &c);
+}
+
+// CTC loss with wildcard gaps (the contract: tfkaldi_hip.h at tfk_accumulate_ctc_wild): the plain entry's pass with the flags
+// and the penalty in its CtcSpec.  Both, and the tables the flags are indexed by, are validated on the host before the pass
+// starts, so a refused call leaves the engine as it was; the messages name the utterance and the gap, as tfk_ctc_align_wild's do.
+static int ctc_wild_entry(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                          const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float penalty, int flags,
+                          int train, const RawSpec* raw) {
+  if (!e) return fail(-1, "engine is NULL");
+  if (T <= 0) return fail(-1, "empty micro-batch (T = %d)", T);
+  if (!(penalty >= 0.f) || !std::isfinite(penalty))
+    return fail(-1, "CTC wild: penalty %g is negative or not finite", (double)penalty);
+  if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC wild: utt_len / label_len is NULL or no utterances");
+  int64_t frames = 0, first = 0;
+  for (int u = 0; u < U; ++u) {
+    const int32_t n = label_len[u];
+    if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC wild: utterance %d has a negative length", u);
+    if (n > kCtcMaxLabels) return fail(-1, "CTC wild: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
+    if (n > 0 && !labels) return fail(-1, "CTC wild: labels is NULL");
+    for (int32_t i = 0; i < n; ++i)
+      if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
+        return fail(-1, "CTC wild: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
+    if (wild)
+      for (int32_t g = 0; g <= n; ++g)
+        if (wild[first + u + g] > 1)
+          return fail(-1, "CTC wild: utterance %d, gap %d: wild is %d, not 0 or 1", u, g, (int)wild[first + u + g]);
+    frames += utt_len[u];
+    first += n;
+    if (first > 0x7fffffff - U) return fail(-1, "CTC wild: more than 2^31 - 1 labels and flags in one call");
+  }
+  if (frames != T) return fail(-1, "CTC wild: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
+  CtcSpec c = {utt_len, U, labels, label_len};
+  c.wild = wild;
+  c.wild_cost = penalty;
+  return train_or_eval(e, X, ldx, nullptr, T, train ? flags : flags & ~TFK_LAST_MICROBATCH, train, raw, &c);
+}
+int tfk_accumulate_ctc_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                            const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float penalty, int flags) {
+  return ctc_wild_entry(e, X, ldx, T, utt_len, U, labels, label_len, wild, penalty, flags, 1, nullptr);
+}
+int tfk_eval_accumulate_ctc_wild(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
+                                 const int32_t* labels, const int32_t* label_len, const uint8_t* wild, float penalty, int flags) {
+  return ctc_wild_entry(e, X, ldx, T, utt_len, U, labels, label_len, wild, penalty, flags, 0, nullptr);
+}
+int tfk_accumulate_ctc_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len, int32_t U,
+                                int32_t context_width, const float* cmvn, const int32_t* labels, const int32_t* label_len,
+                                const uint8_t* wild, float penalty, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_wild_entry(e, raw, ldraw, T, utt_len, U, labels, label_len, wild, penalty, flags, 1, &r);
+}
+int tfk_eval_accumulate_ctc_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, const int32_t* utt_len,
+                                     int32_t U, int32_t context_width, const float* cmvn, const int32_t* labels,
+                                     const int32_t* label_len, const uint8_t* wild, float penalty, int flags) {
+  RawSpec r;
+  CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
+  return ctc_wild_entry(e, raw, ldraw, T, utt_len, U, labels, label_len, wild, penalty, flags, 0, &r);
 }
 
 // Expected label errors over an N-best list (MWER) on top of ctc_weight times the CTC loss: everything is validated on the
@@ -2761,6 +2830,58 @@ int tfk_ctc_mmi_logits(void* stream, const float* logits, int64_t ld, int32_t O,
     launched = hipGetLastError();
   }
   const hipError_t freed = hipFreeAsync(scratch, st);  // also when a copy or the launch failed
+  HIPCHK(launched);
+  HIPCHK(freed);
+  return 0;
+}
+
+int tfk_ctc_wild_loss_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
+                             const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, float penalty, float* utt_loss,
+                             float* dlogits, int64_t ldd) {
+  hipStream_t st = (hipStream_t)stream;
+  if (U < 0) return fail(-1, "U = %d < 0", U);
+  if (U == 0) return 0;
+  if (T <= 0) return fail(-1, "CTC wild: empty batch (T = %d)", T);
+  if (!logits || !seg || !lab_off || !utt_loss) return fail(-1, "logits / seg / lab_off / utt_loss is NULL");
+  if (O < 1 || ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
+  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
+  if (dlogits == logits && dlogits && ldd != ld) return fail(-1, "dlogits in place needs ldd == ld");
+  std::vector<int32_t> h(2 * ((size_t)U + 1));  // (the two offset tables come back first, as tfk_ctc_align_logits)
+  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  int max_labels = 0;
+  for (int u = 0; u < U; ++u) {
+    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
+    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC wild: utterance %d has a negative length", u);
+    max_labels = n > max_labels ? n : max_labels;
+  }
+  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC wild: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
+  if (h[U + 1] < 0) return fail(-1, "CTC wild: lab_off[0] = %d < 0", h[U + 1]);
+  if (max_labels > kCtcMaxLabels) return fail(-1, "CTC wild: %d labels in one utterance (limit %d)", max_labels, kCtcMaxLabels);
+  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC wild: labels is NULL");
+  const bool train = dlogits != nullptr;
+  const int sext = ctc_state_stride(max_labels);
+  // the call's own scratch, released in stream order: [off T, offb T, logz U doubles | post T ld, lp / ab / bb T sext, lse T]
+  const size_t t = (size_t)T, u = (size_t)U;
+  const size_t bytes = (2 * t + u) * sizeof(double) + (t * (size_t)ld + 3 * t * (size_t)sext + t) * sizeof(float);
+  unsigned char* scratch = nullptr;
+  HIPCHK(hipMallocAsync((void**)&scratch, bytes, st));
+  CtcBatch b;
+  b.logits = logits; b.ld = (int)ld; b.seg = seg; b.labels = labels; b.lab_off = lab_off;
+  b.U = U; b.T = T; b.O = O; b.sext = sext;
+  b.off = reinterpret_cast<double*>(scratch); b.offb = b.off + t; b.logz = b.offb + t;
+  float* fp = reinterpret_cast<float*>(b.logz + u);
+  b.post = fp;                  fp += t * (size_t)ld;
+  b.lp = fp;                    fp += t * (size_t)sext;
+  b.ab = fp;                    fp += t * (size_t)sext;
+  b.bb = fp;                    fp += t * (size_t)sext;
+  b.lse = fp;
+  b.utt_loss = utt_loss;
+  b.wild = wild; b.wild_cost = penalty;
+  ctc_loss_grad_rows(st, b, dlogits, (int)ldd, h[0], h[U] - h[0], train ? 1 : 0);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t freed = hipFreeAsync(scratch, st);  // also when the launch failed
   HIPCHK(launched);
   HIPCHK(freed);
   return 0;

@@ -164,6 +164,24 @@ def _accumulate_mmi(engine, mb, last, train):
                                   ctc_weight=mb.ctc_weight, last=last, train=train)
 
 
+class CtcWildMicroBatch(CtcMicroBatch):
+    """A CTC micro-batch trained on the CTC loss with wildcard gaps (tfk_accumulate_ctc_wild): wild holds label_lens[u] + 1
+    flags per utterance, back to back (None: none set), and a flagged gap absorbs any frames at `penalty` per frame."""
+
+    def __init__(self, X, utt_lens, labels, label_lens, wild=None, penalty=0.0, context_width=None, cmvn=None):
+        CtcMicroBatch.__init__(self, X, utt_lens, labels, label_lens, context_width, cmvn)
+        self.wild, self.penalty = wild, float(penalty)
+
+
+def _accumulate_wild(engine, mb, last, train):
+    if mb.context_width is not None:
+        engine.accumulate_ctc_wild_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, wild=mb.wild,
+                                       penalty=mb.penalty, last=last, cmvn=mb.cmvn, train=train)
+    else:
+        engine.accumulate_ctc_wild(mb.X, mb.utt_lens, mb.labels, mb.label_lens, wild=mb.wild, penalty=mb.penalty, last=last,
+                                   train=train)
+
+
 def _mwer_tables(engine, mb):
     """the pair tables of an MWER micro-batch: its own, or the N best of a search on `engine` (evaluation passes that leave
     the sums of an open step alone); padding paths -- beam score -inf -- are dropped, as _label_errors drops them"""
@@ -205,6 +223,8 @@ def _accumulate(engine, mb, last):
         _accumulate_mwer(engine, mb, last, True)
     elif isinstance(mb, CtcMmiMicroBatch):
         _accumulate_mmi(engine, mb, last, True)
+    elif isinstance(mb, CtcWildMicroBatch):
+        _accumulate_wild(engine, mb, last, True)
     elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, last=last,
@@ -224,6 +244,8 @@ def _eval_accumulate(engine, mb):
         _accumulate_mwer(engine, mb, False, False)
     elif isinstance(mb, CtcMmiMicroBatch):
         _accumulate_mmi(engine, mb, False, False)
+    elif isinstance(mb, CtcWildMicroBatch):
+        _accumulate_wild(engine, mb, False, False)
     elif isinstance(mb, CtcMicroBatch):
         if mb.context_width is not None:
             engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, cmvn=mb.cmvn,

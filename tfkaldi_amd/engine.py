@@ -833,6 +833,42 @@ class Engine(object):
                  utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
                  label_lens.ctypes.data_as(c_void_p), lm_scale, ctc_weight, _lib.LAST_MICROBATCH if (last and train) else 0))
 
+    # ---- CTC loss with wildcard gaps (W-CTC / STC): training on transcripts that cover only part of a recording ----
+    @staticmethod
+    def _penalty(penalty):
+        penalty = float(penalty)
+        if not (np.isfinite(penalty) and penalty >= 0.0):
+            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
+        return penalty
+
+    def accumulate_ctc_wild(self, X, utt_lens, labels, label_lens, wild=None, penalty=0.0, last=False, train=True):
+        """One micro-batch of the CTC loss with WILDCARD GAPS (tfk_accumulate_ctc_wild; the contract is stated in
+        include/tfkaldi_hip.h): `wild` as ctc_align_wild takes it -- label_lens[u] + 1 flags per utterance, back to back
+        (uint8 or bool; None: none set) -- and a flagged gap absorbs any frames at `penalty` per frame (finite, >= 0).  The
+        loss is the value of the lattice: a labelling that several paths reach through a wildcard counts once per path, so
+        it can be negative.  With no flag set this is accumulate_ctc bit for bit.  train=False: evaluation-mode forward,
+        loss only."""
+        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
+        wild, penalty = self._wild(wild, label_lens, "CTC micro-batch"), self._penalty(penalty)
+        fn = self.lib.tfk_accumulate_ctc_wild if train else self.lib.tfk_eval_accumulate_ctc_wild
+        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p), _ptr(wild), penalty,
+                 _lib.LAST_MICROBATCH if (last and train) else 0))
+
+    def eval_accumulate_ctc_wild(self, X, utt_lens, labels, label_lens, wild=None, penalty=0.0):
+        self.accumulate_ctc_wild(X, utt_lens, labels, label_lens, wild, penalty, train=False)
+
+    def accumulate_ctc_wild_raw(self, raw, utt_lens, context_width, labels, label_lens, wild=None, penalty=0.0, last=False,
+                                cmvn=None, train=True):
+        """accumulate_ctc_wild from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
+        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
+        wild, penalty = self._wild(wild, label_lens, "CTC micro-batch"), self._penalty(penalty)
+        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
+        fn = self.lib.tfk_accumulate_ctc_wild_raw if train else self.lib.tfk_eval_accumulate_ctc_wild_raw
+        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
+                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
+                 label_lens.ctypes.data_as(c_void_p), _ptr(wild), penalty, _lib.LAST_MICROBATCH if (last and train) else 0))
+
     # ---- the optimiser step in parts (data parallel: Adam per reduced span, see dataparallel.BucketReducer) ----
     def apply_begin(self):
         check(self.lib.tfk_apply_begin(self._h))

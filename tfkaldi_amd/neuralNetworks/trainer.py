@@ -493,3 +493,52 @@ class CTCTrainer(Trainer):
         if inputs is None or targets is None:
             return None
         return self.dp.eval_step(self.engine, self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight))
+
+    # ---- training on partial transcripts: the CTC loss with wildcard gaps (W-CTC / STC) ----
+    def _wild_microbatches(self, inputs, targets, wild, penalty):
+        from ..dataparallel import CtcWildMicroBatch
+        from .decoder import Decoder
+        if len(inputs) != len(targets):
+            raise ValueError("%d utterances, %d label sequences" % (len(inputs), len(targets)))
+        try:
+            penalty = float(penalty)
+        except (TypeError, ValueError):
+            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
+        if not (np.isfinite(penalty) and penalty >= 0):
+            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
+        seqs = [np.asarray(t).astype(np.int32).reshape(-1) for t in targets]
+        flat = Decoder._gap_flags(wild, seqs)  # (validates `wild`; len(s) + 1 flags per utterance, back to back)
+        first = np.concatenate([[0], np.cumsum([s.size + 1 for s in seqs], dtype=np.int64)])
+        plan = [idx for idx in microbatch_indices(len(inputs), self.numutterances_per_minibatch) if idx]
+        plain = self._microbatches(inputs, targets)  # (one per non-empty group that holds frames, in plan order)
+        plan = [idx for idx in plan if sum(np.asarray(inputs[i]).shape[0] for i in idx) > 0]
+        assert len(plan) == len(plain)
+        out = []
+        for idx, mb in zip(plan, plain):  # the flags are cut per micro-batch: utterance u's start at lab_off[u] + u THERE
+            cut = None if flat is None else np.concatenate([flat[first[i]:first[i + 1]] for i in idx])
+            out.append(CtcWildMicroBatch(mb.X, mb.utt_lens, mb.labels, mb.label_lens, wild=cut, penalty=penalty,
+                                         context_width=mb.context_width, cmvn=mb.cmvn))
+        return out
+
+    def update_wild(self, inputs, targets, wild="ends", penalty=0.0):
+        """One optimiser step on the CTC loss with WILDCARD GAPS (tfk_accumulate_ctc_wild; W-CTC, Cai et al. 2022; the star
+        token of STC, Pratap et al. 2022), for transcripts that cover only PART of a recording: a flagged gap of the label
+        sequence absorbs any frames at `penalty` per frame (finite, >= 0; 0: free), where update would force them onto
+        blanks or the neighbouring labels.  wild as Decoder.ctc_align_wild takes it: "ends" (untranscribed material before
+        and after the transcript), "all", None (update's criterion), or one boolean array of len(targets[u]) + 1 flags per
+        utterance.  The loss is the value of the lattice -- a frame labelling that several lattice paths reach through a
+        wildcard counts once per path -- so it can be negative.  A bad wild or penalty raises a ValueError before the step
+        starts.  Returns the step's loss per reference label, before the update."""
+        microbatches = self._wild_microbatches(inputs, targets, wild, penalty)
+        if not microbatches:
+            raise ValueError("CTCTrainer.update_wild: the batch holds no frames (no micro-batch could be built from %d "
+                             "utterance(s))" % len(inputs))
+        loss = self.dp.train_step(self.engine, microbatches)
+        self._summarise(loss)
+        return loss
+
+    def evaluate_wild(self, inputs, targets, wild="ends", penalty=0.0):
+        """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
+        if inputs is None or targets is None:
+            return None
+        return self.dp.eval_step(self.engine, self._wild_microbatches(inputs, targets, wild, penalty))

@@ -42,6 +42,10 @@ to 12 labels per utterance, and for 10 patterns of 130 to 250 and of 260 to 500 
 tfk_ctc_score on the same pairs -- ms per call, the profiler family's time, that time per
 frame step, and the two ratios (wild alignment to plain alignment, spot to score: each compares two kernels with the same
 dependent chain of Tn steps).
+`--wild-loss` runs the wildcard-loss leg alone (its output is kept in profiles/ctc_wild_loss_bench.txt): one step on the CTC loss
+with wildcard gaps (tfk_accumulate_ctc_wild) beside one plain CTC step on the same build and batch -- wild="ends" at penalty 0,
+then random flags at penalty 0.5 -- the three steps timed in alternating blocks (median and spread over all blocks, and the
+spread of the plain step's block medians), then the profiler's per-kernel-family rows of each.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -109,6 +113,11 @@ def main():
     if "--mmi" in sys.argv:
         eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
         mmi_leg(eng, rng, X, utt, labels, np.asarray(lab), Tu)
+        eng.close()
+        return
+    if "--wild-loss" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        wild_loss_leg(eng, rng, X, utt, labels, np.asarray(lab), Tu)
         eng.close()
         return
     if "--topk-only" in sys.argv:
@@ -562,6 +571,56 @@ def mmi_leg(eng, rng, X, utt, labels, lab, Tu):
                   loss) + med + (med[0] / base[0], rows.get("softmax_xent", 0.0), sweep, sweep * 1e3 / Tu, Tu,
                                         sweep * 1e6 / Tu / graph.composed_states, grad)))
     eng.ctc_set_den(None)
+
+
+def wild_loss_leg(eng, rng, X, utt, labels, lab, Tu):
+    """the learning rate is set to zero first, so that every step sees the same model; the three steps alternate in blocks of K
+    timed steps, so that whatever else the host is doing falls on all of them alike"""
+    for _ in range(40):
+        eng.halve_learning_rate()
+    U, K, rounds = len(utt), 5, 6
+    ends = np.concatenate([np.r_[1, np.zeros(n - 1, np.uint8), 1] if n else np.ones(1, np.uint8) for n in lab]).astype(np.uint8)
+    anyf = rng.integers(0, 2, size=int(lab.sum()) + U).astype(np.uint8)
+
+    def plain():
+        eng.accumulate_ctc(X, utt, labels, lab, last=True)
+        return eng.apply()
+
+    def wild(flags, penalty):
+        eng.accumulate_ctc_wild(X, utt, labels, lab, wild=flags, penalty=penalty, last=True)
+        return eng.apply()
+    steps = [("plain CTC step (tfk_accumulate_ctc)", plain),
+             ('wildcard step, wild="ends", penalty 0', lambda: wild(ends, 0.0)),
+             ("wildcard step, random flags, penalty 0.5", lambda: wild(anyf, 0.5))]
+    loss = [step() for _, step in steps]
+    for _, step in steps:
+        for _ in range(2):
+            step()
+    ts = [[] for _ in steps]
+    for _ in range(rounds):
+        for i, (_, step) in enumerate(steps):
+            block = []
+            for _ in range(K):
+                t0 = time.perf_counter()
+                step()
+                block.append((time.perf_counter() - t0) * 1e3)
+            ts[i].append(block)
+    med = [float(np.median(np.concatenate(b))) for b in ts]
+    print("  wild-loss: %d utterances x %d frames, %d labels each, %d outputs; %d alternating blocks of %d timed steps (each step: "
+          "accumulate + tfk_apply, host clock around a call that ends in a synchronise)" % (U, Tu, int(lab[0]), eng.O, rounds, K))
+    for i, (name, _) in enumerate(steps):
+        blocks = [float(np.median(b)) for b in ts[i]]
+        print("  wild-loss %-42s: loss/label %9.4f; median %.3f ms (%.3f .. %.3f) = %.3f x the plain step; block medians "
+              "%.3f .. %.3f ms" % (name, loss[i], med[i], min(map(min, ts[i])), max(map(max, ts[i])), med[i] / med[0],
+                                   min(blocks), max(blocks)))
+    for name, step in steps:
+        eng.profile_begin()
+        for _ in range(K):
+            step()
+        rows = [s for s in eng.profile_end() if s["name"] in ("softmax_xent", "loss_reduce")]
+        print("  wild-loss %-42s: kernels per step: %s" % (name, ", ".join(
+            "%s %.3f ms (n=%d)" % (s["name"], s["total_ms"] / K, s["launches"] // K) for s in rows)))
+    print("  (softmax_xent is the loss family: row softmax, emission gather, both sweeps, gradient)")
 
 
 def align_leg(eng, X, utt, labels, lab, case):
