@@ -272,13 +272,14 @@ def test_limits_are_reported_and_leave_the_engine_usable(gpu):
     with pytest.raises(ValueError):
         eng.ctc_align(X, utt, labels, lab[:1])
     eng.close()
-    # the stand-alone entry: more than 511 labels, a negative length
+    # the stand-alone entry: more than 511 labels, a negative length, labels that would start in front of `labels`
     lib = _lib.load()
     z = torch.zeros((8, 4), dtype=torch.float32, device="cuda")
     out = torch.zeros(8, dtype=torch.int32, device="cuda")
     tab = lambda v: torch.tensor(v, dtype=torch.int32, device="cuda")
     lab_dev = torch.zeros(600, dtype=torch.int32, device="cuda")
-    for seg, off, word in (([0, 8], [0, 512], b"511"), ([0, 8, 6], [0, 1, 2], b"negative"), ([0, 4, 8], [0, 2, 1], b"negative")):
+    for seg, off, word in (([0, 8], [0, 512], b"511"), ([0, 8, 6], [0, 1, 2], b"negative"), ([0, 4, 8], [0, 2, 1], b"negative"),
+                           ([0, 8], [-1, 1], b"lab_off[0]")):
         d_seg, d_off = tab(seg), tab(off)
         assert lib.tfk_ctc_align_logits(c_void_p(0), c_void_p(z.data_ptr()), 4, 4, 8, c_void_p(d_seg.data_ptr()), len(seg) - 1,
                                         c_void_p(lab_dev.data_ptr()), c_void_p(d_off.data_ptr()), c_void_p(out.data_ptr()),

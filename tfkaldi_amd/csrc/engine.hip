@@ -11,9 +11,11 @@
 //     logits, two ping-pong gradient buffers, BN batch statistics, reduction workspace.
 #include "../../include/tfkaldi_hip.h"
 #include "ctc.h"
+#include "ctc_tables.h"
 #include "gemm_bf16.h"
 #include "gemm_f32.h"
 #include "kernels.h"
+#include "tfk_error.h"
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -32,29 +34,7 @@ using namespace tfk;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code ? code : -1;
-}
-
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                      __FILE__, __LINE__);                                        \
-  } while (0)
-#define CHK(expr)            \
-  do {                       \
-    int rc_ = (expr);        \
-    if (rc_ != 0) return rc_; \
-  } while (0)
+thread_local std::string g_err;  // what tfk_last_error returns: every unit's fail() ends in tfk::set_error below
 
 inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -1573,6 +1553,34 @@ int grow_pinned(tfk_engine* e, Tp** p, size_t* cap, size_t need, bool slack, boo
   *cap = n;
   return 0;
 }
+// The pair tables of tfk_ctc_score / _spot / _align_wild and of the MWER loss travel to e->ctc_pair through the pinned
+// e->h_pair, guarded by its own event (a call that failed midway may have left a copy in flight).  pair_tables_reserve: both
+// buffers hold `words` words (and one more, so that an empty tail still has an address) and e->h_pair is free to be
+// written; pair_tables_send: the first `words` words go to the device on the engine's stream.
+int pair_tables_reserve(tfk_engine* e, size_t words) {
+  CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, words + 1));
+  if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
+  return grow_pinned(e, &e->h_pair, &e->h_pair_cap, words + 1, /*slack=*/true, /*sync=*/false);
+}
+int pair_tables_send(tfk_engine* e, size_t words) {
+  if (words > 0) HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, words * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
+  return 0;
+}
+// The same in one step, from the caller's arrays: [tab `words` words | labels `total` words | flags `nflags` bytes]
+int stage_pair_tables(tfk_engine* e, const int32_t* tab, size_t words, const int32_t* labels, size_t total,
+                      const uint8_t* flags, size_t nflags) {
+  const size_t flag_words = (nflags + 3) / 4, all = words + total + flag_words;
+  CHK(pair_tables_reserve(e, all));
+  if (words > 0) memcpy(e->h_pair, tab, words * sizeof(int32_t));
+  if (total > 0) memcpy(e->h_pair + words, labels, total * sizeof(int32_t));
+  if (flag_words > 0) {
+    e->h_pair[all - 1] = 0;
+    memcpy(e->h_pair + words + total, flags, nflags);
+  }
+  return pair_tables_send(e, all);
+}
 // Validate the utterance / label tables of a CTC batch and stage (seg, lab_off, labels) in e->ctc_seg / ctc_lab_off /
 // ctc_lab (and, with c.wild, the gap flags in e->ctc_wild) on the engine's stream.  Labels follow tf.nn.ctc_loss: values in
 // [0, O - 1) (the blank is the LAST class), at most kCtcMaxLabels per utterance.  label_len may be NULL only when
@@ -1627,9 +1635,9 @@ int ctc_stage(tfk_engine* e, const CtcSpec& c, int T, bool need_labels, int* max
   return 0;
 }
 
-// Loss + dLogits of one CTC micro-batch (logits already in e->logits).  Replaces compute_loss of the reference's
-// CTCTrainer (trainer.py:533-570); batch_loss += sum of -log p, num_frames += number of labels (trainer.py:126-133).
-int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
+// The staged tables and the engine's lattice buffers (grown to T frames of the batch's state stride) as the CtcBatch of the
+// plain, the wildcard and the MMI loss.
+int ctc_engine_batch(tfk_engine* e, const CtcSpec& c, int T, int train, CtcBatch* batch) {
   int max_labels = 0;
   CHK(ctc_stage(e, c, T, true, &max_labels));
   const int sext = ctc_state_stride(max_labels);
@@ -1643,13 +1651,22 @@ int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
     CHK(grow(e, &e->ctc_bb, &e->ctc_cap_bb, (size_t)T * sext));
     CHK(grow(e, &e->ctc_offb, &e->ctc_cap_offb, (size_t)T));
   }
-  CtcBatch b;
+  CtcBatch& b = *batch;
   b.logits = e->logits; b.ld = e->ldO; b.post = e->post; b.lse = e->ctc_lse;
   b.seg = e->ctc_seg; b.labels = e->ctc_lab; b.lab_off = e->ctc_lab_off;
   b.U = c.U; b.T = T; b.O = e->O; b.sext = sext;
   b.lp = e->ctc_lp; b.ab = e->ctc_ab; b.bb = e->ctc_bb; b.utt_loss = e->ctc_utt_loss;
   b.off = e->ctc_off; b.offb = e->ctc_offb; b.logz = e->ctc_logz;
   if (c.wild) { b.wild = e->ctc_wild; b.wild_cost = c.wild_cost; }
+  return 0;
+}
+
+// Loss + dLogits of one CTC micro-batch (logits already in e->logits).  Replaces compute_loss of the reference's
+// CTCTrainer (trainer.py:533-570); batch_loss += sum of -log p, num_frames += number of labels (trainer.py:126-133).
+int ctc_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
+  CtcBatch b;
+  CHK(ctc_engine_batch(e, c, T, train, &b));
+  const int sext = b.sext;
   {
     ProfScope ps(e, KF_SOFTMAX_XENT, 0, 8.0 * T * e->O + 16.0 * T * sext);
     Twin tw;
@@ -1674,23 +1691,18 @@ int mwer_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const 
     return fail(-1, "CTC MWER: utt_len / ref_len / hyp_count is NULL or no utterances");
   if (!(mw->ctc_weight >= 0.f) || !std::isfinite(mw->ctc_weight))
     return fail(-1, "CTC MWER: ctc_weight %g is negative or not finite", (double)mw->ctc_weight);
-  int64_t P64 = 0, PR = 0, frames = 0, ref_total = 0;
-  int max_ref = 0;
-  for (int u = 0; u < U; ++u) {
-    if (mw->hyp_count[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative hypothesis count", u);
-    if (utt_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative length", u);
+  int64_t PR = 0, ref_total = 0;
+  int P = 0, max_ref = 0;
+  CHK(pairs_count("CTC MWER", "hypothesis", mw->hyp_count, utt_len, U, kCtcScoreMaxPairs, &P));
+  for (int u = 0; u < U; ++u) {  // (the references are worded on their own: "reference length", "reference label")
     if (ref_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative reference length", u);
     if (ref_len[u] > kCtcMaxLabels)
       return fail(-1, "CTC MWER: utterance %d has a reference of %d labels (limit %d)", u, ref_len[u], kCtcMaxLabels);
-    P64 += mw->hyp_count[u];
-    if (P64 > kCtcScoreMaxPairs)
-      return fail(-1, "CTC MWER: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
     PR += (int64_t)(mw->hyp_count[u] + (mw->ctc_weight > 0.f ? 1 : 0)) * utt_len[u];
-    frames += utt_len[u];
     ref_total += ref_len[u];
     max_ref = ref_len[u] > max_ref ? ref_len[u] : max_ref;
   }
-  if (frames != T) return fail(-1, "CTC MWER: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
+  CHK(utt_len_check("CTC MWER", utt_len, U, T));
   if (ref_total > 0 && !ref_labels) return fail(-1, "CTC MWER: ref_labels is NULL");
   {
     int64_t at = 0;
@@ -1699,24 +1711,14 @@ int mwer_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const 
         if (ref_labels[at] < 0 || ref_labels[at] >= e->O - 1)
           return fail(-1, "CTC MWER: utterance %d: reference label %d outside [0, %d)", u, ref_labels[at], e->O - 1);
   }
-  const int P = (int)P64;
   if (P > 0 && !mw->hyp_len) return fail(-1, "CTC MWER: hyp_len is NULL");
   int max_hyp = 0;
   int64_t first = 0;
-  for (int u = 0, p = 0; u < U; ++u)
-    for (int h = 0; h < mw->hyp_count[u]; ++h, ++p) {
-      const int32_t n = mw->hyp_len[p];
-      if (n < 0) return fail(-1, "CTC MWER: utterance %d, hypothesis %d has a negative length", u, h);
-      if (n > kCtcMaxLabels)
-        return fail(-1, "CTC MWER: utterance %d, hypothesis %d has %d labels (limit %d)", u, h, n, kCtcMaxLabels);
-      if (n > 0 && !mw->hyp_labels) return fail(-1, "CTC MWER: hyp_labels is NULL");
-      for (int32_t i = 0; i < n; ++i)
-        if (mw->hyp_labels[first + i] < 0 || mw->hyp_labels[first + i] >= e->O - 1)
-          return fail(-1, "CTC MWER: utterance %d, hypothesis %d: label %d outside [0, %d)", u, h, mw->hyp_labels[first + i],
-                      e->O - 1);
-      first += n;
-      max_hyp = n > max_hyp ? n : max_hyp;
-    }
+  if (!mw->hyp_labels)  // (the shared check would say "labels is NULL")
+    for (int p = 0; p < P; ++p)
+      if (mw->hyp_len[p] > 0) return fail(-1, "CTC MWER: hyp_labels is NULL");
+  CHK(pairs_build("CTC MWER", "hypothesis", false, mw->hyp_count, U, mw->hyp_len, mw->hyp_labels, nullptr, e->O, kCtcMaxLabels,
+                  nullptr, nullptr, &max_hyp, &first));
   if (first + ref_total > 0x7fffffff) return fail(-1, "CTC MWER: more than 2^31 - 1 labels in one call");
   mw->P = P;
   mw->max_hyp = max_hyp;
@@ -1742,16 +1744,11 @@ int ctc_mwer_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   const int sext = ctc_state_stride(mw.max_labels);
   const size_t lattice = (ctc_mwer_scratch_bytes(T, NP, P, mw.PR, sext) + 15) & ~(size_t)15;
   CHK(grow(e, &e->ctc_mw, &e->ctc_cap_mw, lattice + ((size_t)c.U + 2 * (size_t)P + 4) * sizeof(float)));
-  CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, tab_words + total + 1));
-  // pinned staging, guarded by its own event, as tfk_ctc_score stages its pair tables
-  if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
-  CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, tab_words + total + 1, /*slack=*/true, /*sync=*/false));
+  CHK(pair_tables_reserve(e, tab_words + total));  // (the table is written straight into the pinned buffer)
   ctc_mwer_table(c.utt_len, c.U, mw.hyp_count, mw.hyp_len, c.label_len, NP > P, e->h_pair);
   if (mw.hyp_total > 0) memcpy(e->h_pair + tab_words, mw.hyp_labels, (size_t)mw.hyp_total * sizeof(int32_t));
   if (mw.ref_total > 0) memcpy(e->h_pair + tab_words + mw.hyp_total, c.labels, (size_t)mw.ref_total * sizeof(int32_t));
-  HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, (tab_words + total) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
+  CHK(pair_tables_send(e, tab_words + total));
   CtcMwer m = {};
   m.logits = e->logits; m.ld = e->ldO; m.O = e->O; m.T = T; m.U = c.U; m.seg = e->ctc_seg;
   m.P = P; m.NP = NP; m.PR = mw.PR; m.sext = sext; m.max_hyp = mw.max_hyp; m.ctc_weight = mw.ctc_weight;
@@ -1795,16 +1792,14 @@ int mmi_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const i
   if (!(mm.ctc_weight >= 0.f) || !std::isfinite(mm.ctc_weight))
     return fail(-1, "CTC MMI: ctc_weight %g is negative or not finite", (double)mm.ctc_weight);
   if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC MMI: utt_len / label_len is NULL or no utterances");
-  int64_t frames = 0, total = 0;
+  CHK(utt_len_check("CTC MMI", utt_len, U, T));
+  int64_t total = 0;
   for (int u = 0; u < U; ++u) {
-    if (utt_len[u] < 0) return fail(-1, "CTC MMI: utterance %d has a negative length", u);
     if (label_len[u] < 0) return fail(-1, "CTC MMI: utterance %d has a negative reference length", u);
     if (label_len[u] > kCtcMaxLabels)
       return fail(-1, "CTC MMI: utterance %d has a reference of %d labels (limit %d)", u, label_len[u], kCtcMaxLabels);
-    frames += utt_len[u];
     total += label_len[u];
   }
-  if (frames != T) return fail(-1, "CTC MMI: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
   if (total > 0x7fffffff) return fail(-1, "CTC MMI: more than 2^31 - 1 labels in one call");
   if (total > 0 && !labels) return fail(-1, "CTC MMI: labels is NULL");
   for (int64_t i = 0; i < total; ++i)
@@ -1820,25 +1815,9 @@ int mmi_check(const tfk_engine* e, const int32_t* utt_len, int U, int T, const i
 int ctc_mmi_loss(tfk_engine* e, const CtcSpec& c, int T, int train) {
   const MmiSpec& mm = *c.mmi;
   const CtcDenGraph& g = *e->den;
-  int max_labels = 0;
-  CHK(ctc_stage(e, c, T, true, &max_labels));
-  const int sext = ctc_state_stride(max_labels);
-  CHK(grow(e, &e->ctc_utt_loss, &e->ctc_cap_loss, (size_t)c.U));
-  CHK(grow(e, &e->ctc_lp, &e->ctc_cap_lp, (size_t)T * sext));
-  CHK(grow(e, &e->ctc_ab, &e->ctc_cap_ab, (size_t)T * sext));
-  CHK(grow(e, &e->ctc_lse, &e->ctc_cap_rows, (size_t)T));
-  CHK(grow(e, &e->ctc_off, &e->ctc_cap_offrows, (size_t)T));
-  CHK(grow(e, &e->ctc_logz, &e->ctc_cap_logz, (size_t)c.U));
-  if (train) {
-    CHK(grow(e, &e->ctc_bb, &e->ctc_cap_bb, (size_t)T * sext));
-    CHK(grow(e, &e->ctc_offb, &e->ctc_cap_offb, (size_t)T));
-  }
   CtcBatch b;
-  b.logits = e->logits; b.ld = e->ldO; b.post = e->post; b.lse = e->ctc_lse;
-  b.seg = e->ctc_seg; b.labels = e->ctc_lab; b.lab_off = e->ctc_lab_off;
-  b.U = c.U; b.T = T; b.O = e->O; b.sext = sext;
-  b.lp = e->ctc_lp; b.ab = e->ctc_ab; b.bb = e->ctc_bb; b.utt_loss = e->ctc_utt_loss;
-  b.off = e->ctc_off; b.offb = e->ctc_offb; b.logz = e->ctc_logz;
+  CHK(ctc_engine_batch(e, c, T, train, &b));
+  const int sext = b.sext;
   CtcDen d = {};
   d.tab = e->den_tab; d.logw = e->den_logw;
   d.O = g.O; d.S = g.S; d.A = g.A; d.K = g.K; d.N = g.N; d.start = g.start;
@@ -2219,8 +2198,11 @@ int check_seg_utts(const tfk_engine* e, const char* who, const int32_t* utt_len,
 }  // namespace
 
 namespace tfk {
-// the other translation units of the library (features.hip) report through the same thread-local message
-int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+// every translation unit of the library reports through this thread-local message (tfk_error.h)
+int set_error(int code, const char* msg) {
+  g_err = msg;
+  return code;
+}
 }  // namespace tfk
 
 extern "C" {
@@ -2535,24 +2517,9 @@ static int ctc_wild_entry(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
   if (!(penalty >= 0.f) || !std::isfinite(penalty))
     return fail(-1, "CTC wild: penalty %g is negative or not finite", (double)penalty);
   if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC wild: utt_len / label_len is NULL or no utterances");
-  int64_t frames = 0, first = 0;
-  for (int u = 0; u < U; ++u) {
-    const int32_t n = label_len[u];
-    if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC wild: utterance %d has a negative length", u);
-    if (n > kCtcMaxLabels) return fail(-1, "CTC wild: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
-    if (n > 0 && !labels) return fail(-1, "CTC wild: labels is NULL");
-    for (int32_t i = 0; i < n; ++i)
-      if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
-        return fail(-1, "CTC wild: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
-    if (wild)
-      for (int32_t g = 0; g <= n; ++g)
-        if (wild[first + u + g] > 1)
-          return fail(-1, "CTC wild: utterance %d, gap %d: wild is %d, not 0 or 1", u, g, (int)wild[first + u + g]);
-    frames += utt_len[u];
-    first += n;
-    if (first > 0x7fffffff - U) return fail(-1, "CTC wild: more than 2^31 - 1 labels and flags in one call");
-  }
-  if (frames != T) return fail(-1, "CTC wild: utterance lengths sum to %lld, expected T = %d", (long long)frames, T);
+  int64_t total = 0;
+  CHK(transcripts_check("CTC wild", utt_len, label_len, labels, wild, U, e->O, kCtcMaxLabels, T, &total));
+  if (total > 0x7fffffff - U) return fail(-1, "CTC wild: more than 2^31 - 1 labels and flags in one call");
   CtcSpec c = {utt_len, U, labels, label_len};
   c.wild = wild;
   c.wild_cost = penalty;
@@ -2661,29 +2628,6 @@ int tfk_eval_accumulate_ctc_mmi_raw(tfk_engine* e, const float* raw, int64_t ldr
   return ctc_mmi_entry(e, raw, ldraw, T, utt_len, U, labels, label_len, lm_scale, ctc_weight, flags, 0, &r);
 }
 
-// Validation shared by tfk_ctc_den_set and tfk_ctc_mmi_logits (host tables): the rules of tfk_ctc_graph_set, then the limits of
-// the composed lattice -- all before anything is allocated.
-static int den_tables_check(const char* who, const float* weight, const int32_t* next, int O, int64_t num_states, int start) {
-  if (num_states < 1) return fail(-1, "%s: num_states %lld < 1", who, (long long)num_states);
-  if (const char* why = ctc_den_graph_limits(O, num_states, 0))
-    return fail(-1, "%s (%lld states over %d outputs): %s", who, (long long)num_states, O, why);
-  if (start < 0 || start >= num_states) return fail(-1, "%s: start %d outside [0, %lld)", who, start, (long long)num_states);
-  const size_t n = (size_t)num_states * (size_t)O;
-  int64_t arcs = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const float w = weight[i];
-    if (std::isnan(w) || w == INFINITY) return fail(-1, "%s: entry %zu of weight is NaN or +inf", who, i);
-    if (i % O != (size_t)O - 1 && w > -INFINITY) {
-      if (next[i] < 0 || next[i] >= num_states)
-        return fail(-1, "%s: entry %zu of next is %d, outside [0, %lld)", who, i, next[i], (long long)num_states);
-      ++arcs;
-    }
-  }
-  if (const char* why = ctc_den_graph_limits(O, num_states, arcs))
-    return fail(-1, "%s (%lld states + %lld arcs = %lld composed states, limit %d): %s", who, (long long)num_states,
-                (long long)arcs, (long long)(num_states + arcs), kCtcDenMaxStates, why);
-  return 0;
-}
 // The denominator graph: a model of its own beside the decoder's.  Everything is validated, compiled and uploaded before the
 // engine's model is touched: any failure leaves the old one in force.
 int tfk_ctc_den_set(tfk_engine* e, const float* weight, const int32_t* next, int32_t num_states, int32_t start) {
@@ -2694,7 +2638,7 @@ int tfk_ctc_den_set(tfk_engine* e, const float* weight, const int32_t* next, int
   float* d_w = nullptr;
   if (weight) {
     if (!next) return fail(-1, "tfk_ctc_den_set: next is NULL");
-    CHK(den_tables_check("tfk_ctc_den_set", weight, next, e->O, num_states, start));
+    CHK(den_tables_check("tfk_ctc_den_set", weight, next, e->O, num_states, start, ctc_den_graph_limits, kCtcDenMaxStates));
     g = new CtcDenGraph();
     ctc_den_compile(weight, next, num_states, e->O, start, g);
     hipError_t got = hipMalloc((void**)&d_tab, g->tab.size() * sizeof(int32_t));
@@ -2728,162 +2672,6 @@ int tfk_ctc_den_info(tfk_engine* e, int32_t* num_states, int32_t* num_arcs, int3
   if (num_arcs) *num_arcs = g.A;
   if (num_groups) *num_groups = g.K;
   if (residence) *residence = ctc_den_residence(g.O, g.N, g.S, g.A, g.K);
-  return 0;
-}
-
-int tfk_ctc_mmi_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                       const int32_t* labels, const int32_t* lab_off, const float* weight_dev, const int32_t* next_dev,
-                       int32_t num_states, int32_t start, float lm_scale, float ctc_weight, float* utt_loss, float* logz,
-                       float* dlogits, int64_t ldd) {
-  hipStream_t st = (hipStream_t)stream;
-  if (U < 0) return fail(-1, "U = %d < 0", U);
-  if (!(lm_scale >= 0.f) || !std::isfinite(lm_scale)) return fail(-1, "CTC MMI: lm_scale %g is negative or not finite", (double)lm_scale);
-  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight))
-    return fail(-1, "CTC MMI: ctc_weight %g is negative or not finite", (double)ctc_weight);
-  if (!weight_dev || !next_dev) return fail(-1, "CTC MMI: no denominator graph (weight / next is NULL)");
-  if (num_states < 1) return fail(-1, "CTC MMI: num_states %d < 1", num_states);
-  if (const char* why = ctc_den_graph_limits(O, num_states, 0))
-    return fail(-1, "CTC MMI (%d states over %d outputs): %s", num_states, O, why);
-  if (U == 0) return 0;
-  if (T <= 0) return fail(-1, "CTC MMI: empty batch (T = %d)", T);
-  if (!seg || !lab_off || !utt_loss || !logz || (T > 0 && !logits)) return fail(-1, "logits / seg / lab_off / utt_loss / logz is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
-  // The shapes and the graph live on the device: they come back first (one synchronisation)
-  const size_t ng = (size_t)num_states * (size_t)O;
-  std::vector<int32_t> h_seg((size_t)U + 1), h_off((size_t)U + 1), h_next(ng);
-  std::vector<float> h_w(ng);
-  HIPCHK(hipMemcpyAsync(h_seg.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_off.data(), lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_w.data(), weight_dev, ng * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_next.data(), next_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  int max_labels = 0;
-  for (int u = 0; u < U; ++u) {
-    if (h_seg[u + 1] < h_seg[u]) return fail(-1, "CTC MMI: utterance %d has a negative length", u);
-    if (h_off[u + 1] < h_off[u]) return fail(-1, "CTC MMI: utterance %d has a negative reference length", u);
-    max_labels = std::max(max_labels, h_off[u + 1] - h_off[u]);
-  }
-  if (h_seg[0] != 0 || h_seg[U] != T) return fail(-1, "CTC MMI: seg = [%d, %d] is not [0, T = %d]", h_seg[0], h_seg[U], T);
-  if (h_off[0] != 0) return fail(-1, "CTC MMI: lab_off[0] = %d is not 0", h_off[0]);
-  if (max_labels > kCtcMaxLabels) return fail(-1, "CTC MMI: %d labels in one utterance (limit %d)", max_labels, kCtcMaxLabels);
-  const int total = h_off[U];
-  if (total > 0 && !labels) return fail(-1, "CTC MMI: labels is NULL");
-  std::vector<int32_t> h_lab((size_t)(total > 0 ? total : 1));
-  if (total > 0) {
-    HIPCHK(hipMemcpyAsync(h_lab.data(), labels, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  for (int i = 0; i < total; ++i)
-    if (h_lab[i] < 0 || h_lab[i] >= O - 1) return fail(-1, "CTC MMI: label %d outside [0, %d)", h_lab[i], O - 1);
-  CHK(den_tables_check("CTC MMI", h_w.data(), h_next.data(), O, num_states, start));
-  CtcDenGraph g;
-  ctc_den_compile(h_w.data(), h_next.data(), num_states, O, start, &g);
-  if (const char* why = ctc_den_limits(O, T, U, g.N))
-    return fail(-1, "CTC MMI (O %d, T %d, U %d, %d composed states): %s", O, T, U, g.N, why);
-  std::vector<double> gy((size_t)U);
-  for (int u = 0; u < U; ++u) gy[u] = ctc_den_walk(g, h_lab.data() + h_off[u], h_off[u + 1] - h_off[u]);
-  const bool train = dlogits != nullptr;
-  const int sext = ctc_state_stride(max_labels);
-  CtcDen d = {};
-  d.O = g.O; d.S = g.S; d.A = g.A; d.K = g.K; d.N = g.N; d.start = g.start;
-  d.ld = (int)ld; d.T = T; d.U = U; d.seg = seg; d.lm_scale = lm_scale; d.ctc_weight = ctc_weight;
-  // the call's own scratch, released in stream order:
-  // [G(y) U doubles | off T, offb T, logz U doubles | post T ld, g T ld, lp / ab / bb T sext, lse T, CTC losses U floats |
-  //  tab | logw | the denominator's lattices]
-  const size_t t = (size_t)(T > 0 ? T : 0), u = (size_t)U;
-  const size_t dbl = (2 * u + 2 * t) * sizeof(double);
-  const size_t flt = (2 * t * (size_t)ld + 3 * t * (size_t)sext + t + u + g.logw.size()) * sizeof(float);
-  const size_t ints = (g.tab.size() * sizeof(int32_t) + 15) & ~(size_t)15;
-  const size_t head = (dbl + flt + ints + 15) & ~(size_t)15;
-  unsigned char* scratch = nullptr;
-  HIPCHK(hipMallocAsync((void**)&scratch, head + ctc_den_scratch_bytes(d, train), st));
-  double* dp = reinterpret_cast<double*>(scratch);
-  double* d_gy = dp;
-  CtcBatch b;
-  b.logits = logits; b.ld = (int)ld; b.seg = seg; b.labels = labels; b.lab_off = lab_off;
-  b.U = U; b.T = T; b.O = O; b.sext = sext;
-  b.off = dp + u; b.offb = b.off + t; b.logz = b.offb + t;
-  float* fp = reinterpret_cast<float*>(b.logz + u);
-  b.post = fp;                  fp += t * (size_t)ld;
-  float* gbuf = fp;             fp += t * (size_t)ld;
-  b.lp = fp;                    fp += t * (size_t)sext;
-  b.ab = fp;                    fp += t * (size_t)sext;
-  b.bb = fp;                    fp += t * (size_t)sext;
-  b.lse = fp;                   fp += t;
-  b.utt_loss = fp;              fp += u;
-  float* d_logw = fp;           fp += g.logw.size();
-  int32_t* d_tab = reinterpret_cast<int32_t*>(fp);
-  hipError_t copied = hipMemcpyAsync(d_gy, gy.data(), u * sizeof(double), hipMemcpyHostToDevice, st);
-  if (copied == hipSuccess)
-    copied = hipMemcpyAsync(d_logw, g.logw.data(), g.logw.size() * sizeof(float), hipMemcpyHostToDevice, st);
-  if (copied == hipSuccess)
-    copied = hipMemcpyAsync(d_tab, g.tab.data(), g.tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (copied == hipSuccess) copied = hipStreamSynchronize(st);  // (the tables leave pageable host memory)
-  hipError_t launched = copied;
-  if (copied == hipSuccess) {
-    d.tab = d_tab; d.logw = d_logw; d.post = b.post; d.gy = d_gy; d.utt_loss = utt_loss;
-    ctc_den_carve(scratch + head, &d, train);
-    ctc_loss_grad(st, b, gbuf, train ? 1 : 0, Twin());
-    ctc_den_sweep(st, d, b, train, logz);
-    if (train) ctc_den_grad(st, d, gbuf, (int)ld, dlogits, (int)ldd, 0, T, Twin());
-    launched = hipGetLastError();
-  }
-  const hipError_t freed = hipFreeAsync(scratch, st);  // also when a copy or the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
-
-int tfk_ctc_wild_loss_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                             const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, float penalty, float* utt_loss,
-                             float* dlogits, int64_t ldd) {
-  hipStream_t st = (hipStream_t)stream;
-  if (U < 0) return fail(-1, "U = %d < 0", U);
-  if (U == 0) return 0;
-  if (T <= 0) return fail(-1, "CTC wild: empty batch (T = %d)", T);
-  if (!logits || !seg || !lab_off || !utt_loss) return fail(-1, "logits / seg / lab_off / utt_loss is NULL");
-  if (O < 1 || ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
-  if (dlogits == logits && dlogits && ldd != ld) return fail(-1, "dlogits in place needs ldd == ld");
-  std::vector<int32_t> h(2 * ((size_t)U + 1));  // (the two offset tables come back first, as tfk_ctc_align_logits)
-  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  int max_labels = 0;
-  for (int u = 0; u < U; ++u) {
-    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
-    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC wild: utterance %d has a negative length", u);
-    max_labels = n > max_labels ? n : max_labels;
-  }
-  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC wild: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
-  if (h[U + 1] < 0) return fail(-1, "CTC wild: lab_off[0] = %d < 0", h[U + 1]);
-  if (max_labels > kCtcMaxLabels) return fail(-1, "CTC wild: %d labels in one utterance (limit %d)", max_labels, kCtcMaxLabels);
-  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC wild: labels is NULL");
-  const bool train = dlogits != nullptr;
-  const int sext = ctc_state_stride(max_labels);
-  // the call's own scratch, released in stream order: [off T, offb T, logz U doubles | post T ld, lp / ab / bb T sext, lse T]
-  const size_t t = (size_t)T, u = (size_t)U;
-  const size_t bytes = (2 * t + u) * sizeof(double) + (t * (size_t)ld + 3 * t * (size_t)sext + t) * sizeof(float);
-  unsigned char* scratch = nullptr;
-  HIPCHK(hipMallocAsync((void**)&scratch, bytes, st));
-  CtcBatch b;
-  b.logits = logits; b.ld = (int)ld; b.seg = seg; b.labels = labels; b.lab_off = lab_off;
-  b.U = U; b.T = T; b.O = O; b.sext = sext;
-  b.off = reinterpret_cast<double*>(scratch); b.offb = b.off + t; b.logz = b.offb + t;
-  float* fp = reinterpret_cast<float*>(b.logz + u);
-  b.post = fp;                  fp += t * (size_t)ld;
-  b.lp = fp;                    fp += t * (size_t)sext;
-  b.ab = fp;                    fp += t * (size_t)sext;
-  b.bb = fp;                    fp += t * (size_t)sext;
-  b.lse = fp;
-  b.utt_loss = utt_loss;
-  b.wild = wild; b.wild_cost = penalty;
-  ctc_loss_grad_rows(st, b, dlogits, (int)ldd, h[0], h[U] - h[0], train ? 1 : 0);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(scratch, st);  // also when the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
   return 0;
 }
 
@@ -3466,94 +3254,6 @@ int tfk_ctc_beam_topk_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_
   return ctc_beam_impl(e, raw, ldraw, T, utt_len, U, beam_width, top_paths, ref_labels, ref_len, hyp, hyp_len, score, edits,
                        flags, &r, &lm, label_topk);
 }
-static int ctc_beam_logits_impl(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
-                                int32_t U, int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len,
-                                float* score, const CtcLm* lm, float* am_score, int label_topk = 0) {
-  if (label_topk) {
-    if (const char* why = ctc_beam_topk_limits(O, T, U, beam_width, top_paths, label_topk))
-      return fail(-1, "CTC beam search (beam_width %d, top_paths %d, label_topk %d, O %d, T %d, U %d): %s", beam_width,
-                  top_paths, label_topk, O, T, U, why);
-  } else if (const char* why = ctc_beam_limits(O, T, U, beam_width, top_paths)) {
-    return fail(-1, "CTC beam search (beam_width %d, top_paths %d, O %d, T %d, U %d): %s", beam_width, top_paths, O, T, U, why);
-  }
-  if (U == 0) return 0;
-  if (!seg || !hyp_len || !score || (T > 0 && (!logits || !hyp))) return fail(-1, "logits / seg / hyp / hyp_len / score is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  unsigned long long* trie = nullptr;  // the call's own scratch, released in stream order
-  HIPCHK(hipMallocAsync((void**)&trie, ctc_beam_scratch_words(T, U, beam_width) * sizeof(unsigned long long),
-                        (hipStream_t)stream));
-  uint32_t* pre = nullptr;
-  if (label_topk && T > 0) {
-    const hipError_t got = hipMallocAsync((void**)&pre, ctc_beam_topk_scratch_words(T) * sizeof(uint32_t), (hipStream_t)stream);
-    if (got != hipSuccess) {
-      (void)hipFreeAsync(trie, (hipStream_t)stream);
-      HIPCHK(got);
-    }
-  }
-  if (label_topk) ctc_beam_topk_rows((hipStream_t)stream, logits, (int)ld, O, T, label_topk, pre);
-  if (label_topk)
-    ctc_beam_topk_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, label_topk, trie, pre, hyp,
-                         hyp_len, score, lm, am_score);
-  else
-    ctc_beam_search((hipStream_t)stream, logits, (int)ld, O, T, seg, U, beam_width, top_paths, trie, hyp, hyp_len, score, lm,
-                    am_score);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(trie, (hipStream_t)stream);  // also when the launch failed
-  const hipError_t freed_pre = pre ? hipFreeAsync(pre, (hipStream_t)stream) : hipSuccess;
-  HIPCHK(launched);
-  HIPCHK(freed);
-  HIPCHK(freed_pre);
-  return 0;
-}
-int tfk_ctc_beam_topk_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                             int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* lm_dev, int32_t order,
-                             float lm_weight, float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score,
-                             float* am_score) {
-  if (label_topk < 1) return fail(-1, "tfk_ctc_beam_topk_logits: label_topk outside [1, 63]");
-  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "tfk_ctc_beam_topk_logits: flags %d, it takes 0 or TFK_CTC_LM_EOS", flags);
-  if (!lm_dev) {
-    if (flags) return fail(-1, "tfk_ctc_beam_topk_logits: TFK_CTC_LM_EOS without a table");
-    return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, nullptr, am_score,
-                                label_topk);
-  }
-  if (order < 1 || order > kCtcLmMaxOrder)
-    return fail(-1, "tfk_ctc_beam_topk_logits: order %d outside [1, %d]", order, kCtcLmMaxOrder);
-  if (O >= 2 && O <= kCtcTopkMaxClasses && ctc_lm_entries(O, order) > kCtcLmMaxEntries)
-    return fail(-1, "tfk_ctc_beam_topk_logits: a table of order %d over %d outputs has more than %zu entries", order, O,
-                kCtcLmMaxEntries);
-  const CtcLm lm = {lm_dev, order, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0};
-  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score,
-                              label_topk);
-}
-int tfk_ctc_beam_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                        int32_t beam_width, int32_t top_paths, int32_t* hyp, int32_t* hyp_len, float* score) {
-  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, nullptr, nullptr);
-}
-int tfk_ctc_beam_lm_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                           int32_t beam_width, int32_t top_paths, const float* lm_dev, int32_t order, float lm_weight,
-                           float label_bonus, int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score) {
-  if (order < 1 || order > kCtcLmMaxOrder) return fail(-1, "tfk_ctc_beam_lm_logits: order %d outside [1, %d]", order, kCtcLmMaxOrder);
-  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "tfk_ctc_beam_lm_logits: flags %d, it takes 0 or TFK_CTC_LM_EOS", flags);
-  if (!lm_dev) return fail(-1, "tfk_ctc_beam_lm_logits: the table is NULL");
-  const CtcLm lm = {lm_dev, order, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0};
-  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score);
-}
-int tfk_ctc_beam_graph_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
-                              int32_t U, int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* weight_dev,
-                              const int32_t* next_dev, int32_t num_states, int32_t start, float lm_weight, float label_bonus,
-                              int flags, int32_t* hyp, int32_t* hyp_len, float* score, float* am_score) {
-  if (label_topk < 0) return fail(-1, "tfk_ctc_beam_graph_logits: label_topk outside [0, 63]");
-  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "tfk_ctc_beam_graph_logits: flags %d, it takes 0 or TFK_CTC_LM_EOS", flags);
-  if (!weight_dev || !next_dev) return fail(-1, "tfk_ctc_beam_graph_logits: weight / next is NULL");
-  if (num_states < 1 || start < 0 || start >= num_states)
-    return fail(-1, "tfk_ctc_beam_graph_logits: start %d outside [0, num_states = %d)", start, num_states);
-  if (O >= 2 && (size_t)num_states * (size_t)O > kCtcGraphMaxEntries)
-    return fail(-1, "tfk_ctc_beam_graph_logits: a graph of %d states over %d outputs has more than %zu entries per table",
-                num_states, O, kCtcGraphMaxEntries);
-  const CtcLm lm = {weight_dev, 0, lm_weight, label_bonus, (flags & TFK_CTC_LM_EOS) != 0, next_dev, num_states, start};
-  return ctc_beam_logits_impl(stream, logits, ld, O, T, seg, U, beam_width, top_paths, hyp, hyp_len, score, &lm, am_score,
-                              label_topk);
-}
 // Forced alignment (the Viterbi path of every utterance's known label sequence; the contract: tfkaldi_hip.h):
 // evaluation-mode forward as tfk_posteriors, then ctc_viterbi_align on the logits in HBM; T + U words go back to the host.
 static int ctc_align_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
@@ -3562,19 +3262,8 @@ static int ctc_align_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
   CHK(decode_args(e, "tfk_ctc_align", X, T, flags, raw));
   if (!ali || !score) return fail(-1, "ali / score is NULL");
   if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC align: utt_len / label_len is NULL or no utterances");
-  {  // what ctc_stage would refuse as well, with the utterance named
-    int64_t first = 0;
-    for (int u = 0; u < U; ++u) {
-      const int32_t n = label_len[u];
-      if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
-      if (n > kCtcMaxLabels) return fail(-1, "CTC align: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
-      if (n > 0 && !labels) return fail(-1, "CTC align: labels is NULL");
-      for (int32_t i = 0; i < n; ++i)
-        if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
-          return fail(-1, "CTC align: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
-      first += n;
-    }
-  }
+  int64_t total = 0;  // what ctc_stage would refuse as well, with the utterance named (the sum of the lengths is ctc_stage's)
+  CHK(transcripts_check("CTC align", utt_len, label_len, labels, nullptr, U, e->O, kCtcMaxLabels, -1, &total));
   const size_t back = (size_t)T + (size_t)U;  // [ali | score]
   int max_labels = 0;
   CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, labels, label_len}, true, back, 0, back, &max_labels, [&]() -> int {
@@ -3601,38 +3290,6 @@ int tfk_ctc_align_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T,
   CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_align_impl(e, raw, ldraw, T, utt_len, U, labels, label_len, ali, score, flags, &r);
 }
-int tfk_ctc_align_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                         const int32_t* labels, const int32_t* lab_off, int32_t* ali, float* score) {
-  if (U < 0) return fail(-1, "U = %d < 0", U);
-  if (U == 0) return 0;
-  if (!seg || !lab_off || !score || (T > 0 && (!logits || !ali))) return fail(-1, "logits / seg / lab_off / ali / score is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  // The register tile follows the longest label sequence, which only the device knows: the two offset tables come back
-  // first (2 (U + 1) words, one synchronisation); everything after that is stream-ordered.
-  std::vector<int32_t> h(2 * ((size_t)U + 1));
-  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
-                        (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  int max_labels = 0;
-  for (int u = 0; u < U; ++u) {
-    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
-    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
-    max_labels = n > max_labels ? n : max_labels;
-  }
-  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC align: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
-  if (const char* why = ctc_align_limits(O, T, U, max_labels)) return fail(-1, "CTC align (O %d, T %d, U %d): %s", O, T, U, why);
-  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC align: labels is NULL");
-  void* scratch = nullptr;  // the call's own scratch, released in stream order
-  const size_t bytes = ctc_align_scratch_bytes(T, max_labels);
-  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
-  ctc_viterbi_align((hipStream_t)stream, logits, (int)ld, O, T, seg, U, labels, lab_off, max_labels, scratch, ali, score);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
 // N-best rescoring (the exact log p(labels | x) of the caller's hypotheses and their label errors; the contract: tfkaldi_hip.h):
 // evaluation-mode forward as tfk_posteriors, then ctc_score (and label_edit_distance) on the logits in HBM; P or 2P words go
 // back to the host.  The references travel through ctc_stage as tfk_ctc_greedy's do; the pair tables are staged behind them.
@@ -3642,15 +3299,8 @@ static int ctc_score_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
   CHK(decode_args(e, "tfk_ctc_score", X, T, flags, raw));
   if (U <= 0 || !utt_len || !hyp_count) return fail(-1, "CTC score: utt_len / hyp_count is NULL or no utterances");
   if (edits && !ref_len) return fail(-1, "CTC score: edits without references (ref_len is NULL)");
-  int64_t P64 = 0;
-  for (int u = 0; u < U; ++u) {
-    if (hyp_count[u] < 0) return fail(-1, "CTC score: utterance %d has a negative hypothesis count", u);
-    if (utt_len[u] < 0) return fail(-1, "CTC score: utterance %d has a negative length", u);
-    P64 += hyp_count[u];
-    if (P64 > kCtcScoreMaxPairs)
-      return fail(-1, "CTC score: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
-  }
-  const int P = (int)P64;
+  int P = 0;
+  CHK(pairs_count("CTC score", "hypothesis", hyp_count, utt_len, U, kCtcScoreMaxPairs, &P));
   if (P > 0 && (!label_len || !score)) return fail(-1, "CTC score: label_len / score is NULL");
   std::vector<int32_t> tab(4 * (size_t)P + 1);  // [pair_utt | lab_off | reference start | reference length]
   int32_t* pair_utt = tab.data();
@@ -3658,29 +3308,16 @@ static int ctc_score_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
   int32_t* ref_at = lab_off + P + 1;
   int32_t* ref_cnt = ref_at + P;
   int max_hyp = 0;
+  // (at most 2^20 pairs of at most 511 labels: the offsets fit an int32)
+  CHK(pairs_build("CTC score", "hypothesis", false, hyp_count, U, label_len, labels, nullptr, e->O, kCtcMaxLabels, pair_utt,
+                  lab_off, &max_hyp));
   {
-    int p = 0;
-    int64_t first = 0, ref_first = 0;
-    lab_off[0] = 0;
-    for (int u = 0; u < U; ++u) {
+    int64_t ref_first = 0;
+    for (int u = 0, p = 0; u < U; ++u) {
       const int32_t rn = edits ? ref_len[u] : 0;
       for (int h = 0; h < hyp_count[u]; ++h, ++p) {
-        const int32_t n = label_len[p];
-        if (n < 0) return fail(-1, "CTC score: utterance %d, hypothesis %d has a negative length", u, h);
-        if (n > kCtcMaxLabels)
-          return fail(-1, "CTC score: utterance %d, hypothesis %d has %d labels (limit %d)", u, h, n, kCtcMaxLabels);
-        if (n > 0 && !labels) return fail(-1, "CTC score: labels is NULL");
-        for (int32_t i = 0; i < n; ++i)
-          if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
-            return fail(-1, "CTC score: utterance %d, hypothesis %d: label %d outside [0, %d)", u, h, labels[first + i],
-                        e->O - 1);
-        first += n;
-        if (first > 0x7fffffff) return fail(-1, "CTC score: more than 2^31 - 1 labels in one call");
-        pair_utt[p] = u;
-        lab_off[p + 1] = (int32_t)first;
         ref_at[p] = (int32_t)ref_first;
         ref_cnt[p] = rn;
-        max_hyp = n > max_hyp ? n : max_hyp;
       }
       if (rn > 0) ref_first += rn;  // (a negative reference length is ctc_stage's to refuse)
     }
@@ -3693,16 +3330,7 @@ static int ctc_score_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T,
   CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, ref_labels, edits ? ref_len : nullptr}, edits != nullptr,
                   2 * (size_t)P, 0, back, &max_ref, [&]() -> int {
     CHK(grow(e, &e->ctc_sc, &e->ctc_cap_sc, ctc_score_scratch_bytes(T)));
-    CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, tab_words + (total > 0 ? total : 1)));
-    // pinned staging, guarded by its own event (a call that failed midway may have left a copy in flight)
-    if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
-    CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, tab_words + total, /*slack=*/true, /*sync=*/false));
-    memcpy(e->h_pair, tab.data(), tab_words * sizeof(int32_t));
-    if (total > 0) memcpy(e->h_pair + tab_words, labels, total * sizeof(int32_t));
-    HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, (tab_words + total) * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
-    return 0;
+    return stage_pair_tables(e, tab.data(), tab_words, labels, total, nullptr, 0);
   }, [&] {
     const int32_t* d_utt = e->ctc_pair;
     const int32_t* d_off = d_utt + P;
@@ -3742,67 +3370,6 @@ int tfk_ctc_score_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T,
   return ctc_score_impl(e, raw, ldraw, T, utt_len, U, hyp_count, labels, label_len, ref_labels, ref_len, score, edits, flags,
                         &r);
 }
-int tfk_ctc_score_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                         const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off, float* score) {
-  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
-  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC score: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
-  if (P == 0) return 0;
-  if (U == 0) return fail(-1, "CTC score: %d pairs and no utterance", P);
-  if (!seg || !pair_utt || !lab_off || !score || (T > 0 && !logits))
-    return fail(-1, "logits / seg / pair_utt / lab_off / score is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  // The register tile follows the longest hypothesis, which only the device knows: the three small tables come back first
-  // (U + 2P + 2 words, one synchronisation); everything after that is stream-ordered.
-  std::vector<int32_t> h((size_t)U + 1 + 2 * (size_t)P + 1);
-  int32_t* h_utt = h.data() + U + 1;
-  int32_t* h_off = h_utt + P;
-  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  for (int u = 0; u < U; ++u)
-    if (h[u + 1] < h[u]) return fail(-1, "CTC score: utterance %d has a negative length", u);
-  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC score: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
-  int max_labels = 0;
-  for (int p = 0; p < P; ++p) {
-    const int32_t n = h_off[p + 1] - h_off[p];
-    if (n < 0) return fail(-1, "CTC score: pair %d has a negative length", p);
-    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC score: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
-    max_labels = n > max_labels ? n : max_labels;
-  }
-  if (h_off[0] < 0) return fail(-1, "CTC score: lab_off[0] = %d < 0", h_off[0]);
-  if (const char* why = ctc_score_limits(O, T, U, P, max_labels))
-    return fail(-1, "CTC score (O %d, T %d, U %d, P %d): %s", O, T, U, P, why);
-  if (h_off[P] > h_off[0] && !labels) return fail(-1, "CTC score: labels is NULL");
-  void* scratch = nullptr;  // the call's own scratch, released in stream order
-  const size_t bytes = ctc_score_scratch_bytes(T);
-  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
-  ctc_score((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, max_labels, scratch, score);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
-// The small tables of tfk_ctc_align_wild / tfk_ctc_spot in e->ctc_pair: [tab `words` words | labels `total` words | flags
-// `nflags` bytes], through the pinned staging of tfk_ctc_score's pair tables (guarded by its own event).
-static int stage_pair_tables(tfk_engine* e, const int32_t* tab, size_t words, const int32_t* labels, size_t total,
-                             const uint8_t* flags, size_t nflags) {
-  const size_t flag_words = (nflags + 3) / 4, all = words + total + flag_words;
-  CHK(grow(e, &e->ctc_pair, &e->ctc_cap_pair, all > 0 ? all : 1));
-  if (!e->ctc_pair_staged) HIPCHK(hipEventCreateWithFlags(&e->ctc_pair_staged, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(e->ctc_pair_staged));
-  CHK(grow_pinned(e, &e->h_pair, &e->h_pair_cap, all, /*slack=*/true, /*sync=*/false));
-  if (words > 0) memcpy(e->h_pair, tab, words * sizeof(int32_t));
-  if (total > 0) memcpy(e->h_pair + words, labels, total * sizeof(int32_t));
-  if (flag_words > 0) {
-    e->h_pair[all - 1] = 0;
-    memcpy(e->h_pair + words + total, flags, nflags);
-  }
-  if (all > 0) HIPCHK(hipMemcpyAsync(e->ctc_pair, e->h_pair, all * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipEventRecord(e->ctc_pair_staged, e->stream));
-  return 0;
-}
 // Alignment with wildcard gaps (the contract: tfkaldi_hip.h at tfk_ctc_align_wild): ctc_align_impl's recipe -- its checks, the
 // evaluation-mode forward, ctc_viterbi_align_wild on the logits in HBM -- plus the flags, which are checked here (the
 // utterance and the gap are named) and staged as the pair tables of tfk_ctc_score are; T + 2U words go back to the host.
@@ -3812,25 +3379,9 @@ static int ctc_align_wild_impl(tfk_engine* e, const float* X, int64_t ldx, int32
   CHK(decode_args(e, "tfk_ctc_align_wild", X, T, flags, raw));
   if (!ali || !score || !free_score) return fail(-1, "ali / score / free_score is NULL");
   if (U <= 0 || !utt_len || !label_len) return fail(-1, "CTC align: utt_len / label_len is NULL or no utterances");
-  size_t nflags = 0;
-  {
-    int64_t first = 0;
-    for (int u = 0; u < U; ++u) {
-      const int32_t n = label_len[u];
-      if (utt_len[u] < 0 || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
-      if (n > kCtcMaxLabels) return fail(-1, "CTC align: utterance %d has %d labels (limit %d)", u, n, kCtcMaxLabels);
-      if (n > 0 && !labels) return fail(-1, "CTC align: labels is NULL");
-      for (int32_t i = 0; i < n; ++i)
-        if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
-          return fail(-1, "CTC align: utterance %d: label %d outside [0, %d)", u, labels[first + i], e->O - 1);
-      if (wild)
-        for (int32_t g = 0; g <= n; ++g)
-          if (wild[first + u + g] > 1)
-            return fail(-1, "CTC align: utterance %d, gap %d: wild is %d, not 0 or 1", u, g, (int)wild[first + u + g]);
-      first += n;
-    }
-    nflags = wild ? (size_t)first + (size_t)U : 0;
-  }
+  int64_t total = 0;
+  CHK(transcripts_check("CTC align", utt_len, label_len, labels, wild, U, e->O, kCtcMaxLabels, -1, &total));
+  const size_t nflags = wild ? (size_t)total + (size_t)U : 0;
   const size_t back = (size_t)T + 2 * (size_t)U;  // [ali | score | free]
   int max_labels = 0;
   CHK(decode_pass(e, X, ldx, T, flags, raw, {utt_len, U, labels, label_len}, true, back, 0, back, &max_labels, [&]() -> int {
@@ -3862,40 +3413,6 @@ int tfk_ctc_align_wild_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32
   CHK(raw_spec(&r, utt_len, U, context_width, cmvn));
   return ctc_align_wild_impl(e, raw, ldraw, T, utt_len, U, labels, label_len, wild, ali, score, free_score, flags, &r);
 }
-int tfk_ctc_align_wild_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg,
-                              int32_t U, const int32_t* labels, const int32_t* lab_off, const uint8_t* wild, int32_t* ali,
-                              float* score, float* free_score) {
-  if (U < 0) return fail(-1, "U = %d < 0", U);
-  if (U == 0) return 0;
-  if (!seg || !lab_off || !score || !free_score || (T > 0 && (!logits || !ali)))
-    return fail(-1, "logits / seg / lab_off / ali / score / free_score is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  std::vector<int32_t> h(2 * ((size_t)U + 1));  // (the two offset tables come back first, as tfk_ctc_align_logits)
-  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipMemcpyAsync(h.data() + U + 1, lab_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
-                        (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  int max_labels = 0;
-  for (int u = 0; u < U; ++u) {
-    const int32_t n = h[U + 1 + u + 1] - h[U + 1 + u];
-    if (h[u + 1] < h[u] || n < 0) return fail(-1, "CTC align: utterance %d has a negative length", u);
-    max_labels = n > max_labels ? n : max_labels;
-  }
-  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC align: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
-  if (h[U + 1] < 0) return fail(-1, "CTC align: lab_off[0] = %d < 0", h[U + 1]);
-  if (const char* why = ctc_align_limits(O, T, U, max_labels)) return fail(-1, "CTC align (O %d, T %d, U %d): %s", O, T, U, why);
-  if (h[2 * U + 1] > h[U + 1] && !labels) return fail(-1, "CTC align: labels is NULL");
-  void* scratch = nullptr;  // the call's own scratch, released in stream order
-  const size_t bytes = ctc_align_wild_scratch_bytes(T, max_labels);
-  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
-  ctc_viterbi_align_wild((hipStream_t)stream, logits, (int)ld, O, T, seg, U, labels, lab_off, wild, max_labels, scratch, ali,
-                         score, free_score);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
 // Keyword spotting (the contract: tfkaldi_hip.h at tfk_ctc_spot): ctc_score_impl's recipe -- the pair tables built and checked
 // on the host, staged behind the forward's own tables -- with the flags behind the labels; 3P + U words go back to the host.
 static int ctc_spot_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,
@@ -3904,46 +3421,16 @@ static int ctc_spot_impl(tfk_engine* e, const float* X, int64_t ldx, int32_t T, 
   CHK(decode_args(e, "tfk_ctc_spot", X, T, flags, raw));
   if (U <= 0 || !utt_len || !hyp_count) return fail(-1, "CTC spot: utt_len / hyp_count is NULL or no utterances");
   if (!free_score) return fail(-1, "CTC spot: free_score is NULL");
-  int64_t P64 = 0;
-  for (int u = 0; u < U; ++u) {
-    if (hyp_count[u] < 0) return fail(-1, "CTC spot: utterance %d has a negative pattern count", u);
-    if (utt_len[u] < 0) return fail(-1, "CTC spot: utterance %d has a negative length", u);
-    P64 += hyp_count[u];
-    if (P64 > kCtcScoreMaxPairs) return fail(-1, "CTC spot: more than %d (utterance, pattern) pairs in one call", kCtcScoreMaxPairs);
-  }
-  const int P = (int)P64;
+  int P = 0;
+  CHK(pairs_count("CTC spot", "pattern", hyp_count, utt_len, U, kCtcScoreMaxPairs, &P));
   if (P > 0 && (!label_len || !score || !start || !end)) return fail(-1, "CTC spot: label_len / score / start / end is NULL");
   std::vector<int32_t> tab(2 * (size_t)P + 1);  // [pair_utt | lab_off]
   int32_t* pair_utt = tab.data();
   int32_t* lab_off = pair_utt + P;
   int max_pat = 0;
-  {
-    int p = 0;
-    int64_t first = 0;
-    lab_off[0] = 0;
-    for (int u = 0; u < U; ++u)
-      for (int k = 0; k < hyp_count[u]; ++k, ++p) {
-        const int32_t n = label_len[p];
-        if (n < 0) return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d) has a negative length", u, k, p);
-        if (n > kCtcMaxLabels)
-          return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d) has %d labels (limit %d)", u, k, p, n, kCtcMaxLabels);
-        if (n > 0 && !labels) return fail(-1, "CTC spot: labels is NULL");
-        for (int32_t i = 0; i < n; ++i)
-          if (labels[first + i] < 0 || labels[first + i] >= e->O - 1)
-            return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d): label %d outside [0, %d)", u, k, p,
-                        labels[first + i], e->O - 1);
-        if (wild)
-          for (int32_t g = 0; g <= n; ++g)
-            if (wild[first + p + g] > 1)
-              return fail(-1, "CTC spot: utterance %d, pattern %d (pair %d), gap %d: wild is %d, not 0 or 1", u, k, p, g,
-                          (int)wild[first + p + g]);
-        first += n;
-        if (first > 0x7fffffff - kCtcScoreMaxPairs) return fail(-1, "CTC spot: too many labels in one call");
-        pair_utt[p] = u;
-        lab_off[p + 1] = (int32_t)first;
-        max_pat = n > max_pat ? n : max_pat;
-      }
-  }
+  // (at most 2^20 pairs of at most 511 labels: the offsets, and the flags behind them, fit an int32)
+  CHK(pairs_build("CTC spot", "pattern", true, hyp_count, U, label_len, labels, wild, e->O, kCtcMaxLabels, pair_utt, lab_off,
+                  &max_pat));
   if (const char* why = ctc_score_limits(e->O, T, U, P, max_pat)) return fail(-1, "CTC spot (T %d, U %d, P %d): %s", T, U, P, why);
   const size_t total = (size_t)lab_off[P], tab_words = 2 * (size_t)P + 1, nflags = wild ? total + (size_t)P : 0;
   const size_t back = 3 * (size_t)P + (size_t)U;  // [score | start | end | free]
@@ -3986,148 +3473,6 @@ int tfk_ctc_spot_raw(tfk_engine* e, const float* raw, int64_t ldraw, int32_t T, 
   return ctc_spot_impl(e, raw, ldraw, T, utt_len, U, hyp_count, labels, label_len, wild, score, start, end, free_score, flags,
                        &r);
 }
-int tfk_ctc_spot_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
-                        const uint8_t* wild, float* score, int32_t* start, int32_t* end, float* free_score) {
-  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
-  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC spot: more than %d (utterance, pattern) pairs in one call", kCtcScoreMaxPairs);
-  if (U == 0) return P == 0 ? 0 : fail(-1, "CTC spot: %d pairs and no utterance", P);
-  if (!seg || !free_score || (T > 0 && !logits)) return fail(-1, "logits / seg / free_score is NULL");
-  if (P > 0 && (!pair_utt || !lab_off || !score || !start || !end))
-    return fail(-1, "pair_utt / lab_off / score / start / end is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  // the small tables come back first (one synchronisation), as tfk_ctc_score_logits
-  std::vector<int32_t> h((size_t)U + 1 + 2 * (size_t)P + 1, 0);
-  int32_t* h_utt = h.data() + U + 1;
-  int32_t* h_off = h_utt + P;
-  HIPCHK(hipMemcpyAsync(h.data(), seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  if (P > 0) {
-    HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  }
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  for (int u = 0; u < U; ++u)
-    if (h[u + 1] < h[u]) return fail(-1, "CTC spot: utterance %d has a negative length", u);
-  if (h[0] < 0 || h[U] > T) return fail(-1, "CTC spot: seg = [%d, %d] outside [0, T = %d]", h[0], h[U], T);
-  int max_labels = 0;
-  for (int p = 0; p < P; ++p) {
-    const int32_t n = h_off[p + 1] - h_off[p];
-    if (n < 0) return fail(-1, "CTC spot: pair %d has a negative length", p);
-    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC spot: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
-    max_labels = n > max_labels ? n : max_labels;
-  }
-  if (h_off[0] < 0) return fail(-1, "CTC spot: lab_off[0] = %d < 0", h_off[0]);
-  if (const char* why = ctc_score_limits(O, T, U, P, max_labels))
-    return fail(-1, "CTC spot (O %d, T %d, U %d, P %d): %s", O, T, U, P, why);
-  if (h_off[P] > h_off[0] && !labels) return fail(-1, "CTC spot: labels is NULL");
-  void* scratch = nullptr;  // the call's own scratch, released in stream order
-  const size_t bytes = ctc_spot_scratch_bytes(T);
-  HIPCHK(hipMallocAsync(&scratch, bytes > 0 ? bytes : 16, (hipStream_t)stream));
-  ctc_spot((hipStream_t)stream, logits, (int)ld, O, T, seg, U, pair_utt, P, labels, lab_off, wild, max_labels, scratch, score,
-           start, end, free_score);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t freed = hipFreeAsync(scratch, (hipStream_t)stream);  // also when the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
-int tfk_ctc_mwer_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
-                        const int32_t* pair_utt, int32_t P, const int32_t* labels, const int32_t* lab_off,
-                        const int32_t* ref_labels, const int32_t* ref_off, float ctc_weight, float* dlogits, int64_t ldd,
-                        float* risk, float* score, int32_t* edits) {
-  hipStream_t st = (hipStream_t)stream;
-  if (U < 0 || P < 0) return fail(-1, "U = %d / P = %d < 0", U, P);
-  if (P > kCtcScoreMaxPairs) return fail(-1, "CTC MWER: more than %d (utterance, hypothesis) pairs in one call", kCtcScoreMaxPairs);
-  if (!(ctc_weight >= 0.f) || !std::isfinite(ctc_weight))
-    return fail(-1, "CTC MWER: ctc_weight %g is negative or not finite", (double)ctc_weight);
-  if (U == 0) return P == 0 ? 0 : fail(-1, "CTC MWER: %d pairs and no utterance", P);
-  if (!seg || !ref_off || !risk || (T > 0 && !logits)) return fail(-1, "logits / seg / ref_off / risk is NULL");
-  if (P > 0 && (!pair_utt || !lab_off || !score || !edits)) return fail(-1, "pair_utt / lab_off / score / edits is NULL");
-  if (ld < O || ld > 0x7fffffff) return fail(-1, "ld = %lld outside [O = %d, 2^31)", (long long)ld, O);
-  if (dlogits && (ldd < O || ldd > 0x7fffffff)) return fail(-1, "ldd = %lld outside [O = %d, 2^31)", (long long)ldd, O);
-  // The shapes live in the small tables, which only the device knows: they come back first (one synchronisation)
-  std::vector<int32_t> h(2 * ((size_t)U + 1) + 2 * (size_t)P + 1);
-  int32_t* h_seg = h.data();
-  int32_t* h_roff = h_seg + U + 1;
-  int32_t* h_utt = h_roff + U + 1;
-  int32_t* h_off = h_utt + P;
-  HIPCHK(hipMemcpyAsync(h_seg, seg, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(h_roff, ref_off, ((size_t)U + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (P > 0) {
-    HIPCHK(hipMemcpyAsync(h_utt, pair_utt, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_off, lab_off, ((size_t)P + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  } else {
-    h_off[0] = 0;
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<int32_t> utt_len(U), ref_len(U), hyp_count(U, 0), hyp_len(P > 0 ? P : 1);
-  int max_hyp = 0, max_ref = 0;
-  int64_t PR = 0;
-  for (int u = 0; u < U; ++u) {
-    utt_len[u] = h_seg[u + 1] - h_seg[u];
-    ref_len[u] = h_roff[u + 1] - h_roff[u];
-    if (utt_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative length", u);
-    if (ref_len[u] < 0) return fail(-1, "CTC MWER: utterance %d has a negative reference length", u);
-    max_ref = ref_len[u] > max_ref ? ref_len[u] : max_ref;
-  }
-  if (h_seg[0] < 0 || h_seg[U] > T) return fail(-1, "CTC MWER: seg = [%d, %d] outside [0, T = %d]", h_seg[0], h_seg[U], T);
-  if (h_roff[0] < 0 || h_off[0] < 0) return fail(-1, "CTC MWER: lab_off[0] / ref_off[0] < 0");
-  for (int p = 0; p < P; ++p) {
-    hyp_len[p] = h_off[p + 1] - h_off[p];
-    if (hyp_len[p] < 0) return fail(-1, "CTC MWER: pair %d has a negative length", p);
-    if (h_utt[p] < 0 || h_utt[p] >= U) return fail(-1, "CTC MWER: pair %d names utterance %d outside [0, %d)", p, h_utt[p], U);
-    if (p > 0 && h_utt[p] < h_utt[p - 1]) return fail(-1, "CTC MWER: pair %d: the pairs are not ordered by utterance", p);
-    ++hyp_count[h_utt[p]];
-    max_hyp = hyp_len[p] > max_hyp ? hyp_len[p] : max_hyp;
-  }
-  for (int u = 0; u < U; ++u) PR += (int64_t)(hyp_count[u] + (ctc_weight > 0.f ? 1 : 0)) * utt_len[u];
-  const int max_labels = std::max(max_hyp, max_ref);  // (the references' edit distance rides the same limit)
-  if (const char* why = ctc_mwer_limits(O, ld, T, U, P, max_labels, PR))
-    return fail(-1, "CTC MWER (O %d, T %d, U %d, P %d, longest label sequence %d): %s", O, T, U, P, max_labels, why);
-  const int hyp_total = h_off[P] - h_off[0], ref_total = h_roff[U] - h_roff[0];
-  if ((hyp_total > 0 && !labels) || (ref_total > 0 && !ref_labels)) return fail(-1, "CTC MWER: labels / ref_labels is NULL");
-  const int NP = ctc_weight > 0.f ? P + U : P;
-  const int sext = ctc_state_stride(ctc_weight > 0.f ? max_labels : max_hyp);
-  const size_t tab_words = ctc_mwer_table_words(U, P, NP), total = (size_t)hyp_total + (size_t)ref_total;
-  const size_t ints = ((tab_words + total + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-  std::vector<int32_t> tab(tab_words);
-  ctc_mwer_table(utt_len.data(), U, hyp_count.data(), hyp_len.data(), ref_len.data(), NP > P, tab.data());
-  unsigned char* scratch = nullptr;  // the call's own scratch, released in stream order: [tables | labels | lattices]
-  HIPCHK(hipMallocAsync((void**)&scratch, ints + ctc_mwer_scratch_bytes(T, NP, P, PR, sext), st));
-  int32_t* d_tab = reinterpret_cast<int32_t*>(scratch);
-  hipError_t copied = hipMemcpyAsync(d_tab, tab.data(), tab_words * sizeof(int32_t), hipMemcpyHostToDevice, st);
-  if (copied == hipSuccess && hyp_total > 0)
-    copied = hipMemcpyAsync(d_tab + tab_words, labels + h_off[0], (size_t)hyp_total * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-  if (copied == hipSuccess && ref_total > 0)
-    copied = hipMemcpyAsync(d_tab + tab_words + hyp_total, ref_labels + h_roff[0], (size_t)ref_total * sizeof(int32_t),
-                            hipMemcpyDeviceToDevice, st);
-  if (copied == hipSuccess) copied = hipStreamSynchronize(st);  // (the table leaves pageable host memory)
-  hipError_t launched = copied;
-  if (copied == hipSuccess) {
-    CtcMwer m = {};
-    m.logits = logits; m.ld = (int)ld; m.O = O; m.T = T; m.U = U; m.seg = seg;
-    m.P = P; m.NP = NP; m.PR = PR; m.sext = sext; m.max_hyp = max_hyp; m.ctc_weight = ctc_weight;
-    m.tab = d_tab; m.labels = d_tab + tab_words;
-    ctc_mwer_carve(scratch + ints, &m);
-    m.risk = risk; m.score = score; m.edits = edits;
-    ctc_mwer(st, m, dlogits, (int)ldd, h_seg[0], h_seg[U] - h_seg[0], Twin());
-    launched = hipGetLastError();
-  }
-  const hipError_t freed = hipFreeAsync(scratch, st);  // also when a copy or the launch failed
-  HIPCHK(launched);
-  HIPCHK(freed);
-  return 0;
-}
-int tfk_label_edit_distance(void* stream, const int32_t* hyp, const int32_t* hyp_off, const int32_t* ref,
-                            const int32_t* ref_off, int32_t U, int32_t* dist) {
-  if (U < 0) return fail(-1, "U = %d < 0", U);
-  if (U == 0) return 0;
-  if (!hyp_off || !ref_off || !dist) return fail(-1, "hyp_off / ref_off / dist is NULL");
-  label_edit_distance((hipStream_t)stream, hyp, hyp_off, nullptr, ref, ref_off, U, kCtcMaxLabels, dist);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 int tfk_reduce_region(tfk_engine* e, void** device_ptr, size_t* num_floats) {
   if (!e || !device_ptr || !num_floats) return fail(-1, "NULL argument");
   *device_ptr = e->p_grad();

@@ -19,6 +19,7 @@
 // TFK_COMM_LOOPBACK (tests): N engines of ONE process on one GPU form a group; collectives are rendezvous + plain kernels.
 // That is how the C++ protocol is exercised at world 2 / 4 / 8 on a single-GPU box (RCCL refuses two ranks per device).
 #include "../../include/tfkaldi_hip.h"
+#include "tfk_error.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -35,30 +36,9 @@
 #include <string>
 #include <vector>
 
-namespace tfk {
-int set_error(int code, const char* msg);  // engine.hip: the library's thread-local error message
-}
-
 namespace {
 
-int failx(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return tfk::set_error(code ? code : -1, buf);
-}
-#define XHIP(expr)                                                                                          \
-  do {                                                                                                      \
-    hipError_t e_ = (expr);                                                                                 \
-    if (e_ != hipSuccess) return failx((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define XCHK(expr)           \
-  do {                       \
-    int rc_ = (expr);        \
-    if (rc_ != 0) return rc_; \
-  } while (0)
+using tfk::fail;
 
 // ---- RCCL, bound at run time ----
 struct Rccl {
@@ -117,7 +97,7 @@ Rccl* rccl() {
 #define XNCCL(expr)                                                                                              \
   do {                                                                                                           \
     ncclResult_t r_ = (expr);                                                                                    \
-    if (r_ != ncclSuccess) return failx((int)r_, "%s failed: %s (%s:%d)", #expr, rccl()->GetErrorString(r_), __FILE__, __LINE__); \
+    if (r_ != ncclSuccess) return fail((int)r_, "%s failed: %s (%s:%d)", #expr, rccl()->GetErrorString(r_), __FILE__, __LINE__); \
   } while (0)
 
 // ---- the collectives the protocol needs; every one IN PLACE on `world` equal shards ----
@@ -166,7 +146,7 @@ struct RcclBackend : Backend {
   int exchange_shards(const void* send, void* recv, size_t bytes, hipStream_t st) override {
     Rccl* r = rccl();
     if (!r->Send || !r->Recv)
-      return failx(-1, "this RCCL has no ncclSend / ncclRecv: TFK_DP_ALGO=direct and TFK_DP_WIRE=bf16 are not available");
+      return fail(-1, "this RCCL has no ncclSend / ncclRecv: TFK_DP_ALGO=direct and TFK_DP_WIRE=bf16 are not available");
     const char* s = static_cast<const char*>(send);
     char* d = static_cast<char*>(recv);
     // one group: every rank sends world - 1 blocks and receives world - 1 blocks over its world - 1 links at once -- on
@@ -178,7 +158,7 @@ struct RcclBackend : Backend {
       ncclResult_t b = a == ncclSuccess ? r->Recv(d + (size_t)q * bytes, bytes, ncclInt8, q, comm, st) : a;
       if (b != ncclSuccess) {
         (void)r->GroupEnd();
-        return failx((int)b, "ncclSend / ncclRecv failed: %s", r->GetErrorString(b));
+        return fail((int)b, "ncclSend / ncclRecv failed: %s", r->GetErrorString(b));
       }
     }
     XNCCL(r->GroupEnd());
@@ -186,7 +166,7 @@ struct RcclBackend : Backend {
   }
   int all_gather_direct(void* buf, size_t bytes_per_rank, hipStream_t st) override {
     Rccl* r = rccl();
-    if (!r->Send || !r->Recv) return failx(-1, "this RCCL has no ncclSend / ncclRecv: TFK_DP_ALGO=direct is not available");
+    if (!r->Send || !r->Recv) return fail(-1, "this RCCL has no ncclSend / ncclRecv: TFK_DP_ALGO=direct is not available");
     char* b = static_cast<char*>(buf);
     XNCCL(r->GroupStart());
     for (int q = 0; q < world; ++q) {
@@ -195,20 +175,20 @@ struct RcclBackend : Backend {
       ncclResult_t c = a == ncclSuccess ? r->Recv(b + (size_t)q * bytes_per_rank, bytes_per_rank, ncclInt8, q, comm, st) : a;
       if (c != ncclSuccess) {
         (void)r->GroupEnd();
-        return failx((int)c, "ncclSend / ncclRecv failed: %s", r->GetErrorString(c));
+        return fail((int)c, "ncclSend / ncclRecv failed: %s", r->GetErrorString(c));
       }
     }
     XNCCL(r->GroupEnd());
     return 0;
   }
   int min_max(unsigned long long* v, hipStream_t st) override {
-    if (!d_pair) XHIP(hipMalloc((void**)&d_pair, 2 * sizeof(unsigned long long)));
+    if (!d_pair) HIPCHK(hipMalloc((void**)&d_pair, 2 * sizeof(unsigned long long)));
     const unsigned long long in[2] = {v[0], v[0]};
-    XHIP(hipMemcpyAsync(d_pair, in, sizeof(in), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pair, in, sizeof(in), hipMemcpyHostToDevice, st));
     XNCCL(rccl()->AllReduce(d_pair, d_pair, 1, ncclUint64, ncclMin, comm, st));
     XNCCL(rccl()->AllReduce(d_pair + 1, d_pair + 1, 1, ncclUint64, ncclMax, comm, st));
-    XHIP(hipMemcpyAsync(v, d_pair, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    XHIP(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(v, d_pair, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
   }
   // (an RCCL call costs its stream 10-13 us of event work whatever it moves -- profiles/r04_dp_trace.txt; a group pays it once)
@@ -312,7 +292,7 @@ struct LoopBackend : Backend {
     const tfk_loopback::Slot& s0 = g->slot[0];
     for (int r = 1; r < W; ++r)
       if (g->slot[r].kind != s0.kind || g->slot[r].count != s0.count)
-        return failx(-1, "loopback group: rank %d posted collective kind %d x %zu, rank 0 kind %d x %zu -- the ranks "
+        return fail(-1, "loopback group: rank %d posted collective kind %d x %zu, rank 0 kind %d x %zu -- the ranks "
                          "launched different collectives", r, g->slot[r].kind, g->slot[r].count, s0.kind, s0.count);
     if (s0.kind == 3) {
       g->vmin = g->vmax = g->slot[0].value;
@@ -325,9 +305,9 @@ struct LoopBackend : Backend {
     // one communicator's operations run one after the other whatever streams they were posted on (RCCL orders them itself; the
     // comm posts the tail of a step on the engine stream, the rest on its comm stream): behind the previous operation's end ...
     for (int r = 0; r < W; ++r)
-      for (int q = 0; q < W; ++q) XHIP(hipStreamWaitEvent(g->slot[r].st, g->slot[q].finish, 0));
+      for (int q = 0; q < W; ++q) HIPCHK(hipStreamWaitEvent(g->slot[r].st, g->slot[q].finish, 0));
     for (int r = 0; r < W; ++r)  // ... and nobody starts before every rank's operand is ready
-      for (int q = 0; q < W; ++q) XHIP(hipStreamWaitEvent(g->slot[r].st, g->slot[q].arrive, 0));
+      for (int q = 0; q < W; ++q) HIPCHK(hipStreamWaitEvent(g->slot[r].st, g->slot[q].arrive, 0));
     const size_t n = s0.count;
     if (s0.kind == 0) {
       for (int r = 0; r < W; ++r) {
@@ -341,48 +321,48 @@ struct LoopBackend : Backend {
       for (int r = 0; r < W; ++r)
         for (int q = 0; q < W; ++q)
           if (q != r)
-            XHIP(hipMemcpyAsync(static_cast<char*>(g->slot[r].buf) + (size_t)q * n,
+            HIPCHK(hipMemcpyAsync(static_cast<char*>(g->slot[r].buf) + (size_t)q * n,
                                 static_cast<const char*>(g->slot[q].send) + (size_t)r * n, n, hipMemcpyDeviceToDevice, g->slot[r].st));
     } else if (s0.kind == 1) {
       for (int r = 0; r < W; ++r)
         for (int q = 0; q < W; ++q)
           if (q != r)
-            XHIP(hipMemcpyAsync(static_cast<char*>(g->slot[r].buf) + (size_t)q * n,
+            HIPCHK(hipMemcpyAsync(static_cast<char*>(g->slot[r].buf) + (size_t)q * n,
                                 static_cast<const char*>(g->slot[q].buf) + (size_t)q * n, n, hipMemcpyDeviceToDevice,
                                 g->slot[r].st));
     } else {
       if (n > g->scratch_floats) {
-        if (g->scratch) XHIP(hipFree(g->scratch));  // (synchronises the device: every earlier operation is over)
+        if (g->scratch) HIPCHK(hipFree(g->scratch));  // (synchronises the device: every earlier operation is over)
         g->scratch = nullptr;
-        XHIP(hipMalloc((void**)&g->scratch, n * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&g->scratch, n * sizeof(float)));
         g->scratch_floats = n;
       }
       SrcList src;
       for (int q = 0; q < W; ++q) src.p[q] = static_cast<const float*>(g->slot[q].buf);
       const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
       hipLaunchKernelGGL(loop_sum_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, g->slot[0].st, g->scratch, src, W, n);
-      XHIP(hipEventRecord(g->sum_done, g->slot[0].st));
+      HIPCHK(hipEventRecord(g->sum_done, g->slot[0].st));
       for (int r = 0; r < W; ++r) {
-        XHIP(hipStreamWaitEvent(g->slot[r].st, g->sum_done, 0));
-        XHIP(hipMemcpyAsync(g->slot[r].buf, g->scratch, n * sizeof(float), hipMemcpyDeviceToDevice, g->slot[r].st));
+        HIPCHK(hipStreamWaitEvent(g->slot[r].st, g->sum_done, 0));
+        HIPCHK(hipMemcpyAsync(g->slot[r].buf, g->scratch, n * sizeof(float), hipMemcpyDeviceToDevice, g->slot[r].st));
       }
     }
-    XHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // ... and nobody's operation is complete before every rank has finished reading its peers' buffers
-    for (int r = 0; r < W; ++r) XHIP(hipEventRecord(g->slot[r].finish, g->slot[r].st));
+    for (int r = 0; r < W; ++r) HIPCHK(hipEventRecord(g->slot[r].finish, g->slot[r].st));
     for (int r = 0; r < W; ++r)
       for (int q = 0; q < W; ++q)
-        if (q != r) XHIP(hipStreamWaitEvent(g->slot[r].st, g->slot[q].finish, 0));
+        if (q != r) HIPCHK(hipStreamWaitEvent(g->slot[r].st, g->slot[q].finish, 0));
     return 0;
   }
   int post(int kind, void* buf, size_t count, hipStream_t st, unsigned long long value = 0, const void* send = nullptr) {
     if (!arrive) {
-      XHIP(hipEventCreateWithFlags(&arrive, hipEventDisableTiming));
-      XHIP(hipEventCreateWithFlags(&finish, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&arrive, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&finish, hipEventDisableTiming));
     }
-    if (kind != 3) XHIP(hipEventRecord(arrive, st));
+    if (kind != 3) HIPCHK(hipEventRecord(arrive, st));
     std::unique_lock<std::mutex> lock(g->m);
-    if (g->error) return failx(g->error, "loopback group failed earlier: %s", g->error_text.c_str());
+    if (g->error) return fail(g->error, "loopback group failed earlier: %s", g->error_text.c_str());
     tfk_loopback::Slot& s = g->slot[rank];
     s.kind = kind; s.buf = buf; s.count = count; s.st = st; s.arrive = arrive; s.finish = finish; s.value = value;
     s.send = send;
@@ -399,7 +379,7 @@ struct LoopBackend : Backend {
     } else {
       g->cv.wait(lock, [&] { return g->generation != gen; });
     }
-    if (g->error) return failx(g->error, "%s", g->error_text.c_str());
+    if (g->error) return fail(g->error, "%s", g->error_text.c_str());
     return 0;
   }
   int reduce_scatter(float* buf, size_t per_rank, hipStream_t st) override { return post(0, buf, per_rank, st); }
@@ -410,7 +390,7 @@ struct LoopBackend : Backend {
   }
   int all_gather_direct(void* buf, size_t bytes_per_rank, hipStream_t st) override { return post(1, buf, bytes_per_rank, st); }
   int min_max(unsigned long long* v, hipStream_t st) override {
-    XCHK(post(3, nullptr, 0, st, v[0]));
+    CHK(post(3, nullptr, 0, st, v[0]));
     // (the values stay valid until the next operation completes, which needs this rank again)
     v[0] = g->vmin;
     v[1] = g->vmax;
@@ -507,7 +487,7 @@ namespace {
 constexpr size_t kDefaultBucketBytes = (size_t)32 << 20;  // (tfk_comm_create: why)
 
 int new_event(hipEvent_t* ev) {
-  XHIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
   return 0;
 }
 
@@ -564,7 +544,7 @@ bool shardable(const tfk_comm* c, size_t lo, size_t hi) {
 // streams is legal for RCCL: it orders its operations itself.)
 int ensure_stage(tfk_comm* c) {
   if (c->stage) return 0;
-  XHIP(hipMalloc(&c->stage, std::max<size_t>(c->num_params, 1) * sizeof(float)));
+  HIPCHK(hipMalloc(&c->stage, std::max<size_t>(c->num_params, 1) * sizeof(float)));
   return 0;
 }
 
@@ -588,12 +568,12 @@ struct Timed {
   Timed(tfk_comm* c_, int phase_, hipStream_t st_) : c(c_), st(st_), phase(phase_) {
     if (!c->timing || phase < 0) return;
     a = take(c);
-    if (!a || hipEventRecord(a, st) != hipSuccess) rc = failx(-1, "timing event could not be recorded");
+    if (!a || hipEventRecord(a, st) != hipSuccess) rc = fail(-1, "timing event could not be recorded");
   }
   int end() {
     if (!c->timing || rc || !a || phase < 0) return rc;
     hipEvent_t b = take(c);
-    if (!b || hipEventRecord(b, st) != hipSuccess) return failx(-1, "timing event could not be recorded");
+    if (!b || hipEventRecord(b, st) != hipSuccess) return fail(-1, "timing event could not be recorded");
     c->timed.push_back({phase, a, b});
     a = nullptr;
     return 0;
@@ -605,7 +585,7 @@ struct Group {  // a backend group, closed on every way out: a failed collective
   bool open;
   ~Group() { if (open) (void)be->group_end(); }
   int begin() {
-    XCHK(be->group_begin());
+    CHK(be->group_begin());
     open = true;
     return 0;
   }
@@ -618,8 +598,8 @@ struct Group {  // a backend group, closed on every way out: a failed collective
 // a parameter gather of `world` equal shards in place, by the algorithm in force
 int gather_span(tfk_comm* c, void* buf, size_t bytes_per_rank, hipStream_t st, bool timed = true) {
   Timed t(c, timed ? PH_AG : -1, st);
-  if (c->algo_ag == TFK_ALGO_DIRECT) XCHK(c->be->all_gather_direct(buf, bytes_per_rank, st));
-  else XCHK(c->be->all_gather(buf, bytes_per_rank, st));
+  if (c->algo_ag == TFK_ALGO_DIRECT) CHK(c->be->all_gather_direct(buf, bytes_per_rank, st));
+  else CHK(c->be->all_gather(buf, bytes_per_rank, st));
   return t.end();
 }
 
@@ -638,8 +618,8 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
   for (int k = 0; k < pieces; ++k) {
     if (c->num_spans == c->spans.size()) {
       Span s;
-      XCHK(new_event(&s.ready));
-      XCHK(new_event(&s.done));
+      CHK(new_event(&s.ready));
+      CHK(new_event(&s.done));
       c->spans.push_back(s);
     }
     Span& s = c->spans[c->num_spans++];
@@ -648,8 +628,8 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
   }
   hipStream_t st = inline_on_engine ? c->engine_stream : c->comm_stream;
   if (!inline_on_engine) {
-    XHIP(hipEventRecord(c->spans[first].ready, c->engine_stream));
-    XHIP(hipStreamWaitEvent(c->comm_stream, c->spans[first].ready, 0));
+    HIPCHK(hipEventRecord(c->spans[first].ready, c->engine_stream));
+    HIPCHK(hipStreamWaitEvent(c->comm_stream, c->spans[first].ready, 0));
   }
   // reduce-scattered spans that travel as point-to-point transfers (direct algorithm, bf16 wire) first, each on its own: the
   // exchange must have been LAUNCHED, not deferred to the end of a group, when the owner's sum is enqueued behind it.  The
@@ -665,7 +645,7 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
       rest += s.rs ? pcs.size() : 1;
       continue;
     }
-    XCHK(ensure_stage(c));
+    CHK(ensure_stage(c));
     Timed t(c, PH_RS, st);
     Group g = {c->be, false};
     if (c->wire_bf16) {
@@ -674,16 +654,16 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
       const unsigned blocks = (unsigned)std::min<size_t>((s.n + 255) / 256, 1 << 14);
       hipLaunchKernelGGL(wire_pack_kernel, dim3(blocks), dim3(256), 0, st, c->grad + s.off, static_cast<uint16_t*>(c->stage) + s.off, s.n);
     }
-    if (pcs.size() > 1) XCHK(g.begin());
+    if (pcs.size() > 1) CHK(g.begin());
     for (const Piece& p : pcs) {
       const size_t per = p.n / W;
       if (c->wire_bf16)
-        XCHK(c->be->exchange_shards(static_cast<uint16_t*>(c->stage) + p.off, static_cast<uint16_t*>(c->stage) + c->num_params + p.off,
+        CHK(c->be->exchange_shards(static_cast<uint16_t*>(c->stage) + p.off, static_cast<uint16_t*>(c->stage) + c->num_params + p.off,
                                     per * sizeof(uint16_t), st));
       else
-        XCHK(c->be->exchange_shards(c->grad + p.off, static_cast<float*>(c->stage) + p.off, per * sizeof(float), st));
+        CHK(c->be->exchange_shards(c->grad + p.off, static_cast<float*>(c->stage) + p.off, per * sizeof(float), st));
     }
-    if (pcs.size() > 1) XCHK(g.end());
+    if (pcs.size() > 1) CHK(g.end());
     for (const Piece& p : pcs) {
       const size_t per = p.n / W;
       if (c->wire_bf16) {
@@ -696,8 +676,8 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
                            static_cast<float*>(c->stage) + p.off, R, W, per);
       }
     }
-    XHIP(hipGetLastError());
-    XCHK(t.end());
+    HIPCHK(hipGetLastError());
+    CHK(t.end());
     c->cur_rs += 1;
   }
   const bool grouped = rest > 1;
@@ -707,21 +687,21 @@ int launch_range(tfk_comm* c, size_t lo, size_t hi, bool inline_on_engine = fals
   for (size_t k = first; k < c->num_spans; ++k)
     if (c->spans[k].rs && !p2p) lone_phase = PH_RS;
   Timed tg(c, lone_phase, st);
-  if (grouped) XCHK(group.begin());
+  if (grouped) CHK(group.begin());
   for (size_t k = first; k < c->num_spans; ++k) {
     Span& s = c->spans[k];
     if (s.rs && p2p) continue;
     if (s.rs) {
-      for (const Piece& p : pieces_of(c, s.off, s.n)) XCHK(c->be->reduce_scatter(c->grad + p.off, p.n / W, st));
+      for (const Piece& p : pieces_of(c, s.off, s.n)) CHK(c->be->reduce_scatter(c->grad + p.off, p.n / W, st));
       c->cur_rs += 1;
     } else {
-      XCHK(c->be->all_reduce(c->grad + s.off, s.n, st));
+      CHK(c->be->all_reduce(c->grad + s.off, s.n, st));
       c->cur_ar += 1;
     }
   }
-  if (grouped) XCHK(group.end());
-  if (rest) XCHK(tg.end());
-  if (!inline_on_engine) XHIP(hipEventRecord(c->spans[c->num_spans - 1].done, c->comm_stream));
+  if (grouped) CHK(group.end());
+  if (rest) CHK(tg.end());
+  if (!inline_on_engine) HIPCHK(hipEventRecord(c->spans[c->num_spans - 1].done, c->comm_stream));
   return 0;
 }
 
@@ -745,24 +725,24 @@ int flush_range(tfk_comm* c, bool inline_on_engine = false) {
     //  under tfk_comm_timing every operation keeps its own launch so that its events bracket it)
     const bool one_launch = !p2p && !c->timing;
     Group g = {c->be, false};
-    if (one_launch) XCHK(g.begin());
+    if (one_launch) CHK(g.begin());
     if (c->have_head) {
       c->have_head = false;
-      XCHK(launch_range(c, c->head_lo, c->head_hi, true));
+      CHK(launch_range(c, c->head_lo, c->head_hi, true));
     }
     if (c->have_hold) {
       c->have_hold = false;
-      XCHK(launch_range(c, c->hold_lo, c->hold_hi, true));
+      CHK(launch_range(c, c->hold_lo, c->hold_hi, true));
     }
     if (c->have_range) {
       c->have_range = false;
-      XCHK(launch_range(c, c->lo, c->hi, true));
+      CHK(launch_range(c, c->lo, c->hi, true));
     }
     return one_launch ? g.end() : 0;
   }
   if (c->have_hold) {  // (a flush in the middle of a step: the held weight range goes first, in announcement order)
     c->have_hold = false;
-    XCHK(launch_range(c, c->hold_lo, c->hold_hi, inline_on_engine));
+    CHK(launch_range(c, c->hold_lo, c->hold_hi, inline_on_engine));
   }
   if (!c->have_range) return 0;
   c->have_range = false;
@@ -770,7 +750,7 @@ int flush_range(tfk_comm* c, bool inline_on_engine = false) {
 }
 
 int announce(tfk_comm* c, int b) {
-  if (b < 0 || b >= (int)c->buckets.size()) return failx(-1, "bucket %d out of range", b);
+  if (b < 0 || b >= (int)c->buckets.size()) return fail(-1, "bucket %d out of range", b);
   const size_t off = c->buckets[b].first, n = c->buckets[b].second;
   if (b == c->L + 2 && !c->have_range && hold_last()) {
     // [scalars + BN increments]: always the FIRST announcement of a step.  Its all-reduce used to go to the comm stream at once
@@ -795,12 +775,12 @@ int announce(tfk_comm* c, int b) {
     c->lo = off;
     c->hi = off + n;
   } else {
-    XCHK(flush_range(c));
+    CHK(flush_range(c));
     c->have_range = true;
     c->lo = off;
     c->hi = off + n;
   }
-  if (c->hi - c->lo >= c->min_floats) XCHK(flush_range(c));
+  if (c->hi - c->lo >= c->min_floats) CHK(flush_range(c));
   return 0;
 }
 
@@ -814,7 +794,7 @@ int raise_remembered(tfk_comm* c) {
   if (!c->error) return 0;
   const int rc = c->error;
   c->error = 0;
-  return failx(rc, "%s", c->error_text.c_str());
+  return fail(rc, "%s", c->error_text.c_str());
 }
 
 double g_bucket_us = 0;  // (TFK_DP_HOST_PHASES) host time inside the bucket callback, i.e. the collectives launched under backward
@@ -831,7 +811,7 @@ void on_bucket(void* user, int b) {
 }
 
 int drain(tfk_comm* c) {
-  for (const Gather& g : c->pending) XHIP(hipStreamWaitEvent(c->engine_stream, g.done, 0));
+  for (const Gather& g : c->pending) HIPCHK(hipStreamWaitEvent(c->engine_stream, g.done, 0));
   c->pending.clear();
   return 0;
 }
@@ -847,8 +827,8 @@ int wait_layer(tfk_comm* c, int layer) {
   if (last < 0) return 0;
   // (the gathers run in launch order on one stream: the last one that matters implies the earlier ones)
   Timed exposed(c, PH_GATHER_EXPOSED, c->engine_stream);  // what the forward pass really waits: the gap this wait opens
-  XHIP(hipStreamWaitEvent(c->engine_stream, c->pending[last].done, 0));
-  XCHK(exposed.end());
+  HIPCHK(hipStreamWaitEvent(c->engine_stream, c->pending[last].done, 0));
+  CHK(exposed.end());
   c->pending.erase(c->pending.begin(), c->pending.begin() + last + 1);
   return 0;
 }
@@ -860,7 +840,7 @@ int wait_layer(tfk_comm* c, int layer) {
 int twins_behind_gather(tfk_comm* c, const std::pair<size_t, size_t>& span, hipStream_t st, bool* all_current) {
   int current = 0;
   Timed t(c, PH_TWINS, st);
-  XCHK(tfk_twins_from_params(c->e, span.first, span.second, st, &current));
+  CHK(tfk_twins_from_params(c->e, span.first, span.second, st, &current));
   if (!current) *all_current = false;
   return t.end();
 }
@@ -877,24 +857,24 @@ int gather_pieces(tfk_comm* c, const std::pair<size_t, size_t>& span, hipStream_
   {
     Timed t(c, PH_AG, st);
     Group g = {c->be, false};
-    if (pcs.size() > 1) XCHK(g.begin());
+    if (pcs.size() > 1) CHK(g.begin());
     for (const Piece& p : pcs) {
       if (p.planes) {
         const tfk_comm::TwinOf& tw = c->twin[p.layer];
-        XCHK(gather_span(c, tw.ptr, tw.bytes / W, st, false));
+        CHK(gather_span(c, tw.ptr, tw.bytes / W, st, false));
         *planes_any = true;
         const std::pair<size_t, size_t> piece(p.off, p.n);
         if (std::find(c->shard_spans.begin(), c->shard_spans.end(), piece) == c->shard_spans.end()) c->shard_spans.push_back(piece);
       } else {
-        XCHK(gather_span(c, target + p.off * elem, p.n / W * elem, st, false));
+        CHK(gather_span(c, target + p.off * elem, p.n / W * elem, st, false));
       }
     }
-    if (pcs.size() > 1) XCHK(g.end());
-    XCHK(t.end());
+    if (pcs.size() > 1) CHK(g.end());
+    CHK(t.end());
   }
   if (!via_shadow)
     for (const Piece& p : pcs)
-      if (!p.planes) XCHK(twins_behind_gather(c, {p.off, p.n}, st, derived_current));
+      if (!p.planes) CHK(twins_behind_gather(c, {p.off, p.n}, st, derived_current));
   return 0;
 }
 
@@ -910,7 +890,7 @@ void on_layer(void* user, int layer) {
 int wait_span(tfk_comm* c, Span& s) {
   const size_t index = (size_t)(&s - c->spans.data());
   if (!s.waited && index >= c->waited_upto) {
-    if (s.wait_on) XHIP(hipStreamWaitEvent(c->engine_stream, s.wait_on, 0));  // (nullptr: it ran on the engine stream itself)
+    if (s.wait_on) HIPCHK(hipStreamWaitEvent(c->engine_stream, s.wait_on, 0));  // (nullptr: it ran on the engine stream itself)
     if (s.wait_on) c->waited_upto = index + 1;
   }
   s.waited = true;
@@ -918,17 +898,17 @@ int wait_span(tfk_comm* c, Span& s) {
 }
 
 int verify_replicas(tfk_comm* c, bool via_shadow, bool planes) {
-  XCHK(drain(c));
+  CHK(drain(c));
   // what every rank must agree on after the gathers: the fp32 parameters -- or, where the masters stay with their owners, what
   // the contractions read (bf16 shadow / every three-plane twin) + the all-reduced vectors
   const int which[2] = {via_shadow ? 1 : planes ? 3 : 0, 2};
   for (int k = 0; k < ((via_shadow || planes) ? 2 : 1); ++k) {
     uint64_t sum = 0;
-    XCHK(tfk_param_checksum(c->e, which[k], &sum));
+    CHK(tfk_param_checksum(c->e, which[k], &sum));
     unsigned long long v[2] = {(unsigned long long)sum, 0};
-    XCHK(c->be->min_max(v, c->comm_stream));
+    CHK(c->be->min_max(v, c->comm_stream));
     if (v[0] != v[1])
-      return failx(-1, "data-parallel replicas diverged after the sharded exchange step: rank %d holds checksum %llu of "
+      return fail(-1, "data-parallel replicas diverged after the sharded exchange step: rank %d holds checksum %llu of "
                        "the %s, the ranks' values span %llu .. %llu", c->be->rank, (unsigned long long)sum,
                    which[k] == 0 ? "fp32 parameters" : which[k] == 1 ? "bf16 shadow" : which[k] == 3 ? "three-plane twins"
                                                                                                        : "bias / beta vectors", v[0], v[1]);
@@ -944,7 +924,7 @@ int attach(tfk_engine* e, Backend* be, int mode, size_t bucket_bytes, tfk_comm**
     tfk_comm_destroy(c);
     return rc;
   };
-  if (mode != TFK_EXCHANGE_SHARDED && mode != TFK_EXCHANGE_ALLREDUCE) return bail(failx(-1, "unknown exchange mode %d", mode));
+  if (mode != TFK_EXCHANGE_SHARDED && mode != TFK_EXCHANGE_ALLREDUCE) return bail(fail(-1, "unknown exchange mode %d", mode));
   c->mode = mode;
   // default: 32 MiB per collective (kDefaultBucketBytes).  Every collective launched under backward costs the engine stream a
   // fixed ~6-10 us (an event record between two backward kernels, RCCL's own stream work) whatever it carries -- with ONE RCCL rank
@@ -961,7 +941,7 @@ int attach(tfk_engine* e, Backend* be, int mode, size_t bucket_bytes, tfk_comm**
   if (const char* v = getenv("TFK_DP_VERIFY_STEPS")) c->verify_left = atoi(v);
   if (const char* v = getenv("TFK_DP_WIRE")) {
     if (!strcmp(v, "bf16")) c->wire_bf16 = true;
-    else if (strcmp(v, "fp32") && strcmp(v, "float32")) return bail(failx(-1, "TFK_DP_WIRE=%s (fp32 | bf16)", v));
+    else if (strcmp(v, "fp32") && strcmp(v, "float32")) return bail(fail(-1, "TFK_DP_WIRE=%s (fp32 | bf16)", v));
   }
   bool tune = false;
   {
@@ -978,7 +958,7 @@ int attach(tfk_engine* e, Backend* be, int mode, size_t bucket_bytes, tfk_comm**
       c->algo_rs = c->algo_ag = TFK_ALGO_DIRECT;
       c->chosen_by = 1;
     } else {
-      return bail(failx(-1, "TFK_DP_ALGO=%s (rccl | direct | auto)", v));
+      return bail(fail(-1, "TFK_DP_ALGO=%s (rccl | direct | auto)", v));
     }
   }
   void* st = nullptr;
@@ -992,10 +972,10 @@ int attach(tfk_engine* e, Backend* be, int mode, size_t bucket_bytes, tfk_comm**
   {
     hipPointerAttribute_t attr;
     hipError_t he = hipPointerGetAttributes(&attr, p);
-    if (he != hipSuccess) return bail(failx((int)he, "hipPointerGetAttributes(engine state) failed: %s", hipGetErrorString(he)));
+    if (he != hipSuccess) return bail(fail((int)he, "hipPointerGetAttributes(engine state) failed: %s", hipGetErrorString(he)));
     c->device = attr.device;
     he = hipSetDevice(c->device);
-    if (he != hipSuccess) return bail(failx((int)he, "hipSetDevice(%d) failed: %s", c->device, hipGetErrorString(he)));
+    if (he != hipSuccess) return bail(fail((int)he, "hipSetDevice(%d) failed: %s", c->device, hipGetErrorString(he)));
   }
   if (tfk_param_region(e, &p, &n)) return bail(-1);
   c->param = static_cast<float*>(p);
@@ -1028,10 +1008,10 @@ int attach(tfk_engine* e, Backend* be, int mode, size_t bucket_bytes, tfk_comm**
     // (an arithmetic without owner-written twins -- exact fp32, mixed precision -- has nothing to gather in place of the
     // parameters / the shadow: the variable is a job-wide setting and is simply not applicable there)
     if (!strcmp(v, "planes")) c->gather_planes = twins && mode == TFK_EXCHANGE_SHARDED;
-    else if (strcmp(v, "params")) return bail(failx(-1, "TFK_DP_GATHER=%s (params | planes)", v));
+    else if (strcmp(v, "params")) return bail(fail(-1, "TFK_DP_GATHER=%s (params | planes)", v));
   }
   hipError_t he = hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking);
-  if (he != hipSuccess) return bail(failx((int)he, "hipStreamCreate failed: %s", hipGetErrorString(he)));
+  if (he != hipSuccess) return bail(fail((int)he, "hipStreamCreate failed: %s", hipGetErrorString(he)));
   if (new_event(&c->ev_adam)) return bail(-1);
   if (tfk_set_bucket_callback(e, on_bucket, c) || tfk_set_layer_callback(e, mode == TFK_EXCHANGE_SHARDED ? on_layer : nullptr, c))
     return bail(-1);
@@ -1057,28 +1037,28 @@ extern "C" {
 int tfk_comm_available(tfk_engine* e, int mode) {
   // everything tfk_comm_create can refuse WITHOUT talking to another rank: RCCL loadable with every symbol bound, a known
   // exchange mode, an engine whose regions and stream can be queried on a device this process can select
-  if (!e) return failx(-1, "NULL argument");
-  if (mode != TFK_EXCHANGE_SHARDED && mode != TFK_EXCHANGE_ALLREDUCE) return failx(-1, "unknown exchange mode %d", mode);
+  if (!e) return fail(-1, "NULL argument");
+  if (mode != TFK_EXCHANGE_SHARDED && mode != TFK_EXCHANGE_ALLREDUCE) return fail(-1, "unknown exchange mode %d", mode);
   Rccl* r = rccl();
-  if (!r->error.empty()) return failx(-1, "%s", r->error.c_str());
+  if (!r->error.empty()) return fail(-1, "%s", r->error.c_str());
   void* p = nullptr;
   size_t n = 0;
   int nb = 0;
-  XCHK(tfk_stream(e, &p));
-  XCHK(tfk_reduce_region(e, &p, &n));
+  CHK(tfk_stream(e, &p));
+  CHK(tfk_reduce_region(e, &p, &n));
   hipPointerAttribute_t attr;
-  XHIP(hipPointerGetAttributes(&attr, p));
-  XHIP(hipSetDevice(attr.device));
-  XCHK(tfk_param_region(e, &p, &n));
-  XCHK(tfk_num_buckets(e, &nb));
-  if (nb < 3) return failx(-1, "engine announces %d buckets", nb);
+  HIPCHK(hipPointerGetAttributes(&attr, p));
+  HIPCHK(hipSetDevice(attr.device));
+  CHK(tfk_param_region(e, &p, &n));
+  CHK(tfk_num_buckets(e, &nb));
+  if (nb < 3) return fail(-1, "engine announces %d buckets", nb);
   return 0;
 }
 
 int tfk_comm_unique_id(void* id, size_t capacity, size_t* size) {
-  if (!id || capacity < sizeof(ncclUniqueId)) return failx(-1, "tfk_comm_unique_id needs %zu bytes", sizeof(ncclUniqueId));
+  if (!id || capacity < sizeof(ncclUniqueId)) return fail(-1, "tfk_comm_unique_id needs %zu bytes", sizeof(ncclUniqueId));
   Rccl* r = rccl();
-  if (!r->error.empty()) return failx(-1, "%s", r->error.c_str());
+  if (!r->error.empty()) return fail(-1, "%s", r->error.c_str());
   ncclUniqueId uid;
   XNCCL(r->GetUniqueId(&uid));
   memcpy(id, &uid, sizeof(uid));
@@ -1088,18 +1068,18 @@ int tfk_comm_unique_id(void* id, size_t capacity, size_t* size) {
 
 int tfk_comm_create(tfk_engine* e, const void* id, size_t id_size, int rank, int world, int mode, size_t bucket_bytes,
                     tfk_comm** out) {
-  if (!e || !id || !out) return failx(-1, "NULL argument");
-  if (world < 1 || rank < 0 || rank >= world) return failx(-1, "rank %d of world %d", rank, world);
-  if (id_size != sizeof(ncclUniqueId)) return failx(-1, "unique id of %zu bytes, expected %zu", id_size, sizeof(ncclUniqueId));
+  if (!e || !id || !out) return fail(-1, "NULL argument");
+  if (world < 1 || rank < 0 || rank >= world) return fail(-1, "rank %d of world %d", rank, world);
+  if (id_size != sizeof(ncclUniqueId)) return fail(-1, "unique id of %zu bytes, expected %zu", id_size, sizeof(ncclUniqueId));
   Rccl* r = rccl();
-  if (!r->error.empty()) return failx(-1, "%s", r->error.c_str());
+  if (!r->error.empty()) return fail(-1, "%s", r->error.c_str());
   {  // the communicator binds to the CURRENT device: the engine's
     void* p = nullptr;
     size_t n = 0;
-    XCHK(tfk_reduce_region(e, &p, &n));
+    CHK(tfk_reduce_region(e, &p, &n));
     hipPointerAttribute_t attr;
-    XHIP(hipPointerGetAttributes(&attr, p));
-    XHIP(hipSetDevice(attr.device));
+    HIPCHK(hipPointerGetAttributes(&attr, p));
+    HIPCHK(hipSetDevice(attr.device));
   }
   RcclBackend* be = new RcclBackend;
   be->rank = rank;
@@ -1110,20 +1090,20 @@ int tfk_comm_create(tfk_engine* e, const void* id, size_t id_size, int rank, int
   if (rc != ncclSuccess) {
     be->comm = nullptr;
     delete be;
-    return failx((int)rc, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world, r->GetErrorString(rc));
+    return fail((int)rc, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world, r->GetErrorString(rc));
   }
   return attach(e, be, mode, bucket_bytes, out);
 }
 
 int tfk_loopback_create(int world, tfk_loopback** out) {
-  if (!out || world < 1 || world > kLoopMaxWorld) return failx(-1, "loopback group of %d ranks (1 .. %d)", world, kLoopMaxWorld);
+  if (!out || world < 1 || world > kLoopMaxWorld) return fail(-1, "loopback group of %d ranks (1 .. %d)", world, kLoopMaxWorld);
   tfk_loopback* g = new tfk_loopback;
   g->world = world;
   g->slot.resize(world);
   hipError_t he = hipEventCreateWithFlags(&g->sum_done, hipEventDisableTiming);
   if (he != hipSuccess) {
     delete g;
-    return failx((int)he, "hipEventCreate failed: %s", hipGetErrorString(he));
+    return fail((int)he, "hipEventCreate failed: %s", hipGetErrorString(he));
   }
   *out = g;
   return 0;
@@ -1136,8 +1116,8 @@ int tfk_loopback_destroy(tfk_loopback* g) {
   return 0;
 }
 int tfk_comm_create_loopback(tfk_engine* e, tfk_loopback* group, int rank, int mode, size_t bucket_bytes, tfk_comm** out) {
-  if (!e || !group || !out) return failx(-1, "NULL argument");
-  if (rank < 0 || rank >= group->world) return failx(-1, "rank %d of a loopback group of %d", rank, group->world);
+  if (!e || !group || !out) return fail(-1, "NULL argument");
+  if (rank < 0 || rank >= group->world) return fail(-1, "rank %d of a loopback group of %d", rank, group->world);
   LoopBackend* be = new LoopBackend;
   be->rank = rank;
   be->world = group->world;
@@ -1168,7 +1148,7 @@ int tfk_comm_destroy(tfk_comm* c) {
 }
 
 int tfk_comm_info(tfk_comm* c, int* rank, int* world, int* mode, int* gathers_shadow) {
-  if (!c) return failx(-1, "comm is NULL");
+  if (!c) return fail(-1, "comm is NULL");
   if (rank) *rank = c->be->rank;
   if (world) *world = c->be->world;
   if (mode) *mode = c->mode;
@@ -1177,15 +1157,15 @@ int tfk_comm_info(tfk_comm* c, int* rank, int* world, int* mode, int* gathers_sh
 }
 
 int tfk_comm_idle(tfk_comm* c) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
-  XCHK(tfk_zero_accumulators(c->e));
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
+  CHK(tfk_zero_accumulators(c->e));
   // the order accumulate(TFK_LAST_MICROBATCH) announces them in: scalars + BN increments, the weight matrices from the
   // output layer down, the bias / beta gradients -- every rank must launch the same collectives in the same order
-  XCHK(announce(c, c->L + 2));
-  for (int b = 0; b <= c->L; ++b) XCHK(announce(c, b));
-  XCHK(announce(c, c->L + 1));
+  CHK(announce(c, c->L + 2));
+  for (int b = 0; b <= c->L; ++b) CHK(announce(c, b));
+  CHK(announce(c, c->L + 1));
   return 0;
 }
 
@@ -1216,30 +1196,30 @@ Phases g_phases;
 // for work that should run while the GPU is busy (the dispenser's prefetch of the next batch): round 4 ran that work BEFORE
 // the tail collectives, Adam and the gathers were launched, so a rank with slow I/O held every peer in its collectives.
 int tfk_comm_apply_enqueue(tfk_comm* c) {
-  if (!c) return failx(-1, "comm is NULL");
-  if (c->apply_enqueued) return failx(-1, "tfk_comm_apply_enqueue twice without tfk_comm_apply_end");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
+  if (!c) return fail(-1, "comm is NULL");
+  if (c->apply_enqueued) return fail(-1, "tfk_comm_apply_enqueue twice without tfk_comm_apply_end");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
   g_phases.start();
   // engine-stream time between the last backward kernel and the first optimiser kernel: the tail collectives, the waits for the
   // spans still in flight, tfk_apply_begin -- what the exchange leaves exposed in front of Adam
   Timed tail(c, PH_TAIL_EXPOSED, c->engine_stream);
-  XCHK(flush_range(c, inline_tail()));
+  CHK(flush_range(c, inline_tail()));
   g_phases.mark(0);
   const size_t head_off = c->buckets.back().first, head_n = c->buckets.back().second;
   for (size_t i = 0; i < c->num_spans; ++i) {
     Span& s = c->spans[i];
-    if (s.off < head_off + head_n && s.off + s.n > head_off) XCHK(wait_span(c, s));
+    if (s.off < head_off + head_n && s.off + s.n > head_off) CHK(wait_span(c, s));
   }
-  XCHK(drain(c));  // (gathers of the previous step that no forward pass has consumed: none in a training loop)
+  CHK(drain(c));  // (gathers of the previous step that no forward pass has consumed: none in a training loop)
   g_phases.mark(1);
-  XCHK(tfk_apply_begin(c->e));
+  CHK(tfk_apply_begin(c->e));
   g_phases.mark(2);
   bool via_shadow = c->shadow != nullptr;
   if (via_shadow) {
     int direct = 0;
-    XCHK(tfk_apply_writes_shadow(c->e, &direct));
-    if (!direct) return failx(-1, "mixed-precision engine with an arena-mirroring shadow that the optimiser does not write");
+    CHK(tfk_apply_writes_shadow(c->e, &direct));
+    if (!direct) return fail(-1, "mixed-precision engine with an arena-mirroring shadow that the optimiser does not write");
   }
   const int W = c->be->world, R = c->be->rank;
   // every span is complete by now (the head wait above covered them all, see wait_span); what this rank updates -- its 1/W of
@@ -1248,7 +1228,7 @@ int tfk_comm_apply_enqueue(tfk_comm* c) {
   std::vector<std::pair<size_t, size_t>> sharded, mine;
   for (size_t i = 0; i < c->num_spans; ++i) {
     Span& s = c->spans[i];
-    XCHK(wait_span(c, s));
+    CHK(wait_span(c, s));
     if (s.rs) {
       for (const Piece& p : pieces_of(c, s.off, s.n)) {
         const size_t per = p.n / W;
@@ -1262,24 +1242,24 @@ int tfk_comm_apply_enqueue(tfk_comm* c) {
     }
   }
   std::sort(mine.begin(), mine.end());
-  XCHK(tail.end());
+  CHK(tail.end());
   Timed adam(c, PH_ADAM, c->engine_stream);
   for (size_t i = 0; i < mine.size();) {
     size_t off = mine[i].first, n = mine[i].second, j = i + 1;
     while (j < mine.size() && mine[j].first == off + n) n += mine[j++].second;
-    XCHK(tfk_apply_span(c->e, off, n));
+    CHK(tfk_apply_span(c->e, off, n));
     i = j;
   }
-  XCHK(adam.end());
+  CHK(adam.end());
   g_phases.mark(3);
   bool planes_any = false;
   if (!sharded.empty()) {
     if (c->gather_planes) {
       int direct = 0;
-      XCHK(tfk_apply_writes_shadow(c->e, &direct));
-      if (!direct) return failx(-1, "TFK_DP_GATHER=planes and an optimiser step that does not write the three-plane twins");
+      CHK(tfk_apply_writes_shadow(c->e, &direct));
+      if (!direct) return fail(-1, "TFK_DP_GATHER=planes and an optimiser step that does not write the three-plane twins");
     } else if (c->masters_stale && !via_shadow) {
-      return failx(-1, "sharded fp32 masters and a step that does not write the shadow");
+      return fail(-1, "sharded fp32 masters and a step that does not write the shadow");
     }
     std::sort(sharded.begin(), sharded.end());  // lowest offsets (layer 0) first: the order the next forward pass reads in
     c->gathers_used = 0;
@@ -1290,25 +1270,25 @@ int tfk_comm_apply_enqueue(tfk_comm* c) {
       // pass could not start before it anyway, and the hop to the comm stream and back is saved; the others follow on the
       // comm stream, under the first layers
       Timed exposed(c, PH_GATHER_EXPOSED, c->engine_stream);  // (nothing runs beside it: the forward pass waits for exactly this)
-      XCHK(gather_pieces(c, sharded[0], c->engine_stream, via_shadow, &derived_current, &planes_any));
-      XCHK(exposed.end());
+      CHK(gather_pieces(c, sharded[0], c->engine_stream, via_shadow, &derived_current, &planes_any));
+      CHK(exposed.end());
       c->cur_ag += 1;
       first_on_comm = 1;
     }
     if (first_on_comm < sharded.size()) {
-      XHIP(hipEventRecord(c->ev_adam, c->engine_stream));
-      XHIP(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
+      HIPCHK(hipEventRecord(c->ev_adam, c->engine_stream));
+      HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
     }
     for (size_t k = first_on_comm; k < sharded.size(); ++k) {
       const auto& s = sharded[k];
       if (c->gathers_used == c->gather_events.size()) {
         hipEvent_t ev;
-        XCHK(new_event(&ev));
+        CHK(new_event(&ev));
         c->gather_events.push_back(ev);
       }
       hipEvent_t done = c->gather_events[c->gathers_used++];
-      XCHK(gather_pieces(c, s, c->comm_stream, via_shadow, &derived_current, &planes_any));
-      XHIP(hipEventRecord(done, c->comm_stream));
+      CHK(gather_pieces(c, s, c->comm_stream, via_shadow, &derived_current, &planes_any));
+      HIPCHK(hipEventRecord(done, c->comm_stream));
       Gather g;
       g.off = s.first; g.n = s.second; g.done = done;
       c->pending.push_back(g);
@@ -1320,7 +1300,7 @@ int tfk_comm_apply_enqueue(tfk_comm* c) {
         if (std::find(c->shard_spans.begin(), c->shard_spans.end(), s) == c->shard_spans.end()) c->shard_spans.push_back(s);
     } else {
       if (planes_any) c->masters_stale = true;  // (gather_pieces noted which matrices)
-      if (!derived_current) XCHK(tfk_params_touched(c->e));  // parameters outside this rank's spans change behind the optimiser's back
+      if (!derived_current) CHK(tfk_params_touched(c->e));  // parameters outside this rank's spans change behind the optimiser's back
     }
   }
   c->last_spans.clear();
@@ -1341,42 +1321,42 @@ int tfk_comm_apply_enqueue(tfk_comm* c) {
   return 0;
 }
 int tfk_comm_apply_end(tfk_comm* c, float* average_loss) {
-  if (!c) return failx(-1, "comm is NULL");
-  if (!c->apply_enqueued) return failx(-1, "tfk_comm_apply_end without tfk_comm_apply_enqueue");
+  if (!c) return fail(-1, "comm is NULL");
+  if (!c->apply_enqueued) return fail(-1, "tfk_comm_apply_end without tfk_comm_apply_enqueue");
   c->apply_enqueued = false;
-  XHIP(hipSetDevice(c->device));
-  XCHK(tfk_apply_end(c->e, average_loss));
+  HIPCHK(hipSetDevice(c->device));
+  CHK(tfk_apply_end(c->e, average_loss));
   g_phases.mark(5);
   g_phases.calls += 1;
   if (c->timing) c->timed_steps += 1;
   if (c->verify_left > 0 && c->apply_sharded) {
     c->verify_left -= 1;
-    XCHK(verify_replicas(c, c->apply_via_shadow, c->apply_planes));
+    CHK(verify_replicas(c, c->apply_via_shadow, c->apply_planes));
   }
   return 0;
 }
 int tfk_comm_apply(tfk_comm* c, float* average_loss) {
-  XCHK(tfk_comm_apply_enqueue(c));
+  CHK(tfk_comm_apply_enqueue(c));
   return tfk_comm_apply_end(c, average_loss);
 }
 
 int tfk_comm_finish_reduce(tfk_comm* c) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
-  XCHK(flush_range(c, inline_tail()));
-  for (size_t i = 0; i < c->num_spans; ++i) XCHK(wait_span(c, c->spans[i]));
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
+  CHK(flush_range(c, inline_tail()));
+  for (size_t i = 0; i < c->num_spans; ++i) CHK(wait_span(c, c->spans[i]));
   return 0;
 }
 
 int tfk_comm_eval_finish(tfk_comm* c, float* average_loss) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
   const size_t off = c->buckets.back().first, n = c->buckets.back().second;
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head) return failx(-1, "tfk_comm_eval_finish in the middle of a training step");
-  XCHK(launch_range(c, off, off + n, inline_tail()));
-  XCHK(wait_span(c, c->spans[0]));
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head) return fail(-1, "tfk_comm_eval_finish in the middle of a training step");
+  CHK(launch_range(c, off, off + n, inline_tail()));
+  CHK(wait_span(c, c->spans[0]));
   c->num_spans = 0;
   c->waited_upto = 0;
   c->cur_ar = 0;
@@ -1384,30 +1364,30 @@ int tfk_comm_eval_finish(tfk_comm* c, float* average_loss) {
 }
 
 int tfk_comm_drain(tfk_comm* c) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
   return drain(c);
 }
 
 int tfk_comm_masters_stale(tfk_comm* c, int* stale) {
-  if (!c || !stale) return failx(-1, "NULL argument");
+  if (!c || !stale) return fail(-1, "NULL argument");
   *stale = c->masters_stale ? 1 : 0;
   return 0;
 }
 
 int tfk_comm_gather_masters(tfk_comm* c) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
-  XCHK(drain(c));
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
+  CHK(drain(c));
   if (!c->masters_stale) return 0;
   std::sort(c->shard_spans.begin(), c->shard_spans.end());
-  XHIP(hipEventRecord(c->ev_adam, c->engine_stream));
-  XHIP(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
+  HIPCHK(hipEventRecord(c->ev_adam, c->engine_stream));
+  HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
   for (const auto& s : c->shard_spans)
-    XCHK(gather_span(c, c->param + s.first, s.second / c->be->world * sizeof(float), c->comm_stream));
-  XHIP(hipEventRecord(c->ev_adam, c->comm_stream));
-  XHIP(hipStreamWaitEvent(c->engine_stream, c->ev_adam, 0));
+    CHK(gather_span(c, c->param + s.first, s.second / c->be->world * sizeof(float), c->comm_stream));
+  HIPCHK(hipEventRecord(c->ev_adam, c->comm_stream));
+  HIPCHK(hipStreamWaitEvent(c->engine_stream, c->ev_adam, 0));
   c->masters_stale = false;
   return 0;
 }
@@ -1416,76 +1396,76 @@ namespace {
 // Everything a rank holds of the optimiser's state becomes whole again: the fp32 masters left with their owners (if any) and
 // Adam's moments of every piece sharded so far.  COLLECTIVE.  After it any assignment of shards to ranks is as good as any other.
 int rehome(tfk_comm* c) {
-  XCHK(tfk_comm_gather_masters(c));
+  CHK(tfk_comm_gather_masters(c));
   c->shard_spans.clear();
   if (c->owned_pieces.empty()) return 0;
   std::sort(c->owned_pieces.begin(), c->owned_pieces.end());
-  XHIP(hipEventRecord(c->ev_adam, c->engine_stream));
-  XHIP(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
+  HIPCHK(hipEventRecord(c->ev_adam, c->engine_stream));
+  HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_adam, 0));
   const size_t W = (size_t)c->be->world;
   for (const auto& p : c->owned_pieces) {
-    XCHK(gather_span(c, c->adam_m + p.first, p.second / W * sizeof(float), c->comm_stream, false));
-    XCHK(gather_span(c, c->adam_v + p.first, p.second / W * sizeof(float), c->comm_stream, false));
+    CHK(gather_span(c, c->adam_m + p.first, p.second / W * sizeof(float), c->comm_stream, false));
+    CHK(gather_span(c, c->adam_v + p.first, p.second / W * sizeof(float), c->comm_stream, false));
   }
-  XHIP(hipEventRecord(c->ev_adam, c->comm_stream));
-  XHIP(hipStreamWaitEvent(c->engine_stream, c->ev_adam, 0));
+  HIPCHK(hipEventRecord(c->ev_adam, c->comm_stream));
+  HIPCHK(hipStreamWaitEvent(c->engine_stream, c->ev_adam, 0));
   c->owned_pieces.clear();
   return 0;
 }
 }  // namespace
 
 int tfk_comm_set_exchange(tfk_comm* c, int algo, int wire) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return failx(-1, "tfk_comm_set_exchange in the middle of a step");
-  if (algo != -1 && algo != TFK_ALGO_RCCL && algo != TFK_ALGO_DIRECT) return failx(-1, "exchange algorithm %d", algo);
-  if (wire != -1 && wire != TFK_WIRE_FP32 && wire != TFK_WIRE_BF16) return failx(-1, "wire format %d", wire);
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return fail(-1, "tfk_comm_set_exchange in the middle of a step");
+  if (algo != -1 && algo != TFK_ALGO_RCCL && algo != TFK_ALGO_DIRECT) return fail(-1, "exchange algorithm %d", algo);
+  if (wire != -1 && wire != TFK_WIRE_FP32 && wire != TFK_WIRE_BF16) return fail(-1, "wire format %d", wire);
   if (algo != -1) {
     c->algo_rs = c->algo_ag = algo;
     c->chosen_by = 3;
   }
   if (wire != -1) c->wire_bf16 = wire == TFK_WIRE_BF16;
-  if (c->mode == TFK_EXCHANGE_SHARDED && (c->wire_bf16 || c->algo_rs == TFK_ALGO_DIRECT)) XCHK(ensure_stage(c));
+  if (c->mode == TFK_EXCHANGE_SHARDED && (c->wire_bf16 || c->algo_rs == TFK_ALGO_DIRECT)) CHK(ensure_stage(c));
   return 0;
 }
 
 int tfk_comm_set_gather(tfk_comm* c, int planes) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  XCHK(raise_remembered(c));
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return failx(-1, "tfk_comm_set_gather in the middle of a step");
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  CHK(raise_remembered(c));
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return fail(-1, "tfk_comm_set_gather in the middle of a step");
   if (planes) {
     bool twins = false;
     for (const tfk_comm::TwinOf& t : c->twin) twins = twins || t.bytes > 0;
     if (!twins || c->mode != TFK_EXCHANGE_SHARDED)
-      return failx(-1, "nothing to gather in place of the parameters: owner-written three-plane twins exist under the emulated fp32 "
+      return fail(-1, "nothing to gather in place of the parameters: owner-written three-plane twins exist under the emulated fp32 "
                        "arithmetic and the sharded exchange only");
-    XCHK(rehome(c));  // (the sharding unit changes with the switch: nothing may be left with a previous owner)
+    CHK(rehome(c));  // (the sharding unit changes with the switch: nothing may be left with a previous owner)
     c->gather_planes = true;
     return 0;
   }
   // back to fp32 gathers: the masters the plane gathers left with their owners, and Adam's moments, come home first
   // (COLLECTIVE, like this call)
-  XCHK(rehome(c));
+  CHK(rehome(c));
   c->gather_planes = false;
   return 0;
 }
 
 int tfk_comm_set_bucket_bytes(tfk_comm* c, size_t bucket_bytes) {
-  if (!c) return failx(-1, "comm is NULL");
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return failx(-1, "tfk_comm_set_bucket_bytes in the middle of a step");
+  if (!c) return fail(-1, "comm is NULL");
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return fail(-1, "tfk_comm_set_bucket_bytes in the middle of a step");
   // another span cut is another assignment of shards to ranks: what lives with a shard's owner only -- fp32 masters (mixed
   // precision, plane gathers) and Adam's moments (always) -- comes home first, COLLECTIVE like this call, or the new owner would
   // update stale values
-  XCHK(rehome(c));
+  CHK(rehome(c));
   if (bucket_bytes == 0) bucket_bytes = kDefaultBucketBytes;
   c->min_floats = std::max<size_t>(1, bucket_bytes / 4);
   return 0;
 }
 
 int tfk_comm_get_exchange(tfk_comm* c, int* algo_reduce_scatter, int* algo_all_gather, int* wire, int* chosen_by, double* tune_us) {
-  if (!c) return failx(-1, "comm is NULL");
+  if (!c) return fail(-1, "comm is NULL");
   if (algo_reduce_scatter) *algo_reduce_scatter = c->algo_rs;
   if (algo_all_gather) *algo_all_gather = c->algo_ag;
   if (wire) *wire = c->wire_bf16 ? TFK_WIRE_BF16 : TFK_WIRE_FP32;
@@ -1495,9 +1475,9 @@ int tfk_comm_get_exchange(tfk_comm* c, int* algo_reduce_scatter, int* algo_all_g
 }
 
 int tfk_comm_tune(tfk_comm* c, size_t floats, int iters) {
-  if (!c) return failx(-1, "comm is NULL");
-  XHIP(hipSetDevice(c->device));
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return failx(-1, "tfk_comm_tune in the middle of a step");
+  if (!c) return fail(-1, "comm is NULL");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return fail(-1, "tfk_comm_tune in the middle of a step");
   const int W = c->be->world, R = c->be->rank;
   const size_t unit = 4 * (size_t)W;
   floats = std::max(unit, floats / unit * unit);
@@ -1515,43 +1495,43 @@ int tfk_comm_tune(tfk_comm* c, size_t floats, int iters) {
       if (*b) (void)hipEventDestroy(*b);
     }
   } scratch = {&buf, &recv, &a, &b};
-  XHIP(hipMalloc((void**)&buf, floats * sizeof(float)));
-  XHIP(hipMalloc((void**)&recv, floats * sizeof(float)));
-  XHIP(hipMemsetAsync(buf, 0, floats * sizeof(float), c->comm_stream));
-  XHIP(hipEventCreate(&a));
-  XHIP(hipEventCreate(&b));
+  HIPCHK(hipMalloc((void**)&buf, floats * sizeof(float)));
+  HIPCHK(hipMalloc((void**)&recv, floats * sizeof(float)));
+  HIPCHK(hipMemsetAsync(buf, 0, floats * sizeof(float), c->comm_stream));
+  HIPCHK(hipEventCreate(&a));
+  HIPCHK(hipEventCreate(&b));
   hipStream_t st = c->comm_stream;
   auto run = [&](int what) -> int {  // 0 / 1: reduce-scatter rccl / direct, 2 / 3: all-gather rccl / direct
     if (what == 0) return c->be->reduce_scatter(buf, per, st);
     if (what == 1) {
-      XCHK(c->be->exchange_shards(buf, recv, per * sizeof(float), st));
+      CHK(c->be->exchange_shards(buf, recv, per * sizeof(float), st));
       const unsigned sb = (unsigned)std::min<size_t>((per / 4 + 255) / 256, 1 << 13);
       hipLaunchKernelGGL(direct_sum_kernel, dim3(sb ? sb : 1), dim3(256), 0, st, buf + (size_t)R * per, recv, R, W, per);
-      XHIP(hipGetLastError());
+      HIPCHK(hipGetLastError());
       return 0;
     }
     if (what == 2) return c->be->all_gather(buf, per * sizeof(float), st);
     return c->be->all_gather_direct(buf, per * sizeof(float), st);
   };
   for (int what = 0; what < 4; ++what) {
-    XCHK(run(what));  // (warm-up: connection set-up, first-use kernels)
-    XHIP(hipStreamSynchronize(st));
-    XHIP(hipEventRecord(a, st));
-    for (int i = 0; i < iters; ++i) XCHK(run(what));
-    XHIP(hipEventRecord(b, st));
-    XHIP(hipStreamSynchronize(st));
+    CHK(run(what));  // (warm-up: connection set-up, first-use kernels)
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventRecord(a, st));
+    for (int i = 0; i < iters; ++i) CHK(run(what));
+    HIPCHK(hipEventRecord(b, st));
+    HIPCHK(hipStreamSynchronize(st));
     float ms = 0.f;
-    XHIP(hipEventElapsedTime(&ms, a, b));
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
     // the slowest rank's time counts, and every rank must reach the same decision: MAX over the ranks, in integer nanoseconds
     unsigned long long v[2] = {(unsigned long long)(1e6 * ms / iters), 0};
-    XCHK(c->be->min_max(v, st));
+    CHK(c->be->min_max(v, st));
     c->tune_us[what] = 1e-3 * (double)v[1];
   }
   // RCCL's own collective unless the direct form is clearly faster (3 %: a tie goes to the vendor's code path)
   c->algo_rs = c->tune_us[1] < 0.97 * c->tune_us[0] ? TFK_ALGO_DIRECT : TFK_ALGO_RCCL;
   c->algo_ag = c->tune_us[3] < 0.97 * c->tune_us[2] ? TFK_ALGO_DIRECT : TFK_ALGO_RCCL;
   c->chosen_by = 2;
-  if (c->mode == TFK_EXCHANGE_SHARDED && (c->wire_bf16 || c->algo_rs == TFK_ALGO_DIRECT)) XCHK(ensure_stage(c));
+  if (c->mode == TFK_EXCHANGE_SHARDED && (c->wire_bf16 || c->algo_rs == TFK_ALGO_DIRECT)) CHK(ensure_stage(c));
   if (R == 0 && getenv("TFK_DP_QUIET") == nullptr)
     fprintf(stderr, "tfkaldi_amd exchange tuned on %zu floats, %d ranks (us, slowest rank): reduce-scatter rccl %.1f / direct %.1f -> %s; "
             "all-gather rccl %.1f / direct %.1f -> %s\n", floats, W, c->tune_us[0], c->tune_us[1],
@@ -1561,8 +1541,8 @@ int tfk_comm_tune(tfk_comm* c, size_t floats, int iters) {
 }
 
 int tfk_comm_timing(tfk_comm* c, int on) {
-  if (!c) return failx(-1, "comm is NULL");
-  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return failx(-1, "tfk_comm_timing in the middle of a step");
+  if (!c) return fail(-1, "comm is NULL");
+  if (c->num_spans || c->have_range || c->have_hold || c->have_head || c->apply_enqueued) return fail(-1, "tfk_comm_timing in the middle of a step");
   c->timing = on != 0;
   c->timed.clear();
   c->timing_used = 0;
@@ -1571,14 +1551,14 @@ int tfk_comm_timing(tfk_comm* c, int on) {
 }
 
 int tfk_comm_timing_read(tfk_comm* c, double* ms_per_step, int capacity, long* steps) {
-  if (!c || !ms_per_step) return failx(-1, "NULL argument");
-  XHIP(hipSetDevice(c->device));
-  XHIP(hipStreamSynchronize(c->engine_stream));
-  XHIP(hipStreamSynchronize(c->comm_stream));
+  if (!c || !ms_per_step) return fail(-1, "NULL argument");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->engine_stream));
+  HIPCHK(hipStreamSynchronize(c->comm_stream));
   double sum[PH_COUNT] = {0};
   for (const tfk_comm::TimedPair& t : c->timed) {
     float ms = 0.f;
-    XHIP(hipEventElapsedTime(&ms, t.a, t.b));
+    HIPCHK(hipEventElapsedTime(&ms, t.a, t.b));
     sum[t.phase] += ms;
   }
   const double per = c->timed_steps > 0 ? 1.0 / (double)c->timed_steps : 0.0;
@@ -1589,7 +1569,7 @@ int tfk_comm_timing_read(tfk_comm* c, double* ms_per_step, int capacity, long* s
 
 int tfk_comm_last_step(tfk_comm* c, int* reduce_scatters, int* all_gathers, int* all_reduces, size_t* spans, int capacity,
                        int* num_spans) {
-  if (!c) return failx(-1, "comm is NULL");
+  if (!c) return fail(-1, "comm is NULL");
   if (reduce_scatters) *reduce_scatters = c->last_rs;
   if (all_gathers) *all_gathers = c->last_ag;
   if (all_reduces) *all_reduces = c->last_ar;

@@ -27,31 +27,14 @@
 #include <vector>
 
 #include "../../include/tfkaldi_hip.h"
-
-namespace tfk {
-int set_error(int code, const char* msg);  // engine.hip (thread-local message behind tfk_last_error)
-}
+#include "tfk_error.h"
 
 namespace {
 
+using tfk::fail;
+
 constexpr double kEps = 2.220446049250313e-16;  // numpy.finfo(float).eps: base.py:84,94
 constexpr int kMaxFft = 4096;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return tfk::set_error(code ? code : -1, buf);
-}
-
-#define HIPCHK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return fail((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 struct Batch {
   const void* sig;
