@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TFK_ABI_VERSION 20
+#define TFK_ABI_VERSION 21
 
 typedef struct tfk_engine tfk_engine;
 
@@ -789,6 +789,67 @@ int tfk_ctc_mmi_logits(void* stream, const float* logits, int64_t ld, int32_t O,
  * hyp_off / ref_off [U + 1]; every reference at most 511 long (a longer one, or a negative length, gives dist[u] = -1). */
 int tfk_label_edit_distance(void* stream, const int32_t* hyp, const int32_t* hyp_off, const int32_t* ref,
                             const int32_t* ref_off, int32_t U, int32_t* dist);
+
+/* ---- (ABI 21) streaming CTC decode: the prefix beam search, resumable across chunks --------------
+ *
+ * A stream holds `lanes` independent sessions (one workgroup each, as the batch search has one per utterance).  A lane owns, in
+ * device memory that lives as long as the stream: its trie of 2 * max_frames * beam_width + 64 64-bit words (sized by
+ * max_frames, not by a chunk), and the beam after its last frame -- per prefix pb, pnb, tot, node, parent, last, len, src, with
+ * a model g and ctx, and the model's END TERM table[ctx][O - 1] (graph: weight[state][O - 1]) gathered when the state is
+ * saved, lm_weight beside it -- plus the beam's size, its dead count and the score offset (a double).  A push runs the frame
+ * loop of tfk_ctc_beam* over the chunk's rows from that state to that state; a result ranks and traces back from it and needs
+ * no model.
+ *   IDENTITY.  After pushes whose chunks, concatenated per lane, are z[0:t], tfk_ctc_stream_result gives for that lane what
+ *   the one-shot entry (tfk_ctc_beam_logits / _lm_logits / _graph_logits / _topk_logits with the same beam_width, label_topk,
+ *   model, lm_weight, label_bonus and flags) gives on z[0:t]: labels, lengths, score and am_score bit for bit, for every t
+ *   and every chunking, empty chunks and idle lanes included.  (Node ids differ with the table's capacity; nothing is ordered
+ *   by them.)
+ *   ZERO FRAMES.  A lane without frames gives the empty hypothesis with am_score 0 (score: 0, or the end term of the start
+ *   context under TFK_CTC_LM_EOS), as the one-shot search gives for a zero-frame utterance; padding paths have length 0 and
+ *   both scores -inf.
+ *   A RESULT READS ONLY.  Asking never changes what later pushes produce.
+ *   BINDING.  A lane binds to the model of its first push after a reset; a push that gives it 0 frames counts.  The binding is
+ *   the kind (none, table, graph), the identity of the tables, order / num_states / start, lm_weight and label_bonus (bits).
+ *   The identity of the engine's model is a counter that every tfk_ctc_lm_set / tfk_ctc_graph_set advances, not its address.
+ *   A push under any other model while a lane holds frames returns non-zero and names the lane; a lane without frames binds
+ *   anew.  TFK_CTC_LM_EOS on a stream with a lane that is unbound, or bound without a model, returns non-zero.  Reset unbinds.
+ *   The model must stay alive during a push (as for the one-shot entries), not after it.
+ *   REFUSALS come before anything is enqueued and leave every lane as it was: a NULL pointer, a negative chunk length, lengths
+ *   that do not sum to T, a lane that would pass max_frames (the message names the lane and the limit), an output_dim other
+ *   than the stream's O, lanes outside [1, 1024], max_frames outside [1, 524286], beam_width / output_dim / label_topk outside
+ *   the limits of tfk_ctc_beam (label_topk == 0) or tfk_ctc_beam_topk, top_paths outside [1, beam_width], hyp_cap < 0.
+ *   ORDER.  A stream is used from one HIP stream at a time; its calls are stream-ordered.  Only tfk_ctc_stream_result waits.
+ * Not here: entries on raw (unspliced) frames -- the device splice pads with zeros at the edges of what it is given, which is
+ * wrong in mid-stream (splice on the host: StreamSplicer in the Python package) --, streaming greedy decoding, endpointing,
+ * and capture into a hipGraph (a push and a result allocate stream-ordered scratch). */
+typedef struct tfk_ctc_stream tfk_ctc_stream;
+/* bytes of device memory a stream of this shape holds (16 * max_frames * beam_width per lane dominate) */
+int tfk_ctc_stream_bytes(int32_t O, int32_t lanes, int32_t beam_width, int32_t max_frames, int32_t label_topk, size_t* bytes);
+/* label_topk == 0: the unpruned search (O <= 64); else the pruned one, limits as tfk_ctc_beam_topk.  On the current device;
+ * every lane empty, unbound, at 0 frames. */
+int tfk_ctc_stream_create(int32_t O, int32_t lanes, int32_t beam_width, int32_t max_frames, int32_t label_topk,
+                          tfk_ctc_stream** out);
+int tfk_ctc_stream_destroy(tfk_ctc_stream* s); /* after the work enqueued on it is over */
+/* lane (-1: every lane) back to an empty trie, 0 frames, unbound: two stream-ordered memsets */
+int tfk_ctc_stream_reset(tfk_ctc_stream* s, void* stream, int32_t lane);
+int tfk_ctc_stream_frames(tfk_ctc_stream* s, int32_t* frames /* host [lanes] */);
+/* Tests / tools, and callers with their own logits: DEVICE logits [T, ld], chunk_len[lanes] HOST (>= 0, sum = T, lane l's rows
+ * follow lane l - 1's).  Model as tfk_ctc_beam_lm_logits / tfk_ctc_beam_graph_logits take it (device tables, not validated):
+ * lm_dev == NULL acoustic (the arguments after it are not read); next_dev == NULL the n-gram table of `order`; else the graph
+ * lm_dev = weight, next_dev, num_states, start. */
+int tfk_ctc_stream_push_logits(tfk_ctc_stream* s, void* stream, const float* logits, int64_t ld, int32_t T,
+                               const int32_t* chunk_len, const float* lm_dev, int32_t order, const int32_t* next_dev,
+                               int32_t num_states, int32_t start, float lm_weight, float label_bonus);
+/* Evaluation-mode forward of X [T, ldx] (already SPLICED rows, host pointer, as tfk_ctc_beam takes X; T == 0: no forward) and
+ * the same push on the engine's logits and stream; parameters, accumulators and statistics are untouched.  flags: 0 or
+ * TFK_CTC_LM (the engine's model, table or graph, ranks with lm_weight / label_bonus; non-zero if none is set). */
+int tfk_ctc_stream_push(tfk_engine* e, tfk_ctc_stream* s, const float* X, int64_t ldx, int32_t T, const int32_t* chunk_len,
+                        float lm_weight, float label_bonus, int flags);
+/* The N-best of every lane over the frames pushed so far.  HOST outputs; synchronises `stream`.  flags: 0 or TFK_CTC_LM_EOS.
+ * hyp[(n * lanes + l) * hyp_cap + j], j < min(hyp_len, hyp_cap), the rest -1; hyp_len[n * lanes + l] is the TRUE length (it
+ * may exceed hyp_cap: truncated); score / am_score [n * lanes + l] (am_score may be NULL; without a model it equals score). */
+int tfk_ctc_stream_result(tfk_ctc_stream* s, void* stream, int32_t top_paths, int flags, int32_t* hyp, int32_t hyp_cap,
+                          int32_t* hyp_len, float* score, float* am_score);
 
 /* ---- data parallelism (one engine per rank; the host owns the collective) --------------------- */
 

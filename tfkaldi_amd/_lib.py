@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_double, c_flo
 
 from .build import lib_path, source_id
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # enums of tfkaldi_hip.h
 NONLIN = {"relu": 0, "sigmoid": 1, "tanh": 2, "linear": 3}
@@ -220,6 +220,15 @@ SYMBOLS = {
     "tfk_ctc_wild_loss_logits": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_float, c_void_p, c_void_p, c_int64]),
     "tfk_label_edit_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "tfk_ctc_stream_bytes": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "tfk_ctc_stream_create": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "tfk_ctc_stream_destroy": (c_int, [c_void_p]),
+    "tfk_ctc_stream_reset": (c_int, [c_void_p, c_void_p, c_int32]),
+    "tfk_ctc_stream_frames": (c_int, [c_void_p, c_void_p]),
+    "tfk_ctc_stream_push_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32,
+                                           c_void_p, c_int32, c_int32, c_float, c_float]),
+    "tfk_ctc_stream_push": (c_int, [_E, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_float, c_float, c_int]),
+    "tfk_ctc_stream_result": (c_int, [c_void_p, c_void_p, c_int32, c_int, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "tfk_set_prior": (c_int, [_E, c_void_p, c_size_t]),
     "tfk_reduce_region": (c_int, [_E, POINTER(c_void_p), POINTER(c_size_t)]),
     "tfk_zero_accumulators": (c_int, [_E]),

@@ -124,6 +124,34 @@ void ctc_beam_topk_rows(hipStream_t s, const float* logits, int ld, int O, int T
 void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, int U, int W,
                           int top_paths, int label_topk, unsigned long long* trie, const uint32_t* pre, int32_t* hyp,
                           int32_t* hyp_len, float* score, const CtcLm* lm = nullptr, float* am_score = nullptr);
+// The RESUMABLE search (the contract is the comment at tfk_ctc_stream_create in tfkaldi_hip.h): `lanes` independent sessions, one
+// workgroup each, whose state outlives the launch.  Per lane: trie = ctc_beam_scratch_words(max_frames, 1, W) 64-bit words (its
+// capacity follows max_frames, not the chunk), hdr = kCtcStreamHdrWords 32-bit words, arr = kCtcStreamArrays arrays of W 32-bit
+// words (the layout: BeamResume in ctc.hip; the arithmetic of the whole allocation: ctc_stream_layout in ctc_tables.h).
+//   ctc_stream_reset   lane (-1: every lane) back to the empty table and the start of a search; stream-ordered memsets
+//   ctc_stream_push    the frame loop of ctc_beam_search (label_topk == 0) or ctc_beam_topk_search (pre: the rows of
+//                      ctc_beam_topk_rows for THIS chunk) over rows [seg[l], seg[l + 1]) of logits [T, ld] for lane l, from the
+//                      lane's saved state to its saved state; lm as above (eos is not read: the end terms of the surviving
+//                      prefixes are saved with the state, with lm->weight beside them).  A lane with no row still saves.
+//   ctc_stream_result  the N-best of every lane from its saved state, which it leaves as it is: hyp[(n * lanes + l) * stride + k],
+//                      k < hyp_len[n * lanes + l] only (stride >= every lane's frame count), score / am_score [n * lanes + l]
+//                      (am_score may be NULL).  kind: the model kind the lanes were pushed under; pruned: which search.
+// Any split of a lane's frames into pushes leaves the state, and so the result, of the one search over all of them, bit for
+// bit: the frame step reads nothing else of the past, and node ids, which differ with the table's capacity, order nothing.
+constexpr int kCtcStreamHdrWords = 8;
+constexpr int kCtcStreamArrays = 11;
+constexpr int kCtcModelNone = 0, kCtcModelNgram = 1, kCtcModelGraph = 2;
+struct CtcStreamState {
+  int32_t* hdr;
+  uint32_t* arr;
+  unsigned long long* trie;
+  int lanes, W, max_frames;
+};
+void ctc_stream_reset(hipStream_t s, const CtcStreamState& st, int lane);
+void ctc_stream_push(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, const CtcStreamState& st,
+                     int label_topk, const uint32_t* pre, const CtcLm* lm);
+void ctc_stream_result(hipStream_t s, const CtcStreamState& st, int kind, bool eos, bool pruned, int top_paths, int stride,
+                       int32_t* hyp, int32_t* hyp_len, float* score, float* am_score);
 // Forced alignment: the most probable path through the CTC lattice of every utterance's KNOWN label sequence (the contract
 // is the comment at tfk_ctc_align in tfkaldi_hip.h).  States as the loss: n = 2S + 1, blank, l_0, blank, ..., blank;
 // transitions as ctc_alpha_beta (stay, +1, +2 into a label that differs from the label two states back); start in state

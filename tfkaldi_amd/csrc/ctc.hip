@@ -570,7 +570,7 @@ struct BeamSideLm : BeamSide {
   int ctx[kCtcBeamMaxWidth];
 };
 // the model kind of a search: none (acoustic), the dense n-gram table, a deterministic graph over the labels
-constexpr int kBeamAm = 0, kBeamNgram = 1, kBeamGraph = 2;
+constexpr int kBeamAm = kCtcModelNone, kBeamNgram = kCtcModelNgram, kBeamGraph = kCtcModelGraph;
 template <int LM>
 struct BeamSideOf { typedef BeamSideLm type; };
 template <>
@@ -690,6 +690,75 @@ __device__ __forceinline__ uint32_t beam_radix_select(F keyf, int k0, int k1, in
 // next [S, O] and start; eos = the end term counts.  The launchers build it once from CtcLm (beam_model).
 struct BeamModel { const float* table; int C; float weight, bonus; int eos; const int32_t* next; int start; };
 
+// A resumable search (the contract: tfk_ctc_stream_* in tfkaldi_hip.h).  A stream's lane keeps, in device memory of its own,
+// what the frame step reads of the past: a header of kCtcStreamHdrWords words [live | nb | ndead | lm_weight | off (double) | 2
+// spare] and kCtcStreamArrays arrays of W words [pb | pnb | tot | node | parent | last | len | src | g | ctx | end], end = the
+// model's end term of the prefix's context, gathered when the state is saved so that reading a result needs no model.  live == 0:
+// the lane has been reset and starts from beam_start's values.  The RESUME instantiations of the two kernels load that state
+// in front of the unchanged frame loop and store it behind it; they neither rank nor trace back (ctc_stream_result_kernel does).
+struct BeamResume {
+  int32_t* hdr;    // [lanes, kCtcStreamHdrWords]
+  uint32_t* arr;   // [lanes, kCtcStreamArrays, W]
+  int max_frames;  // what the lane's share of the trie is sized by
+};
+template <int LM, class Side>
+__device__ __forceinline__ void beam_resume_load(Side& b, const BeamResume& rs, int u, int W, int* s_nb, int* s_ndead,
+                                                 double* off) {
+  const int tid = threadIdx.x;
+  const int32_t* hd = rs.hdr + (size_t)u * kCtcStreamHdrWords;
+  if (!hd[0]) return;  // (uniform over the block)
+  const uint32_t* a = rs.arr + (size_t)u * kCtcStreamArrays * (size_t)W;
+  const int nb = hd[1];
+  *off = *reinterpret_cast<const double*>(hd + 4);
+  if (tid < nb) {
+    b.pb[tid] = __builtin_bit_cast(float, a[tid]);
+    b.pnb[tid] = __builtin_bit_cast(float, a[W + tid]);
+    b.tot[tid] = __builtin_bit_cast(float, a[2 * W + tid]);
+    b.node[tid] = (int)a[3 * W + tid];
+    b.parent[tid] = (int)a[4 * W + tid];
+    b.last[tid] = (int)a[5 * W + tid];
+    b.len[tid] = (int)a[6 * W + tid];
+    b.src[tid] = (int)a[7 * W + tid];
+    if constexpr (LM) {
+      b.g[tid] = __builtin_bit_cast(float, a[8 * W + tid]);
+      b.ctx[tid] = (int)a[9 * W + tid];
+    }
+  }
+  if (tid == 0) {  // (the thread that wrote beam_start's values)
+    *s_nb = nb;
+    *s_ndead = hd[2];
+  }
+}
+template <int LM, class Side>
+__device__ __forceinline__ void beam_resume_store(const Side& b, const BeamResume& rs, int u, int W, int nb, int ndead,
+                                                  double off, const float* lm, int O, float lm_w) {
+  const int tid = threadIdx.x;
+  int32_t* hd = rs.hdr + (size_t)u * kCtcStreamHdrWords;
+  uint32_t* a = rs.arr + (size_t)u * kCtcStreamArrays * (size_t)W;
+  if (tid < nb) {
+    a[tid] = __builtin_bit_cast(uint32_t, b.pb[tid]);
+    a[W + tid] = __builtin_bit_cast(uint32_t, b.pnb[tid]);
+    a[2 * W + tid] = __builtin_bit_cast(uint32_t, b.tot[tid]);
+    a[3 * W + tid] = (uint32_t)b.node[tid];
+    a[4 * W + tid] = (uint32_t)b.parent[tid];
+    a[5 * W + tid] = (uint32_t)b.last[tid];
+    a[6 * W + tid] = (uint32_t)b.len[tid];
+    a[7 * W + tid] = (uint32_t)b.src[tid];
+    if constexpr (LM) {
+      a[8 * W + tid] = __builtin_bit_cast(uint32_t, b.g[tid]);
+      a[9 * W + tid] = (uint32_t)b.ctx[tid];
+      a[10 * W + tid] = __builtin_bit_cast(uint32_t, lm[(size_t)b.ctx[tid] * (size_t)O + (size_t)(O - 1)]);
+    }
+  }
+  if (tid == 0) {
+    hd[0] = 1;
+    hd[1] = nb;
+    hd[2] = ndead;
+    hd[3] = (int32_t)__builtin_bit_cast(uint32_t, lm_w);
+    *reinterpret_cast<double*>(hd + 4) = off;
+  }
+}
+
 // The start of both searches: the beam is {(): (0, -inf)}, the block's LDS state cleared.  The caller's barrier follows.
 // (It is the one part of the two kernels that is written once.  Shared bodies for phases B to E and for the epilogue were
 // built and measured -- profiles/ctc_beam_refactor_ab.txt: every output stayed the parent's bit for bit, but each of them,
@@ -730,12 +799,15 @@ __device__ __forceinline__ void beam_start(Side& b, int C, int gstart, uint32_t*
 // needs (sel is written again only behind the first barrier inside beam_radix_select), so that phase C's guard and the
 // select's precondition see the true live count.  A merging extension is never a missing one (its child is in the beam, so
 // the arc existed), hence live = N - ndead - missing.  next is read for survivors only, in D beside the weight's reload.
-template <int LM>
+// RESUME: seg bounds the lanes' chunks, the trie is the stream's (a lane's share is sized by rs.max_frames, not by the chunk),
+// and hyp / hyp_len / score / am_score / top_paths / eos are not read.
+template <int LM, bool RESUME = false>
 __global__ void __launch_bounds__(kBeamThreads)
 ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* __restrict__ seg, int U, int T, int W,
                 int top_paths, unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp,
                 int32_t* __restrict__ hyp_len, float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w,
-                float lm_bonus, int eos, float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart) {
+                float lm_bonus, int eos, float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart,
+                BeamResume rs) {
   typedef typename BeamSideOf<LM>::type Side;
   __shared__ Side beam[2];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
@@ -751,13 +823,16 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
   const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = seg[u], Tn = seg[u + 1] - r0;
   const int blank = O - 1;
-  const uint32_t cap = 2u * (uint32_t)Tn * (uint32_t)W + 64u;  // this utterance's share of the table: load <= 1/2
-  unsigned long long* tab = trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
+  // this utterance's share of the table: load <= 1/2
+  const uint32_t cap = 2u * (uint32_t)(RESUME ? rs.max_frames : Tn) * (uint32_t)W + 64u;
+  unsigned long long* tab = RESUME ? trie + (unsigned long long)u * (unsigned long long)cap
+                                   : trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
   const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)O - 1u) / (unsigned)O);  // k / O for k < 2^13
 
   beam_start<LM>(beam[0], C, gstart, hist, childmask, path, &s_nb, &s_ndead);
   int cur = 0;
   double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
+  if constexpr (RESUME) beam_resume_load<LM>(beam[0], rs, u, W, &s_nb, &s_ndead, &off);
   float z_next = (wave == 0 && lane < O && Tn > 0) ? logits[(size_t)r0 * ld + lane] : 0.f;
   __syncthreads();
 
@@ -931,6 +1006,10 @@ ctc_beam_kernel(const float* __restrict__ logits, int ld, int O, const int32_t* 
     __syncthreads();
   }
 
+  if constexpr (RESUME) {
+    beam_resume_store<LM>(beam[cur], rs, u, W, s_nb, s_ndead, off, lm, O, lm_w);
+    return;
+  }
   // the top_paths best of the final beam: higher total (LM: + g, + the end term under TFK_CTC_LM_EOS), then shorter, then
   // lower slot
   const Side& b = beam[cur];
@@ -1097,13 +1176,14 @@ __device__ __forceinline__ void beam_topk_extend(const BeamSide& b, int i, int c
 //   B-D  candidate k = i * (K + 1) + q: q < K extends by flab[q], q == K stays; a stay collects its parent's extension only if
 //      lpos >= 0.  With K == O - 1 flab is 0 .. O - 2 and k, the keys, the tie-breaks and every value are ctc_beam_kernel's
 //   the trie key holds a 16-bit label
-template <int LM>
+//   RESUME: as ctc_beam_kernel's; the look-ahead registers are primed from the chunk's own pre-pass rows
+template <int LM, bool RESUME = false>
 __global__ void __launch_bounds__(kBeamThreads)
 ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, const uint32_t* __restrict__ pre,
                      const int32_t* __restrict__ seg, int U, int T, int W, int top_paths,
                      unsigned long long* __restrict__ trie, int32_t* __restrict__ hyp, int32_t* __restrict__ hyp_len,
                      float* __restrict__ score, const float* __restrict__ lm, int C, float lm_w, float lm_bonus, int eos,
-                     float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart) {
+                     float* __restrict__ am_score, const int32_t* __restrict__ gnext, int gstart, BeamResume rs) {
   typedef typename BeamSideOf<LM>::type Side;
   __shared__ Side beam[2];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kBeamKeys];
@@ -1123,14 +1203,17 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
   const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = seg[u], Tn = seg[u + 1] - r0;
   const int blank = O - 1, K1 = K + 1;
-  const uint32_t cap = 2u * (uint32_t)Tn * (uint32_t)W + 64u;  // this utterance's share of the table: load <= 1/2
-  unsigned long long* tab = trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
+  // this utterance's share of the table: load <= 1/2
+  const uint32_t cap = 2u * (uint32_t)(RESUME ? rs.max_frames : Tn) * (uint32_t)W + 64u;
+  unsigned long long* tab = RESUME ? trie + (unsigned long long)u * (unsigned long long)cap
+                                   : trie + (2ull * (unsigned long long)r0 * (unsigned long long)W + 64ull * (unsigned long long)u);
   const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)K1 - 1u) / (unsigned)K1);  // k / K1 for k < 2^13
   const uint32_t* prow = pre + (size_t)r0 * kCtcTopkRowWords;
 
   beam_start<LM>(beam[0], C, gstart, hist, childmask, path, &s_nb, &s_ndead);
   int cur = 0;
   double off = 0.0;  // what has been taken out of the beam's scores so far (uniform over the block)
+  if constexpr (RESUME) beam_resume_load<LM>(beam[0], rs, u, W, &s_nb, &s_ndead, &off);
   // wave 0: the next frame's list, in registers until phase E; every thread: the next frame's lsum
   uint32_t lab_next = 0x7fffffffu, val_next = 0u, lpb_next = 0u;
   float lsum_next = 0.f;
@@ -1349,6 +1432,10 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
     __syncthreads();
   }
 
+  if constexpr (RESUME) {
+    beam_resume_store<LM>(beam[cur], rs, u, W, s_nb, s_ndead, off, lm, O, lm_w);
+    return;
+  }
   // the top_paths best of the final beam, as ctc_beam_kernel
   const Side& b = beam[cur];
   const int nb = s_nb;
@@ -1400,6 +1487,79 @@ ctc_beam_topk_kernel(const float* __restrict__ logits, int ld, int O, int K, con
       const unsigned long long nk = __hip_atomic_load(&tab[node], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       out[pos] = (int32_t)(nk & 0xffffull);
       node = (uint32_t)(nk >> 16);
+    }
+  }
+}
+
+// The N-best of a stream's lanes from their saved state (BeamResume's layout) and tries: what the epilogue of the two kernels
+// above produces, written beside them on purpose (the comment at beam_start says what sharing a body with them costs).  ONE
+// WORKGROUP PER LANE; it reads no model -- the end terms were saved -- and writes neither the state nor the trie.  kind: the
+// model the lane's state was saved under (kBeamAm: the value is tot; else tot + g, and with eos the end term on top, -inf for a
+// graph state that is not final); lbits: the width of a trie key's label field (6: ctc_beam_kernel, 16: ctc_beam_topk_kernel).
+// A lane that has not been pushed since its reset (live == 0) is the empty prefix with both scores 0.
+// Out: hyp[(n * U + u) * stride + k] for k < hyp_len[n * U + u] (nothing beyond: the host pads), score / am_score [n * U + u].
+__global__ void __launch_bounds__(kBeamThreads)
+ctc_stream_result_kernel(const int32_t* __restrict__ hdr, const uint32_t* __restrict__ arr,
+                         const unsigned long long* __restrict__ trie, int U, int W, int max_frames, int kind, int eos,
+                         int lbits, int top_paths, int stride, int32_t* __restrict__ hyp, int32_t* __restrict__ hyp_len,
+                         float* __restrict__ score, float* __restrict__ am_score) {
+  __shared__ float val[kCtcBeamMaxWidth], tot[kCtcBeamMaxWidth];
+  __shared__ int len[kCtcBeamMaxWidth], path[kCtcBeamMaxWidth];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int32_t* hd = hdr + (size_t)u * kCtcStreamHdrWords;
+  const uint32_t* a = arr + (size_t)u * kCtcStreamArrays * (size_t)W;
+  const uint32_t cap = 2u * (uint32_t)max_frames * (uint32_t)W + 64u;
+  const unsigned long long* tab = trie + (unsigned long long)u * (unsigned long long)cap;
+  const bool live = hd[0] != 0;
+  const int nb = live ? hd[1] : 1;
+  const double off = live ? *reinterpret_cast<const double*>(hd + 4) : 0.0;
+  const float lm_w = __builtin_bit_cast(float, (uint32_t)hd[3]);
+  if (tid < kCtcBeamMaxWidth) path[tid] = -1;
+  if (tid < nb) {
+    const float t = live ? __builtin_bit_cast(float, a[2 * W + tid]) : 0.f;
+    float v = t;
+    if (kind != kBeamAm) {
+      v = t + (live ? __builtin_bit_cast(float, a[8 * W + tid]) : 0.f);
+      if (eos) {
+        const float fw = __builtin_bit_cast(float, a[10 * W + tid]);
+        if (kind == kBeamGraph && !(fw > -INFINITY)) v = -INFINITY;  // not final, whatever lm_weight is
+        else v = beam_lm_end(v, lm_w, fw);
+      }
+    }
+    tot[tid] = t;
+    val[tid] = v;
+    len[tid] = live ? (int)a[6 * W + tid] : 0;
+  }
+  __syncthreads();
+  if (tid < nb) {  // higher value, then shorter, then lower slot
+    const uint32_t kj = sortable(val[tid]);
+    const int lj = len[tid];
+    int rank = 0;
+    for (int i = 0; i < nb; ++i) {
+      const uint32_t ki = sortable(val[i]);
+      const int li = len[i];
+      rank += ki > kj || (ki == kj && (li < lj || (li == lj && i < tid)));
+    }
+    path[rank] = tid;
+  }
+  __syncthreads();
+  if (tid < top_paths) {
+    const int j = path[tid];
+    const size_t at = (size_t)tid * U + u;
+    const int L = j >= 0 ? min(len[j], stride) : 0;
+    hyp_len[at] = L;
+    const bool alive = j >= 0 && tot[j] > -1e29f;
+    score[at] = alive ? (float)(off + (double)val[j]) : -INFINITY;
+    if (am_score) am_score[at] = alive ? (float)(off + (double)tot[j]) : -INFINITY;
+    if (j >= 0 && live) {  // back-trace through the parent links, labels land in forward order
+      int32_t* out = hyp + at * (size_t)stride;
+      uint32_t node = a[3 * W + j];
+      const unsigned long long mask = (1ull << lbits) - 1ull;
+      for (int pos = L - 1; pos >= 0 && node < cap; --pos) {
+        const unsigned long long nk = __hip_atomic_load(&tab[node], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        out[pos] = (int32_t)(nk & mask);
+        node = (uint32_t)(nk >> lbits);
+      }
     }
   }
 }
@@ -2558,7 +2718,7 @@ void ctc_beam_search(hipStream_t s, const float* logits, int ld, int O, int T, c
   hipLaunchKernelGGL(kind == kBeamGraph ? ctc_beam_kernel<kBeamGraph>
                      : kind == kBeamNgram ? ctc_beam_kernel<kBeamNgram> : ctc_beam_kernel<kBeamAm>,
                      dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, seg, U, T, W, top_paths, trie, hyp, hyp_len, score,
-                     m.table, m.C, m.weight, m.bonus, m.eos, lm ? am_score : nullptr, m.next, m.start);
+                     m.table, m.C, m.weight, m.bonus, m.eos, lm ? am_score : nullptr, m.next, m.start, BeamResume{});
 }
 
 size_t ctc_beam_topk_scratch_words(int T) { return (size_t)(T > 0 ? T : 0) * kCtcTopkRowWords; }
@@ -2595,7 +2755,42 @@ void ctc_beam_topk_search(hipStream_t s, const float* logits, int ld, int O, int
   hipLaunchKernelGGL(kind == kBeamGraph ? ctc_beam_topk_kernel<kBeamGraph>
                      : kind == kBeamNgram ? ctc_beam_topk_kernel<kBeamNgram> : ctc_beam_topk_kernel<kBeamAm>,
                      dim3(U), dim3(kBeamThreads), 0, s, logits, ld, O, K, pre, seg, U, T, W, top_paths, trie, hyp, hyp_len,
-                     score, m.table, m.C, m.weight, m.bonus, m.eos, am_score, m.next, m.start);
+                     score, m.table, m.C, m.weight, m.bonus, m.eos, am_score, m.next, m.start, BeamResume{});
+}
+
+static size_t stream_lane_words(const CtcStreamState& st) { return ctc_beam_scratch_words(st.max_frames, 1, st.W); }
+
+void ctc_stream_reset(hipStream_t s, const CtcStreamState& st, int lane) {
+  const size_t first = lane < 0 ? 0 : (size_t)lane, n = lane < 0 ? (size_t)st.lanes : 1;
+  (void)hipMemsetAsync(st.trie + first * stream_lane_words(st), 0xff, n * stream_lane_words(st) * sizeof(unsigned long long), s);
+  (void)hipMemsetAsync(st.hdr + first * kCtcStreamHdrWords, 0, n * kCtcStreamHdrWords * sizeof(int32_t), s);
+}
+
+void ctc_stream_push(hipStream_t s, const float* logits, int ld, int O, int T, const int32_t* seg, const CtcStreamState& st,
+                     int label_topk, const uint32_t* pre, const CtcLm* lm) {
+  const int kind = beam_kind(lm);
+  const BeamModel m = beam_model(lm, O);
+  const BeamResume rs = {st.hdr, st.arr, st.max_frames};
+  if (label_topk) {
+    auto* const kernel = kind == kBeamGraph   ? (ctc_beam_topk_kernel<kBeamGraph, true>)
+                         : kind == kBeamNgram ? (ctc_beam_topk_kernel<kBeamNgram, true>)
+                                              : (ctc_beam_topk_kernel<kBeamAm, true>);
+    hipLaunchKernelGGL(kernel, dim3(st.lanes), dim3(kBeamThreads), 0, s, logits, ld, O, min(label_topk, O - 1), pre, seg, st.lanes, T,
+                       st.W, 0, st.trie, nullptr, nullptr, nullptr, m.table, m.C, m.weight, m.bonus, 0, nullptr, m.next,
+                       m.start, rs);
+  } else {
+    auto* const kernel = kind == kBeamGraph   ? (ctc_beam_kernel<kBeamGraph, true>)
+                         : kind == kBeamNgram ? (ctc_beam_kernel<kBeamNgram, true>)
+                                              : (ctc_beam_kernel<kBeamAm, true>);
+    hipLaunchKernelGGL(kernel, dim3(st.lanes), dim3(kBeamThreads), 0, s, logits, ld, O, seg, st.lanes, T, st.W, 0, st.trie, nullptr,
+                       nullptr, nullptr, m.table, m.C, m.weight, m.bonus, 0, nullptr, m.next, m.start, rs);
+  }
+}
+
+void ctc_stream_result(hipStream_t s, const CtcStreamState& st, int kind, bool eos, bool pruned, int top_paths, int stride,
+                       int32_t* hyp, int32_t* hyp_len, float* score, float* am_score) {
+  hipLaunchKernelGGL(ctc_stream_result_kernel, dim3(st.lanes), dim3(kBeamThreads), 0, s, st.hdr, st.arr, st.trie, st.lanes, st.W,
+                     st.max_frames, kind, eos ? 1 : 0, pruned ? 16 : 6, top_paths, stride, hyp, hyp_len, score, am_score);
 }
 
 // scratch of ctc_viterbi_align: [back-pointer rows T x bp_row_bytes(R) | row log-sum-exps T floats]

@@ -6,10 +6,12 @@
 //   carve_batch    a CtcBatch out of one allocation (the arithmetic: ctc_batch_layout in ctc_tables.h)
 #include "../../include/tfkaldi_hip.h"
 #include "ctc.h"
+#include "ctc_stream.h"
 #include "ctc_tables.h"
 #include "tfk_error.h"
 
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -122,9 +124,221 @@ int ctc_beam_logits_impl(void* stream, const float* logits, int64_t ld, int32_t 
   return sc.done();
 }
 
+constexpr CtcStreamCaps kStreamCaps = {kCtcBeamMaxWidth, kCtcBeamMaxClasses, kCtcBeamMaxFrames, kCtcTopkMaxClasses,
+                                       kCtcTopkMaxLabels,  kCtcStreamMaxLanes};
+
+const char* model_name(int kind) {
+  return kind == kCtcModelNone ? "no model" : kind == kCtcModelNgram ? "an n-gram table" : kind == kCtcModelGraph ? "a graph" : "nothing";
+}
+bool same_bits(float a, float b) { return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b); }
+bool same_model(const CtcStreamModel& a, const CtcStreamModel& b) {
+  if (a.kind != b.kind || a.owner != b.owner) return false;
+  if (a.kind == kCtcModelNone) return true;
+  if (a.owner ? a.generation != b.generation : (a.table != b.table || a.next != b.next)) return false;
+  return a.order == b.order && a.num_states == b.num_states && a.start == b.start && same_bits(a.weight, b.weight) &&
+         same_bits(a.bonus, b.bonus);
+}
+
+}  // namespace
+
+namespace tfk {
+
+int ctc_stream_push_checks(const tfk_ctc_stream* s, const char* who, int O, int T, const int32_t* chunk_len,
+                           const CtcStreamModel& m) {
+  if (O != s->O) return fail(-1, "%s: output_dim %d differs from the stream's O = %d", who, O, s->O);
+  CHK(ctc_stream_push_check(who, chunk_len, s->frames.data(), s->lanes, T, s->max_frames));
+  for (int l = 0; l < s->lanes; ++l)
+    if (s->frames[l] > 0 && !same_model(s->bound[l], m))
+      return fail(-1, "%s: lane %d holds %d frames decoded with %s; a push with %s (or other tables, weights or bonus) cannot continue it "
+                  "(tfk_ctc_stream_reset first)", who, l, s->frames[l], model_name(s->bound[l].kind), model_name(m.kind));
+  return 0;
+}
+
+int ctc_stream_push_launch(tfk_ctc_stream* s, hipStream_t st, const float* logits, int64_t ld, int T, const int32_t* chunk_len,
+                           const CtcStreamModel& m, const CtcStreamPhase& phase) {
+  const CtcStreamState state = s->state();
+  int32_t* d_seg = reinterpret_cast<int32_t*>(s->dev + s->L.seg);
+  if (s->seg_pending) HIPCHK(hipEventSynchronize(s->seg_copied));  // (the copy of the push before; not its search)
+  s->h_seg[0] = 0;
+  for (int l = 0; l < s->lanes; ++l) s->h_seg[l + 1] = s->h_seg[l] + chunk_len[l];
+  HIPCHK(hipMemcpyAsync(d_seg, s->h_seg, ((size_t)s->lanes + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(s->seg_copied, st));
+  s->seg_pending = true;
+  // a lane without frames that was bound to another model holds that model's start: it starts again (its table is empty)
+  for (int l = 0; l < s->lanes; ++l)
+    if (s->bound[l].kind >= 0 && !same_model(s->bound[l], m))
+      HIPCHK(hipMemsetAsync(state.hdr + (size_t)l * kCtcStreamHdrWords, 0, kCtcStreamHdrWords * sizeof(int32_t), st));
+  const CtcLm lm = {m.table, m.order, m.weight, m.bonus, false, m.next, m.num_states, m.start};
+  Scratch sc(st);
+  uint32_t* pre = nullptr;
+  if (s->label_topk) {
+    CHK(sc.get(&pre, ctc_beam_topk_scratch_words(T) * sizeof(uint32_t)));
+    if (phase) phase(1);
+    ctc_beam_topk_rows(st, logits, (int)ld, s->O, T, s->label_topk, pre);
+  }
+  if (phase) phase(2);
+  ctc_stream_push(st, logits, (int)ld, s->O, T, d_seg, state, s->label_topk, pre, m.kind == kCtcModelNone ? nullptr : &lm);
+  if (phase) phase(0);
+  CHK(sc.done());
+  for (int l = 0; l < s->lanes; ++l) {
+    s->frames[l] += chunk_len[l];
+    s->bound[l] = m;
+  }
+  return 0;
+}
+
+}  // namespace tfk
+
+namespace {
+
+int stream_push_logits(tfk_ctc_stream* s, void* stream, const float* logits, int64_t ld, int32_t T, const int32_t* chunk_len,
+                       const float* lm_dev, int32_t order, const int32_t* next_dev, int32_t num_states, int32_t start,
+                       float lm_weight, float label_bonus) {
+  const char* who = "tfk_ctc_stream_push_logits";
+  if (!s) return fail(-1, "%s: the stream is NULL", who);
+  if (T > 0 && !logits) return fail(-1, "%s: logits is NULL", who);
+  if (T > 0 && (ld < s->O || ld > 0x7fffffff)) return fail(-1, "%s: ld = %lld outside [O = %d, 2^31)", who, (long long)ld, s->O);
+  CtcStreamModel m;
+  m.kind = !lm_dev ? kCtcModelNone : next_dev ? kCtcModelGraph : kCtcModelNgram;
+  if (next_dev && !lm_dev) return fail(-1, "%s: next without weight", who);
+  if (m.kind == kCtcModelNgram) {
+    if (order < 1 || order > kCtcLmMaxOrder) return fail(-1, "%s: order %d outside [1, %d]", who, order, kCtcLmMaxOrder);
+    if (ctc_lm_entries(s->O, order) > kCtcLmMaxEntries)
+      return fail(-1, "%s: a table of order %d over %d outputs has more than %zu entries", who, order, s->O, kCtcLmMaxEntries);
+    m.order = order;
+  } else if (m.kind == kCtcModelGraph) {
+    if (num_states < 1 || start < 0 || start >= num_states)
+      return fail(-1, "%s: start %d outside [0, num_states = %d)", who, start, num_states);
+    if ((size_t)num_states * (size_t)s->O > kCtcGraphMaxEntries)
+      return fail(-1, "%s: a graph of %d states over %d outputs has more than %zu entries per table", who, num_states, s->O,
+                  kCtcGraphMaxEntries);
+    m.num_states = num_states;
+    m.start = start;
+  }
+  if (m.kind != kCtcModelNone) {
+    m.table = lm_dev;
+    m.next = next_dev;
+    m.weight = lm_weight;
+    m.bonus = label_bonus;
+  }
+  CHK(ctc_stream_push_checks(s, who, s->O, T, chunk_len, m));
+  HIPCHK(hipSetDevice(s->device));
+  return ctc_stream_push_launch(s, (hipStream_t)stream, logits, ld, T, chunk_len, m, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
+
+int tfk_ctc_stream_bytes(int32_t O, int32_t lanes, int32_t beam_width, int32_t max_frames, int32_t label_topk, size_t* bytes) {
+  if (!bytes) return fail(-1, "tfk_ctc_stream_bytes: bytes is NULL");
+  CHK(ctc_stream_limits("tfk_ctc_stream_bytes", kStreamCaps, O, lanes, beam_width, max_frames, label_topk));
+  *bytes = ctc_stream_layout(lanes, beam_width, max_frames, kCtcStreamHdrWords, kCtcStreamArrays).bytes;
+  return 0;
+}
+int tfk_ctc_stream_create(int32_t O, int32_t lanes, int32_t beam_width, int32_t max_frames, int32_t label_topk,
+                          tfk_ctc_stream** out) {
+  if (!out) return fail(-1, "tfk_ctc_stream_create: out is NULL");
+  *out = nullptr;
+  CHK(ctc_stream_limits("tfk_ctc_stream_create", kStreamCaps, O, lanes, beam_width, max_frames, label_topk));
+  tfk_ctc_stream* s = new tfk_ctc_stream;
+  s->O = O; s->lanes = lanes; s->W = beam_width; s->max_frames = max_frames; s->label_topk = label_topk;
+  s->L = ctc_stream_layout(lanes, beam_width, max_frames, kCtcStreamHdrWords, kCtcStreamArrays);
+  s->frames.assign(lanes, 0);
+  s->bound.assign(lanes, CtcStreamModel());
+  hipError_t got = hipGetDevice(&s->device);
+  if (got == hipSuccess) got = hipMalloc((void**)&s->dev, s->L.bytes);
+  if (got == hipSuccess) got = hipHostMalloc((void**)&s->h_seg, ((size_t)lanes + 1) * sizeof(int32_t), hipHostMallocDefault);
+  if (got == hipSuccess) got = hipEventCreateWithFlags(&s->seg_copied, hipEventDisableTiming);
+  // every lane empty and at the start of a search, before the first call can be enqueued on any stream
+  if (got == hipSuccess) got = hipMemset(s->dev + s->L.trie, 0xff, s->L.hdr - s->L.trie);
+  if (got == hipSuccess) got = hipMemset(s->dev + s->L.hdr, 0, s->L.bytes - s->L.hdr);
+  if (got == hipSuccess) got = hipDeviceSynchronize();
+  if (got != hipSuccess) {
+    const size_t bytes = s->L.bytes;
+    (void)tfk_ctc_stream_destroy(s);
+    return fail((int)got, "tfk_ctc_stream_create (%zu bytes): %s", bytes, hipGetErrorString(got));
+  }
+  *out = s;
+  return 0;
+}
+int tfk_ctc_stream_destroy(tfk_ctc_stream* s) {
+  if (!s) return 0;
+  hipError_t first = hipSuccess;
+  if (s->seg_pending) first = hipEventSynchronize(s->seg_copied);
+  for (hipError_t got : {s->dev ? hipFree(s->dev) : hipSuccess, s->h_seg ? hipHostFree(s->h_seg) : hipSuccess,
+                         s->seg_copied ? hipEventDestroy(s->seg_copied) : hipSuccess})
+    if (first == hipSuccess) first = got;
+  delete s;
+  HIPCHK(first);
+  return 0;
+}
+int tfk_ctc_stream_reset(tfk_ctc_stream* s, void* stream, int32_t lane) {
+  if (!s) return fail(-1, "tfk_ctc_stream_reset: the stream is NULL");
+  if (lane < -1 || lane >= s->lanes) return fail(-1, "tfk_ctc_stream_reset: lane %d outside [-1, %d)", lane, s->lanes);
+  HIPCHK(hipSetDevice(s->device));
+  ctc_stream_reset((hipStream_t)stream, s->state(), lane);
+  HIPCHK(hipGetLastError());
+  for (int l = lane < 0 ? 0 : lane; l < (lane < 0 ? s->lanes : lane + 1); ++l) {
+    s->frames[l] = 0;
+    s->bound[l] = CtcStreamModel();
+  }
+  return 0;
+}
+int tfk_ctc_stream_frames(tfk_ctc_stream* s, int32_t* frames) {
+  if (!s || !frames) return fail(-1, "tfk_ctc_stream_frames: the stream / frames is NULL");
+  std::copy(s->frames.begin(), s->frames.end(), frames);
+  return 0;
+}
+int tfk_ctc_stream_push_logits(tfk_ctc_stream* s, void* stream, const float* logits, int64_t ld, int32_t T,
+                               const int32_t* chunk_len, const float* lm_dev, int32_t order, const int32_t* next_dev,
+                               int32_t num_states, int32_t start, float lm_weight, float label_bonus) {
+  return stream_push_logits(s, stream, logits, ld, T, chunk_len, lm_dev, order, next_dev, num_states, start, lm_weight,
+                            label_bonus);
+}
+int tfk_ctc_stream_result(tfk_ctc_stream* s, void* stream, int32_t top_paths, int flags, int32_t* hyp, int32_t hyp_cap,
+                          int32_t* hyp_len, float* score, float* am_score) {
+  const char* who = "tfk_ctc_stream_result";
+  hipStream_t st = (hipStream_t)stream;
+  if (!s) return fail(-1, "%s: the stream is NULL", who);
+  if (flags & ~TFK_CTC_LM_EOS) return fail(-1, "%s: flags %d, it takes 0 or TFK_CTC_LM_EOS", who, flags);
+  CHK(ctc_stream_result_check(who, s->W, top_paths, hyp_cap));
+  if (!hyp_len || !score || (hyp_cap > 0 && !hyp)) return fail(-1, "%s: hyp / hyp_len / score is NULL", who);
+  int kind = kCtcModelNone;
+  for (int l = 0; l < s->lanes; ++l) {
+    if (s->bound[l].kind > kCtcModelNone) kind = s->bound[l].kind;
+    if ((flags & TFK_CTC_LM_EOS) && s->bound[l].kind <= kCtcModelNone)
+      return fail(-1, "%s: TFK_CTC_LM_EOS, and lane %d is %s (the end term is the model's)", who, l,
+                  s->bound[l].kind < 0 ? "not bound to a model" : "bound without a model");
+  }
+  HIPCHK(hipSetDevice(s->device));
+  const size_t P = (size_t)top_paths, U = (size_t)s->lanes;
+  const int stride = *std::max_element(s->frames.begin(), s->frames.end());
+  // [hypotheses P U stride | lengths P U | scores P U | acoustic scores P U]
+  const size_t words = P * U * (size_t)stride + 3 * P * U;
+  Scratch sc(st);
+  int32_t* d_hyp = nullptr;
+  CHK(sc.get(&d_hyp, words * sizeof(int32_t)));
+  int32_t* d_len = d_hyp + P * U * (size_t)stride;
+  float* d_score = reinterpret_cast<float*>(d_len + P * U);
+  ctc_stream_result(st, s->state(), kind, (flags & TFK_CTC_LM_EOS) != 0, s->label_topk != 0, top_paths, stride, d_hyp, d_len,
+                    d_score, d_score + P * U);
+  std::vector<int32_t> h(words);
+  hipError_t copied = hipGetLastError();
+  if (copied == hipSuccess) copied = hipMemcpyAsync(h.data(), d_hyp, words * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+  if (copied == hipSuccess) copied = hipStreamSynchronize(st);
+  CHK(sc.done(copied));
+  const int32_t* h_len = h.data() + P * U * (size_t)stride;
+  for (size_t p = 0; p < P * U; ++p) {
+    const int32_t n = std::min(h_len[p], hyp_cap);
+    if (n > 0) memcpy(hyp + p * (size_t)hyp_cap, h.data() + p * (size_t)stride, (size_t)n * sizeof(int32_t));
+    for (int32_t j = n > 0 ? n : 0; j < hyp_cap; ++j) hyp[p * (size_t)hyp_cap + j] = -1;
+  }
+  memcpy(hyp_len, h_len, P * U * sizeof(int32_t));
+  memcpy(score, h_len + P * U, P * U * sizeof(float));
+  if (am_score) memcpy(am_score, h_len + 2 * P * U, P * U * sizeof(float));
+  return 0;
+}
 
 int tfk_ctc_beam_topk_logits(void* stream, const float* logits, int64_t ld, int32_t O, int32_t T, const int32_t* seg, int32_t U,
                              int32_t beam_width, int32_t top_paths, int32_t label_topk, const float* lm_dev, int32_t order,

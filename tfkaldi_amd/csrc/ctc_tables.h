@@ -218,4 +218,73 @@ inline CtcBatchLayout ctc_batch_layout(int T, int U, int64_t ld, int sext, size_
   return L;
 }
 
+// ---- a CTC decode stream (tfk_ctc_stream_*) ----
+
+// The numbers of the search that the checks below need (ctc.h's constants, handed in so that this file stays free of HIP).
+struct CtcStreamCaps {
+  int max_width, max_classes, max_frames, topk_max_classes, topk_max_labels, max_lanes;
+};
+constexpr int kCtcStreamMaxLanes = 1024;
+
+// The shape of a stream (`who` opens the messages): NULL-free arithmetic only, nothing is allocated.
+inline int ctc_stream_limits(const char* who, const CtcStreamCaps& c, int O, int lanes, int W, int max_frames, int label_topk) {
+  if (lanes < 1 || lanes > c.max_lanes) return fail(-1, "%s: lanes %d outside [1, %d]", who, lanes, c.max_lanes);
+  if (W < 1 || W > c.max_width) return fail(-1, "%s: beam_width %d outside [1, %d]", who, W, c.max_width);
+  if (max_frames < 1 || max_frames > c.max_frames)
+    return fail(-1, "%s: max_frames %d outside [1, %d]", who, max_frames, c.max_frames);
+  if (label_topk < 0 || label_topk > c.topk_max_labels)
+    return fail(-1, "%s: label_topk %d outside [0, %d]", who, label_topk, c.topk_max_labels);
+  const int most = label_topk ? c.topk_max_classes : c.max_classes;
+  if (O < 2 || O > most)
+    return fail(-1, "%s: output_dim %d outside [2, %d]%s", who, O, most, label_topk ? "" : " (63 labels + blank, more with label_topk)");
+  return 0;
+}
+
+// One push of T rows cut into chunk_len[lanes]: no NULL, no negative length, the lengths sum to T, no lane passes max_frames
+// (frames[lanes]: what each lane holds).
+inline int ctc_stream_push_check(const char* who, const int32_t* chunk_len, const int32_t* frames, int lanes, int T,
+                                 int max_frames) {
+  if (!chunk_len) return fail(-1, "%s: chunk_len is NULL", who);
+  if (T < 0) return fail(-1, "%s: T = %d < 0", who, T);
+  int64_t rows = 0;
+  for (int l = 0; l < lanes; ++l) {
+    if (chunk_len[l] < 0) return fail(-1, "%s: lane %d has a negative chunk length", who, l);
+    rows += chunk_len[l];
+  }
+  if (rows != T) return fail(-1, "%s: the chunk lengths sum to %lld, expected T = %d", who, (long long)rows, T);
+  for (int l = 0; l < lanes; ++l)
+    if ((int64_t)frames[l] + chunk_len[l] > max_frames)
+      return fail(-1, "%s: lane %d would hold %lld frames (max_frames %d)", who, l, (long long)frames[l] + chunk_len[l],
+                  max_frames);
+  return 0;
+}
+
+// What a result may be asked for.
+inline int ctc_stream_result_check(const char* who, int W, int top_paths, int hyp_cap) {
+  if (top_paths < 1 || top_paths > W) return fail(-1, "%s: top_paths %d outside [1, beam_width = %d]", who, top_paths, W);
+  if (hyp_cap < 0) return fail(-1, "%s: hyp_cap %d < 0", who, hyp_cap);
+  return 0;
+}
+
+// Byte offsets of the regions of a stream's one allocation:
+//   [trie lanes x (2 max_frames W + 64) 64-bit words | hdr lanes x hdr_words | arr lanes x arrays x W | seg lanes + 1], 32-bit
+// words behind the 64-bit ones, and hdr_words even (a lane's header holds a double at word 4), so that every region is aligned
+// to its element.  `bytes` is where seg ends.
+struct CtcStreamLayout {
+  size_t trie, hdr, arr, seg, bytes;
+  size_t lane_trie_words;
+};
+inline CtcStreamLayout ctc_stream_layout(int lanes, int W, int max_frames, int hdr_words, int arrays) {
+  const size_t n = (size_t)lanes, w = (size_t)W;
+  CtcStreamLayout L;
+  L.lane_trie_words = 2 * (size_t)max_frames * w + 64;
+  size_t at = 0;
+  L.trie = at;  at += n * L.lane_trie_words * sizeof(uint64_t);
+  L.hdr = at;   at += n * (size_t)hdr_words * sizeof(int32_t);
+  L.arr = at;   at += n * (size_t)arrays * w * sizeof(uint32_t);
+  L.seg = at;   at += (n + 1) * sizeof(int32_t);
+  L.bytes = at;
+  return L;
+}
+
 }  // namespace tfk

@@ -11,6 +11,7 @@
 //     logits, two ping-pong gradient buffers, BN batch statistics, reduction workspace.
 #include "../../include/tfkaldi_hip.h"
 #include "ctc.h"
+#include "ctc_stream.h"
 #include "ctc_tables.h"
 #include "gemm_bf16.h"
 #include "gemm_f32.h"
@@ -27,6 +28,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -48,7 +50,7 @@ enum KernelFamily {
   KF_GEMM_NN = 0, KF_GEMM_NT, KF_GEMM_TN, KF_GEMM_DUAL, KF_BN_STATS, KF_ACT_FWD, KF_HIDDEN_BWD, KF_COLSUM, KF_SOFTMAX_XENT,
   KF_LOSS_REDUCE, KF_SOFTMAX, KF_ADAM, KF_EMA, KF_MISC, KF_CTC_BEST_PATH, KF_EDIT_DISTANCE, KF_CTC_BEAM, KF_CTC_ALIGN, KF_CTC_BEAM_LM,
   KF_CTC_BEAM_TOPK, KF_CTC_TOPK_ROWS, KF_CTC_SCORE, KF_CTC_MWER_SWEEP, KF_CTC_MWER_WEIGHTS, KF_CTC_MWER_GRAD,
-  KF_CTC_DEN_SWEEP, KF_CTC_DEN_GRAD, KF_CTC_ALIGN_WILD, KF_CTC_SPOT, KF_COUNT
+  KF_CTC_DEN_SWEEP, KF_CTC_DEN_GRAD, KF_CTC_ALIGN_WILD, KF_CTC_SPOT, KF_CTC_STREAM_PUSH, KF_COUNT
 };
 const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)",  "gemm_f32_tn(dW)",
                                      "gemm_f32_dual(dA+dW)",    "bn_stats",
@@ -59,7 +61,7 @@ const char* kFamilyName[KF_COUNT] = {"gemm_f32_nn(fwd affine)", "gemm_f32_nt(dA)
                                      "ctc_beam_search_topk",    "ctc_topk_rows",    "ctc_score",
                                      "ctc_mwer_sweep",          "ctc_mwer_weights", "ctc_mwer_grad",
                                      "ctc_den_sweep",           "ctc_den_grad",     "ctc_align_wild",
-                                     "ctc_spot"};
+                                     "ctc_spot",                "ctc_stream_push"};
 
 struct ProfRec {
   int family;
@@ -205,6 +207,8 @@ struct tfk_engine {
   // or the graph of tfk_ctc_graph_set: ctc_lm is weight [S, O], ctc_graph_next the transitions [S, O]; 0 states: no graph
   int32_t* ctc_graph_next = nullptr;
   int ctc_graph_states = 0, ctc_graph_start = 0;
+  // counts the models this engine has held: what a decode stream's lanes are bound to (an allocator reuses addresses)
+  uint64_t ctc_model_gen = 0;
   // forced alignment (tfk_ctc_align): the back-pointer rows and row log-sum-exps of ctc_viterbi_align
   unsigned char* ctc_bp = nullptr;
   size_t ctc_cap_bp = 0;
@@ -3131,6 +3135,7 @@ static int ctc_model_drop(tfk_engine* e) {
   e->ctc_graph_next = nullptr;
   e->ctc_graph_states = 0;
   e->ctc_graph_start = 0;
+  ++e->ctc_model_gen;  // (both setters come through here, whether they set or clear)
   if (w) HIPCHK(hipFree(w));
   if (nx) HIPCHK(hipFree(nx));
   return 0;
@@ -3198,6 +3203,52 @@ int tfk_ctc_graph_set(tfk_engine* e, const float* weight, const int32_t* next, i
   e->ctc_graph_next = d_n;
   e->ctc_graph_states = num_states;
   e->ctc_graph_start = start;
+  return 0;
+}
+// A push into a decode stream (ctc_stream.h): every refusal first, then the evaluation-mode forward as tfk_posteriors runs it,
+// then the resumable search on e->logits.  Nothing comes back and nothing is waited for.
+int tfk_ctc_stream_push(tfk_engine* e, tfk_ctc_stream* s, const float* X, int64_t ldx, int32_t T, const int32_t* chunk_len,
+                        float lm_weight, float label_bonus, int flags) {
+  const char* who = "tfk_ctc_stream_push";
+  if (!e) return fail(-1, "engine is NULL");
+  if (!s) return fail(-1, "%s: the stream is NULL", who);
+  if (flags & ~TFK_CTC_LM) return fail(-1, "flags %d: %s takes 0 or TFK_CTC_LM", flags, who);
+  if (T > 0 && !X) return fail(-1, "X is NULL");
+  if (s->device != e->cfg.device) return fail(-1, "%s: the stream lives on device %d, the engine on %d", who, s->device, e->cfg.device);
+  CtcStreamModel m;
+  m.kind = kCtcModelNone;
+  if (flags & TFK_CTC_LM) {
+    if (!e->ctc_lm_order && !e->ctc_graph_states) return fail(-1, "%s: no language model is set (tfk_ctc_lm_set)", who);
+    m.kind = e->ctc_graph_states ? kCtcModelGraph : kCtcModelNgram;
+    m.owner = e;
+    m.generation = e->ctc_model_gen;
+    m.table = e->ctc_lm; m.next = e->ctc_graph_next;
+    m.order = e->ctc_lm_order; m.num_states = e->ctc_graph_states; m.start = e->ctc_graph_start;
+    m.weight = lm_weight; m.bonus = label_bonus;
+  }
+  CHK(ctc_stream_push_checks(s, who, e->O, T, chunk_len, m));
+  HIPCHK(hipSetDevice(e->cfg.device));
+  Pass p = {};
+  if (T > 0) {
+    CHK(stage_pass(e, X, ldx, nullptr, T, 0, nullptr, &p));
+    CHK(forward(e, p.Xd, p.ld, T, 0, p.nact, p.nact, p.call));
+  }
+  {
+    // rows: one read of the logits; search: the chunk's rows and the lanes' saved beams, in and out
+    const double state = 2.0 * 4.0 * kCtcStreamArrays * (double)s->lanes * s->W;
+    std::unique_ptr<ProfScope> ps;
+    CHK(ctc_stream_push_launch(s, e->stream, e->logits, e->ldO, T, chunk_len, m, [&](int phase) {
+      ps.reset();
+      if (phase == 1) ps.reset(new ProfScope(e, KF_CTC_TOPK_ROWS, 0, 4.0 * T * e->O + 4.0 * T * kCtcTopkRowWords));
+      if (phase == 2)
+        ps.reset(new ProfScope(e, KF_CTC_STREAM_PUSH, 0,
+                               (s->label_topk ? 4.0 * T * kCtcTopkRowWords + 4.0 * T * s->W : 4.0 * T * e->O) + state));
+    }));
+  }
+  if (T > 0) {
+    CHK(finish_slot(e, 0, p.slot_before));
+    remember_pass(e, T, p.nact, p.call, p.Xd);
+  }
   return 0;
 }
 int tfk_ctc_beam_lm(tfk_engine* e, const float* X, int64_t ldx, int32_t T, const int32_t* utt_len, int32_t U,

@@ -526,6 +526,13 @@ class Engine(object):
         return self._beam_lm(self.lib.tfk_ctc_beam_lm_raw, raw, utt_lens, lm, beam_width, top_paths, labels, label_lens,
                              raw=(context_width, cmvn), label_topk=label_topk)
 
+    # ---- streaming decode: the beam search resumable across chunks (tfk_ctc_stream_*) ----
+    def ctc_stream_open(self, lanes, beam_width, max_frames, label_topk=None):
+        """A decode stream of `lanes` independent sessions on this engine (the contract is stated in include/tfkaldi_hip.h at
+        tfk_ctc_stream_create): each lane decodes at most max_frames frames between two resets.  label_topk: as ctc_beam.
+        Returns a CtcStreamHandle."""
+        return CtcStreamHandle(self, lanes, beam_width, max_frames, label_topk)
+
     # ---- CTC forced alignment: the Viterbi path of the known label sequence, per frame the label POSITION it emits ----
     def _align(self, fn, frames, utt_lens, labels, label_lens, raw=None):
         utt_lens, labels, label_lens = self._refs(utt_lens, labels, label_lens, False, "alignment")
@@ -1064,3 +1071,80 @@ class Engine(object):
         bits = np.empty(shape, dtype=np.uint16)
         check(self.lib.tfk_debug_fetch_twin(self._h, what, layer, bits.ctypes.data_as(c_void_p), bits.size))
         return (bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+class CtcStreamHandle(object):
+    """A decode stream (tfk_ctc_stream_*; the contract is stated in include/tfkaldi_hip.h) that decodes with one Engine's model,
+    on that engine's HIP stream.  Any way of cutting a lane's frames into pushes gives the result of one ctc_beam /
+    ctc_beam_lm call on all of them, bit for bit."""
+
+    def __init__(self, engine, lanes, beam_width, max_frames, label_topk=None):
+        self.engine, self.lib = engine, engine.lib
+        self.lanes, self.beam_width, self.max_frames = int(lanes), int(beam_width), int(max_frames)
+        self.label_topk = 0 if label_topk is None else int(label_topk)
+        if label_topk is not None and self.label_topk < 1:
+            raise ValueError("label_topk %d outside [1, 63]" % self.label_topk)
+        self._lm = None  # the model of the last push: what final=True takes the end-of-sequence switch from
+        self._h = c_void_p()
+        check(self.lib.tfk_ctc_stream_create(engine.O, self.lanes, self.beam_width, self.max_frames, self.label_topk,
+                                             byref(self._h)))
+        engine.on_close.append(self.close)  # (a stream is destroyed before the engine whose HIP stream it works on)
+
+    def _hip_stream(self):
+        stream = c_void_p()
+        check(self.lib.tfk_stream(self.engine._h, byref(stream)))
+        return stream
+
+    def push(self, rows, chunk_lens, lm=None):
+        """rows: SPLICED frames [sum(chunk_lens), F], lane l's chunk behind lane l - 1's; chunk_lens [lanes] (0: the lane
+        idles).  lm: None, or the NgramLM / GraphLM the prefixes are ranked by -- the same one, with the same weights, for as
+        long as a lane holds frames."""
+        chunk_lens = np.ascontiguousarray(chunk_lens, dtype=np.int32).reshape(-1)
+        if chunk_lens.size != self.lanes:
+            raise ValueError("%d chunk lengths for %d lanes" % (chunk_lens.size, self.lanes))
+        X = _f32(rows).reshape(-1, self.engine.F)
+        flags, weight, bonus = 0, 0.0, 0.0
+        if lm is not None:
+            self.engine.ctc_set_lm(lm)
+            flags, weight, bonus = _lib.CTC_LM, lm.weight, lm.label_bonus
+        check(self.lib.tfk_ctc_stream_push(self.engine._h, self._h, _ptr(X) if X.shape[0] else c_void_p(None), X.shape[1],
+                                           X.shape[0], _ptr(chunk_lens), c_float(weight), c_float(bonus), flags))
+        self._lm = lm
+
+    def result(self, top_paths=1, final=False, hyp_cap=None):
+        """The N-best of every lane over what has been pushed: (hyps, scores, am_scores) -- hyps[l][n] int32 label arrays (cut
+        at hyp_cap labels if given), scores / am_scores float32 [lanes, top_paths] as ctc_beam_lm returns them (without a
+        model the two are equal).  final: with a model whose end_of_sequence is set, rank and score with its end term."""
+        top_paths = int(top_paths)
+        frames = self.frames()
+        cap = int(frames.max()) if hyp_cap is None else int(hyp_cap)
+        hyp = np.empty((top_paths, self.lanes, max(cap, 0)), dtype=np.int32)
+        hyp_len = np.zeros((top_paths, self.lanes), dtype=np.int32)
+        score = np.empty((top_paths, self.lanes), dtype=np.float32)
+        am = np.empty((top_paths, self.lanes), dtype=np.float32)
+        flags = _lib.CTC_LM_EOS if final and self._lm is not None and self._lm.end_of_sequence else 0
+        check(self.lib.tfk_ctc_stream_result(self._h, self._hip_stream(), top_paths, flags, _ptr(hyp), cap, _ptr(hyp_len),
+                                             _ptr(score), _ptr(am)))
+        hyps = [[hyp[n, l, :min(hyp_len[n, l], cap)].copy() for n in range(top_paths)] for l in range(self.lanes)]
+        return hyps, np.ascontiguousarray(score.T), np.ascontiguousarray(am.T)
+
+    def reset(self, lane=None):
+        check(self.lib.tfk_ctc_stream_reset(self._h, self._hip_stream(), -1 if lane is None else int(lane)))
+
+    def frames(self):
+        out = np.zeros(self.lanes, dtype=np.int32)
+        check(self.lib.tfk_ctc_stream_frames(self._h, _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            if self.engine._h:  # (the engine closes its streams itself, before it goes)
+                self.engine.synchronize()
+            check(self.lib.tfk_ctc_stream_destroy(self._h))
+            self._h = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass

@@ -3,7 +3,7 @@ import os
 
 import numpy as np
 
-from ..processing.feature_reader import Unspliced, cmvn_table
+from ..processing.feature_reader import StreamSplicer, Unspliced, cmvn_table
 from .classifiers.dnn import ModelSaver
 
 
@@ -282,6 +282,17 @@ class Decoder(object):
                 dst.append(v)
         return out
 
+    def ctc_stream(self, lanes=1, beam_width=100, max_frames=None, lm=None, label_topk=None, context_width=None):
+        """Streaming decoding of a CTC model: `lanes` live sessions whose beam search is resumed chunk by chunk
+        (tfk_ctc_stream_*; the contract is stated in include/tfkaldi_hip.h).  Whatever the chunks are, the hypotheses and
+        scores are those of ctc_beam_search (with lm: ctc_beam_search_lm) on the frames pushed so far, bit for bit on the same
+        logits.  max_frames: the most frames a lane decodes between two resets (default: this decoder's max_length).
+        context_width: given, the chunks are UNSPLICED frames [n, D] and every lane splices them on the host
+        (processing.feature_reader.StreamSplicer), which holds a lane's newest context_width frames back until their right
+        context has arrived; None, the chunks are spliced rows.  Returns a CtcStream."""
+        return CtcStream(self, lanes, beam_width, self.max_length if max_frames is None else max_frames, lm, label_topk,
+                         context_width)
+
     def set_prior(self, prior):
         self.engine.set_prior(prior)
 
@@ -291,3 +302,73 @@ class Decoder(object):
 
     def close(self):
         self.engine.close()
+
+
+class CtcStream(object):
+    """What Decoder.ctc_stream returns: the sessions of one decode stream.  push() feeds chunks, partial() reads the N-best so
+    far (as often as wanted: it changes nothing), finish() ends a lane's utterance, reset() starts the next one."""
+
+    def __init__(self, decoder, lanes, beam_width, max_frames, lm, label_topk, context_width):
+        self.engine, self.lm, self.lanes = decoder.engine, lm, int(lanes)
+        self.context_width = None if context_width is None else int(context_width)
+        self.handle = self.engine.ctc_stream_open(lanes, beam_width, max_frames, label_topk)
+        self.splicers = None
+        if self.context_width is not None:
+            win = 2 * self.context_width + 1
+            if self.context_width < 0 or self.engine.F % win:
+                raise ValueError("input_dim %d is not a multiple of 2 * context_width + 1 = %d" % (self.engine.F, win))
+            self.splicers = [StreamSplicer(self.engine.F // win, self.context_width) for _ in range(self.lanes)]
+
+    def _push_rows(self, rows):
+        lens = [r.shape[0] for r in rows]
+        self.handle.push(np.concatenate(rows), lens, self.lm)
+
+    def push(self, chunks):
+        """chunks: one array per lane -- unspliced frames [n, D] with context_width, else spliced rows [n, F] -- or None for
+        a lane that has nothing new"""
+        if len(chunks) != self.lanes:
+            raise ValueError("%d chunks for %d lanes" % (len(chunks), self.lanes))
+        empty = np.zeros((0, self.engine.F), dtype=np.float32)
+        rows = []
+        for l, chunk in enumerate(chunks):
+            if chunk is None:
+                rows.append(empty)
+            elif self.splicers is not None:
+                rows.append(self.splicers[l].push(chunk))
+            else:
+                rows.append(np.ascontiguousarray(chunk, dtype=np.float32).reshape(-1, self.engine.F))
+        self._push_rows(rows)
+
+    def _nbest(self, top_paths, final):
+        hyps, scores, am = self.handle.result(top_paths, final=final)
+        return (hyps, scores) if self.lm is None else (hyps, scores, am)
+
+    def partial(self, top_paths=1):
+        """(hyps, scores[, am_scores with a model]) of every lane over the rows decoded so far: hyps[l][n], scores
+        [lanes, top_paths].  With context_width a lane's newest context_width frames are not in it yet."""
+        return self._nbest(top_paths, False)
+
+    def finish(self, lane, top_paths=1):
+        """The end of lane's utterance: its held-back frames are spliced with zero right context and pushed, and its final
+        N-best is returned -- (hyps[n], scores [top_paths][, am_scores]) -- ranked with the model's end term when the model has
+        one.  The lane keeps its state until reset()."""
+        rows = [np.zeros((0, self.engine.F), dtype=np.float32) for _ in range(self.lanes)]
+        if self.splicers is not None:
+            rows[lane] = self.splicers[lane].flush()
+        self._push_rows(rows)
+        return tuple(part[lane] for part in self._nbest(top_paths, True))
+
+    def reset(self, lane=None, cmvn=None):
+        """lane (None: every lane) starts a new utterance; cmvn: the [2, D] (mean, standard deviation) table its splicer
+        normalises the coming frames with (None: they come normalised)"""
+        self.handle.reset(lane)
+        if self.splicers is not None:
+            for l in range(self.lanes) if lane is None else [lane]:
+                self.splicers[l].flush()
+                self.splicers[l].set_cmvn(cmvn)
+
+    def frames(self):
+        return self.handle.frames()
+
+    def close(self):
+        self.handle.close()

@@ -156,3 +156,57 @@ def splice(utt, context_width):
     for j in range(1 + 2 * context_width):
         spliced[:, j * dim:(j + 1) * dim] = padded[j:j + num_frames]
     return spliced
+
+
+class StreamSplicer(object):
+    """`splice` (and, with `cmvn` -- a [2, D] float32 table of mean and standard deviation -- `Unspliced.normalised`) for
+    frames that arrive in chunks.  push(frames [n, D]) returns the spliced rows that are now complete, [m, D * (2c + 1)]: a
+    row needs its `c` right neighbours, so the newest c frames are held back and m may be 0.  flush() returns the last rows,
+    with zeros for the right context an utterance's end does not have, and starts a new utterance.
+
+    The rows of all pushes and of the flush, concatenated, are splice(normalised(all frames), c) bit for bit, whatever the
+    chunks are.  One difference: an utterance of fewer than 2c + 1 frames, for which splice returns None, still gives its rows
+    here -- the zero-padded splice written out -- because a stream cannot know its length in advance."""
+
+    def __init__(self, dim, context_width, cmvn=None):
+        self.dim, self.context_width = int(dim), int(context_width)
+        if self.dim < 1 or self.context_width < 0:
+            raise ValueError("dim %d / context_width %d" % (self.dim, self.context_width))
+        self.set_cmvn(cmvn)
+        self._start()
+
+    def set_cmvn(self, cmvn):
+        self.cmvn = None if cmvn is None else np.ascontiguousarray(cmvn, dtype=np.float32).reshape(2, self.dim)
+
+    def _start(self):
+        # the normalised frames that rows still to come will read: c zero frames stand for what lies before the utterance
+        self._held = np.zeros((self.context_width, self.dim), dtype=np.float32)
+        self._done = 0  # rows given out
+        self._seen = 0  # frames taken in
+
+    def _rows(self, frames, final):
+        c, dim = self.context_width, self.dim
+        if frames.shape[0]:
+            if self.cmvn is not None:  # (the expression of Unspliced.normalised)
+                frames = np.divide(np.subtract(frames, self.cmvn[0]), self.cmvn[1])
+            self._held = np.concatenate([self._held, frames])
+            self._seen += frames.shape[0]
+        if final and c:
+            self._held = np.concatenate([self._held, np.zeros((c, dim), dtype=np.float32)])
+        # _held[0] is frame _done - c; row t reads frames t - c .. t + c
+        m = max(self._held.shape[0] - 2 * c, 0)
+        out = np.empty((m, dim * (2 * c + 1)), dtype=np.float32)
+        for j in range(2 * c + 1):
+            out[:, j * dim:(j + 1) * dim] = self._held[j:j + m]
+        self._held = self._held[m:]
+        self._done += m
+        return out
+
+    def push(self, frames):
+        frames = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, self.dim)
+        return self._rows(frames, False)
+
+    def flush(self):
+        out = self._rows(np.zeros((0, self.dim), dtype=np.float32), True)
+        self._start()
+        return out

@@ -46,6 +46,11 @@ dependent chain of Tn steps).
 with wildcard gaps (tfk_accumulate_ctc_wild) beside one plain CTC step on the same build and batch -- wild="ends" at penalty 0,
 then random flags at penalty 0.5 -- the three steps timed in alternating blocks (median and spread over all blocks, and the
 spread of the plain step's block medians), then the profiler's per-kernel-family rows of each.
+`--stream` runs the streaming leg alone (its output is kept in profiles/ctc_stream_bench.txt): one utterance of 800 frames per lane
+decoded through a decode stream (tfk_ctc_stream_push / _result) on 1 and 16 lanes at W = 10 and 100 in chunks of 10, 40 and 160
+frames, dense and pruned at label_topk = 8, acoustic and with an order-3 n-gram -- per case the wall time of the whole utterance
+and per push, the profiler's rows per push (the forward's families summed, the row pre-pass, the search), the time of one
+result, the one-shot call (tfk_ctc_beam / _lm) on the same frames, and the frames per second of a lane.
 `--decode-only` skips the training step (e.g. under rocprofv3), `--align-only` runs the align leg alone, `--topk-only` the
 pruned and the wide leg alone."""
 import os
@@ -120,6 +125,14 @@ def main():
         wild_loss_leg(eng, rng, X, utt, labels, np.asarray(lab), Tu)
         eng.close()
         return
+    if "--stream" in sys.argv:
+        eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
+        bias = np.zeros(O, np.float32)
+        bias[O - 1] = 2.0
+        eng.set(_lib.BIASES, eng.L, bias)
+        stream_leg(eng, X, U, Tu, labels, np.asarray(lab))
+        eng.close()
+        return
     if "--topk-only" in sys.argv:
         eng.set(_lib.WEIGHTS, eng.L, rng.standard_normal((eng.H, O)).astype(np.float32) / np.sqrt(eng.H))
         bias = np.zeros(O, np.float32)
@@ -134,6 +147,69 @@ def main():
     decode_leg(eng, X, utt, labels, lab, rng)
     eng.close()
     wide_leg(rng, X, utt, cfg)
+
+
+def stream_leg(eng, X, U, Tu, labels, lab):
+    """streaming decode against the one-shot call on the same frames (see the module docstring)"""
+    from tfkaldi_amd.neuralNetworks.ctc_lm import NgramLM
+    refs = np.split(labels, np.cumsum(lab)[:-1])
+    ngram = NgramLM.from_label_sequences(refs, eng.O - 1, 3, weight=0.5, label_bonus=1.0)
+    search = ("ctc_stream_push", "ctc_topk_rows")
+    print("streaming decode, blank bias 2.0: %d frames per lane; times in ms; fwd / rows / search = the profiler's kernel time per "
+          "push (forward families summed, ctc_topk_rows, ctc_stream_push)" % Tu)
+    print("%5s %4s %5s %-6s %-6s | %9s %9s %8s %8s %8s | %8s | %9s %9s | %10s"
+          % ("lanes", "W", "chunk", "search", "model", "utt wall", "per push", "fwd", "rows", "search", "result", "one-shot",
+             "stream/1", "frames/s"))
+    for lanes in (1, 16):
+        frames = X[:lanes * Tu].reshape(lanes, Tu, -1)
+        utt = [Tu] * lanes
+        for W in (10, 100):
+            for topk in (None, 8):
+                for lm in (None, ngram):
+                    def oneshot():
+                        if lm is None:
+                            return eng.ctc_beam(frames.reshape(lanes * Tu, -1), utt, beam_width=W, label_topk=topk)
+                        return eng.ctc_beam_lm(frames.reshape(lanes * Tu, -1), utt, lm, beam_width=W, label_topk=topk)
+                    want = oneshot()
+                    times = []
+                    for _ in range(5):
+                        t0 = time.perf_counter()
+                        oneshot()
+                        times.append(time.perf_counter() - t0)
+                    one_ms = 1e3 * float(np.median(times))
+                    for chunk in (10, 40, 160):
+                        pushes = [np.ascontiguousarray(frames[:, t:t + chunk]).reshape(lanes * chunk, -1) for t in range(0, Tu, chunk)]
+                        lens = [chunk] * lanes
+                        h = eng.ctc_stream_open(lanes, W, Tu, topk)
+
+                        def utterance():
+                            h.reset()
+                            for rows in pushes:
+                                h.push(rows, lens, lm)
+                            eng.synchronize()
+                        utterance()
+                        walls = []
+                        for _ in range(3):
+                            t0 = time.perf_counter()
+                            utterance()
+                            walls.append(time.perf_counter() - t0)
+                        wall = float(np.median(walls))
+                        eng.profile_begin()
+                        utterance()
+                        fam = {s["name"]: s["total_ms"] for s in eng.profile_end()}
+                        fwd = sum(v for k, v in fam.items() if k not in search) / len(pushes)
+                        res = []
+                        for _ in range(5):
+                            t0 = time.perf_counter()
+                            got = h.result(1, final=False)
+                            res.append(time.perf_counter() - t0)
+                        same = all(np.array_equal(a[0], b[0]) for a, b in zip(got[0], want[0]))  # (the forwards differ in rows)
+                        h.close()
+                        print("%5d %4d %5d %-6s %-6s | %9.3f %9.3f %8.3f %8.3f %8.3f | %8.3f | %9.3f %9.2f | %10.0f%s"
+                              % (lanes, W, chunk, "dense" if topk is None else "top-%d" % topk, "none" if lm is None else "3-gram",
+                                 1e3 * wall, 1e3 * wall / len(pushes), fwd, fam.get("ctc_topk_rows", 0.0) / len(pushes),
+                                 fam.get("ctc_stream_push", 0.0) / len(pushes), 1e3 * float(np.median(res)), one_ms,
+                                 1e3 * wall / one_ms, Tu / wall, "" if same else "  (best paths differ from the one-shot call's)"))
 
 
 def train_leg(eng, X, raw, utt, labels, lab, T):
