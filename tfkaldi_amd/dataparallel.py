@@ -96,6 +96,12 @@ class RawMicroBatch(object):
     def __init__(self, raw, y, lens, context_width, cmvn=None):
         self.raw, self.y, self.lens, self.context_width, self.cmvn = raw, y, lens, context_width, cmvn
 
+    def accumulate(self, engine, last, train):
+        if train:
+            engine.accumulate_raw(self.raw, self.y, self.lens, self.context_width, last=last, cmvn=self.cmvn)
+        else:
+            engine.eval_accumulate_raw(self.raw, self.y, self.lens, self.context_width, cmvn=self.cmvn)
+
 
 class StackedRawMicroBatches(object):
     """SEVERAL consecutive micro-batches of one optimiser step handed to the engine in one call
@@ -107,6 +113,13 @@ class StackedRawMicroBatches(object):
         self.raw, self.y, self.lens, self.context_width, self.cmvn = raw, y, lens, context_width, cmvn
         self.seg_utts = list(seg_utts)
 
+    def accumulate(self, engine, last, train):
+        args = (self.raw, self.y, self.lens, self.context_width, self.seg_utts)
+        if train:
+            engine.accumulate_stacked_raw(*args, last=last, cmvn=self.cmvn)
+        else:
+            engine.eval_accumulate_stacked_raw(*args, cmvn=self.cmvn)
+
 
 class CtcMicroBatch(object):
     """A micro-batch for the CTC loss: spliced frames [T, F] of U utterances, their frame counts, their label
@@ -115,6 +128,22 @@ class CtcMicroBatch(object):
     def __init__(self, X, utt_lens, labels, label_lens, context_width=None, cmvn=None):
         self.X, self.utt_lens, self.labels, self.label_lens = X, utt_lens, labels, label_lens
         self.context_width, self.cmvn = context_width, cmvn  # context_width set: X holds UNSPLICED frames
+
+    def _call(self, engine, stem, *extra, **kw):
+        """engine.<stem>(frames, frame counts, labels, label counts, *extra, **kw) on spliced frames; on unspliced ones
+        engine.<stem>_raw with the context width behind the frame counts and the cmvn table by keyword"""
+        if self.context_width is None:
+            return getattr(engine, stem)(self.X, self.utt_lens, self.labels, self.label_lens, *extra, **kw)
+        return getattr(engine, stem + "_raw")(self.X, self.utt_lens, self.context_width, self.labels, self.label_lens, *extra,
+                                              cmvn=self.cmvn, **kw)
+
+    def accumulate(self, engine, last, train):
+        if train:
+            self._call(engine, "accumulate_ctc", last=last)
+        elif self.context_width is None:
+            engine.eval_accumulate_ctc(self.X, self.utt_lens, self.labels, self.label_lens)
+        else:  # (unspliced frames have no evaluation method of their own: the training one's switch)
+            self._call(engine, "accumulate_ctc", train=False)
 
 
 class CtcMwerMicroBatch(CtcMicroBatch):
@@ -134,12 +163,22 @@ class CtcMwerMicroBatch(CtcMicroBatch):
         if tables and (hyp_labels is None or hyp_lens is None):
             raise ValueError("pair tables: hyp_counts, hyp_labels and hyp_lens go together")
         if not tables:
-            top_paths = beam_width if top_paths is None else top_paths
-            if not 1 <= int(top_paths) <= int(beam_width):
-                raise ValueError("top_paths %r outside [1, beam_width = %r]" % (top_paths, beam_width))
+            top_paths = self.search_paths(beam_width, top_paths)
         self.hyp_counts, self.hyp_labels, self.hyp_lens = hyp_counts, hyp_labels, hyp_lens
         self.beam_width, self.top_paths, self.lm, self.label_topk = beam_width, top_paths, lm, label_topk
         self.add_reference, self.ctc_weight = bool(add_reference), float(ctc_weight)
+
+    @staticmethod
+    def search_paths(beam_width, top_paths):
+        """the length of the N-best list of a search of width beam_width: top_paths, by default all of the beam"""
+        top_paths = beam_width if top_paths is None else top_paths
+        if not 1 <= int(top_paths) <= int(beam_width):
+            raise ValueError("top_paths %r outside [1, beam_width = %r]" % (top_paths, beam_width))
+        return top_paths
+
+    def accumulate(self, engine, last, train):
+        self._call(engine, "accumulate_ctc_mwer", *_mwer_tables(engine, self), ctc_weight=self.ctc_weight, last=last,
+                   train=train)
 
 
 class CtcMmiMicroBatch(CtcMicroBatch):
@@ -153,15 +192,9 @@ class CtcMmiMicroBatch(CtcMicroBatch):
             raise ValueError("a CtcMmiMicroBatch needs its denominator graph")
         self.graph, self.lm_scale, self.ctc_weight = graph, float(lm_scale), float(ctc_weight)
 
-
-def _accumulate_mmi(engine, mb, last, train):
-    engine.ctc_set_den(mb.graph)
-    if mb.context_width is not None:
-        engine.accumulate_ctc_mmi_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, lm_scale=mb.lm_scale,
-                                      ctc_weight=mb.ctc_weight, last=last, cmvn=mb.cmvn, train=train)
-    else:
-        engine.accumulate_ctc_mmi(mb.X, mb.utt_lens, mb.labels, mb.label_lens, lm_scale=mb.lm_scale,
-                                  ctc_weight=mb.ctc_weight, last=last, train=train)
+    def accumulate(self, engine, last, train):
+        engine.ctc_set_den(self.graph)
+        self._call(engine, "accumulate_ctc_mmi", lm_scale=self.lm_scale, ctc_weight=self.ctc_weight, last=last, train=train)
 
 
 class CtcWildMicroBatch(CtcMicroBatch):
@@ -172,19 +205,35 @@ class CtcWildMicroBatch(CtcMicroBatch):
         CtcMicroBatch.__init__(self, X, utt_lens, labels, label_lens, context_width, cmvn)
         self.wild, self.penalty = wild, float(penalty)
 
+    def accumulate(self, engine, last, train):
+        self._call(engine, "accumulate_ctc_wild", wild=self.wild, penalty=self.penalty, last=last, train=train)
 
-def _accumulate_wild(engine, mb, last, train):
-    if mb.context_width is not None:
-        engine.accumulate_ctc_wild_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, wild=mb.wild,
-                                       penalty=mb.penalty, last=last, cmvn=mb.cmvn, train=train)
-    else:
-        engine.accumulate_ctc_wild(mb.X, mb.utt_lens, mb.labels, mb.label_lens, wild=mb.wild, penalty=mb.penalty, last=last,
-                                   train=train)
+
+def _search(mb, beam_width=None, lm=None, label_topk=None):
+    """(Engine method, keywords) of the decode of a CTC micro-batch: best path (beam_width None) or prefix beam search of that
+    width, ranked by lm, pruned to label_topk labels per frame; the *_raw entry when the micro-batch holds unspliced frames"""
+    entry, kw = ("ctc_greedy", {}) if beam_width is None else ("ctc_beam", {"beam_width": beam_width})
+    if lm is not None:
+        entry, kw = "ctc_beam_lm", dict(kw, lm=lm)
+    if label_topk is not None:  # (forwarded only when given: an engine without the keyword keeps serving the other calls)
+        kw = dict(kw, label_topk=label_topk)
+    if mb.context_width is not None:  # unspliced frames: CMVN + splice on the device
+        entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
+    return entry, kw
+
+
+def _nbest(engine, mb, top_paths, beam_width, lm, label_topk):
+    """per utterance the top_paths best of that search, without the padding paths: they are not hypotheses, and the search's
+    own ranking value -- beam score -inf -- is what marks them"""
+    import numpy as np
+    entry, kw = _search(mb, beam_width, lm, label_topk)
+    found, beam = getattr(engine, entry)(mb.X, mb.utt_lens, top_paths=int(top_paths), **kw)[:2]
+    return [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
 
 
 def _mwer_tables(engine, mb):
     """the pair tables of an MWER micro-batch: its own, or the N best of a search on `engine` (evaluation passes that leave
-    the sums of an open step alone); padding paths -- beam score -inf -- are dropped, as _label_errors drops them"""
+    the sums of an open step alone)"""
     import numpy as np
     from .neuralNetworks.ctc_mwer import pair_tables
     refs = np.split(np.asarray(mb.labels, dtype=np.int32), np.cumsum(mb.label_lens, dtype=np.int64)[:-1])
@@ -196,68 +245,27 @@ def _mwer_tables(engine, mb):
         cuts = np.cumsum(mb.hyp_counts, dtype=np.int64)
         hyps = [flat[int(a):int(b)] for a, b in zip(np.concatenate([[0], cuts[:-1]]), cuts)]
         return pair_tables(hyps, refs, add_reference=True)
-    entry, kw = "ctc_beam", {"beam_width": mb.beam_width}
-    if mb.lm is not None:
-        entry, kw = "ctc_beam_lm", dict(kw, lm=mb.lm)
-    if mb.label_topk is not None:
-        kw = dict(kw, label_topk=mb.label_topk)
-    if mb.context_width is not None:
-        entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
-    found, beam = getattr(engine, entry)(mb.X, mb.utt_lens, top_paths=int(mb.top_paths), **kw)[:2]
-    kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+    kept = _nbest(engine, mb, mb.top_paths, mb.beam_width, mb.lm, mb.label_topk)
     return pair_tables(kept, refs, add_reference=mb.add_reference)
 
 
-def _accumulate_mwer(engine, mb, last, train):
-    counts, labels, lens = _mwer_tables(engine, mb)
-    if mb.context_width is not None:
-        engine.accumulate_ctc_mwer_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, counts, labels, lens,
-                                       ctc_weight=mb.ctc_weight, last=last, cmvn=mb.cmvn, train=train)
+def _dispatch(engine, mb, last, train):
+    """one micro-batch into the sums of the step (train) or of the evaluation: the classes above know their entry, anything
+    else is an (X, y) pair of spliced frames and targets"""
+    if hasattr(mb, "accumulate"):
+        mb.accumulate(engine, last, train)
+    elif train:
+        engine.accumulate(mb[0], mb[1], last=last)
     else:
-        engine.accumulate_ctc_mwer(mb.X, mb.utt_lens, mb.labels, mb.label_lens, counts, labels, lens,
-                                   ctc_weight=mb.ctc_weight, last=last, train=train)
+        engine.eval_accumulate(mb[0], mb[1])
 
 
 def _accumulate(engine, mb, last):
-    if isinstance(mb, CtcMwerMicroBatch):
-        _accumulate_mwer(engine, mb, last, True)
-    elif isinstance(mb, CtcMmiMicroBatch):
-        _accumulate_mmi(engine, mb, last, True)
-    elif isinstance(mb, CtcWildMicroBatch):
-        _accumulate_wild(engine, mb, last, True)
-    elif isinstance(mb, CtcMicroBatch):
-        if mb.context_width is not None:
-            engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, last=last,
-                                      cmvn=mb.cmvn)
-        else:
-            engine.accumulate_ctc(mb.X, mb.utt_lens, mb.labels, mb.label_lens, last=last)
-    elif isinstance(mb, RawMicroBatch):
-        engine.accumulate_raw(mb.raw, mb.y, mb.lens, mb.context_width, last=last, cmvn=mb.cmvn)
-    elif isinstance(mb, StackedRawMicroBatches):
-        engine.accumulate_stacked_raw(mb.raw, mb.y, mb.lens, mb.context_width, mb.seg_utts, last=last, cmvn=mb.cmvn)
-    else:
-        engine.accumulate(mb[0], mb[1], last=last)
+    _dispatch(engine, mb, last, True)
 
 
 def _eval_accumulate(engine, mb):
-    if isinstance(mb, CtcMwerMicroBatch):
-        _accumulate_mwer(engine, mb, False, False)
-    elif isinstance(mb, CtcMmiMicroBatch):
-        _accumulate_mmi(engine, mb, False, False)
-    elif isinstance(mb, CtcWildMicroBatch):
-        _accumulate_wild(engine, mb, False, False)
-    elif isinstance(mb, CtcMicroBatch):
-        if mb.context_width is not None:
-            engine.accumulate_ctc_raw(mb.X, mb.utt_lens, mb.context_width, mb.labels, mb.label_lens, cmvn=mb.cmvn,
-                                      train=False)
-        else:
-            engine.eval_accumulate_ctc(mb.X, mb.utt_lens, mb.labels, mb.label_lens)
-    elif isinstance(mb, RawMicroBatch):
-        engine.eval_accumulate_raw(mb.raw, mb.y, mb.lens, mb.context_width, cmvn=mb.cmvn)
-    elif isinstance(mb, StackedRawMicroBatches):
-        engine.eval_accumulate_stacked_raw(mb.raw, mb.y, mb.lens, mb.context_width, mb.seg_utts, cmvn=mb.cmvn)
-    else:
-        engine.eval_accumulate(mb[0], mb[1])
+    _dispatch(engine, mb, False, False)
 
 
 def _eval_accumulate_all(engine, mine):
@@ -274,32 +282,28 @@ def _eval_accumulate_all(engine, mine):
         _eval_accumulate(engine, mb)
 
 
-def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
-    """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
-    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM or GraphLM; label_topk:
-    pruned to the frame's label_topk most probable labels).  rescore_paths: an int N takes the search's N best, scores them
-    exactly with their label errors (ctc_score) and counts the hypothesis that is best after decoder.ctc_rerank."""
+def _beam_settings(beam_width, lm=None, label_topk=None, rescore_paths=None):
+    """refuse the settings of a beam search where there is none (beam_width None: best-path decoding)"""
     if rescore_paths is not None and beam_width is None:
         raise ValueError("rescoring re-ranks the N best of a beam search: give beam_width with rescore_paths")
     if lm is not None and beam_width is None:
         raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
     if label_topk is not None and beam_width is None:
         raise ValueError("label_topk prunes a beam search: give beam_width with label_topk")
+
+
+def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None, rescore_paths=None):
+    """(sum of the edit distances, number of reference labels) of one CTC micro-batch under best-path decoding
+    (beam_width None) or under prefix beam search of that width (its best path; lm: ranked with that NgramLM or GraphLM; label_topk:
+    pruned to the frame's label_topk most probable labels).  rescore_paths: an int N takes the search's N best, scores them
+    exactly with their label errors (ctc_score) and counts the hypothesis that is best after decoder.ctc_rerank."""
+    _beam_settings(beam_width, lm, label_topk, rescore_paths)
     if not isinstance(mb, CtcMicroBatch):
         raise TypeError("label errors need CTC micro-batches (label sequences), not %s" % type(mb).__name__)
-    entry, kw = ("ctc_greedy", {}) if beam_width is None else ("ctc_beam", {"beam_width": beam_width})
-    if lm is not None:
-        entry, kw = "ctc_beam_lm", dict(kw, lm=lm)
-    if label_topk is not None:  # (forwarded only when given: an engine without the keyword keeps serving the other calls)
-        kw = dict(kw, label_topk=label_topk)
-    if mb.context_width is not None:  # unspliced frames: CMVN + splice on the device
-        entry, kw = entry + "_raw", dict(kw, context_width=mb.context_width, cmvn=mb.cmvn)
     import numpy as np
     if rescore_paths is not None:
         from .neuralNetworks.decoder import ctc_rerank
-        found, beam = getattr(engine, entry)(mb.X, mb.utt_lens, top_paths=int(rescore_paths), **kw)[:2]
-        # (padding paths -- beam score -inf -- are not pairs; the search's own ranking value is what marks them)
-        kept = [[h for h, s in zip(hs, sc) if s > -np.inf] for hs, sc in zip(found, beam)]
+        kept = _nbest(engine, mb, rescore_paths, beam_width, lm, label_topk)
         flat = [h for hs in kept for h in hs]
         labels = np.concatenate(flat) if flat else np.zeros(0, dtype=np.int32)
         raw = mb.context_width is not None
@@ -309,6 +313,7 @@ def _label_errors(engine, mb, beam_width=None, lm=None, label_topk=None, rescore
         edits = [int(d[ctc_rerank(hs, sc, lm)[0][0]]) if len(hs) else int(n)
                  for hs, sc, d, n in zip(kept, scores, dists, mb.label_lens)]
         return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
+    entry, kw = _search(mb, beam_width, lm, label_topk)
     edits = getattr(engine, entry)(mb.X, mb.utt_lens, labels=mb.labels, label_lens=mb.label_lens, **kw)[-1]
     return int(np.sum(edits, dtype=np.int64)), int(np.sum(mb.label_lens, dtype=np.int64))
 

@@ -22,6 +22,17 @@ def _ptr(a):
     return c_void_p(None) if a is None else a.ctypes.data_as(c_void_p)
 
 
+def _finite_nonneg(name, value):
+    """`value` (a weight, a scale, a per-frame penalty) as a float that is finite and >= 0, or a ValueError that names it"""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s %r must be finite and >= 0" % (name, value))
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError("%s %r must be finite and >= 0" % (name, v))
+    return v
+
+
 def _levenshtein(a, b):
     """Levenshtein distance (unit costs) of two int sequences: what the entries report when the engine is not called"""
     row = np.arange(len(b) + 1)
@@ -287,18 +298,26 @@ class Engine(object):
         check(self.lib.tfk_accumulate_stacked(self._h, c_void_p(x_ptr), ldx, c_void_p(y_ptr), T, seg.ctypes.data_as(c_void_p),
                                               seg.size, flags))
 
-    def accumulate_stacked_raw(self, raw, y, lens, context_width, seg_utts, last=False, cmvn=None):
-        """unspliced frames of all utterances back to back, seg_utts utterances per micro-batch (CMVN + splice on the device)"""
+    def _raw_targets(self, raw, y, lens, cmvn):
+        """host frames, targets and cmvn table of a frame-level *_raw entry that takes no device tensor, checked against
+        each other: (raw, y, lens, cmvn table to keep alive over the call, its pointer)"""
         raw, lens = self._raw_batch(raw, lens)
         y = np.ascontiguousarray(y, dtype=np.int32)
-        seg = np.ascontiguousarray(seg_utts, dtype=np.int32)
         cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, lens)
         if y.shape != (raw.shape[0],):
             raise ValueError("targets %s do not match %d frames" % (y.shape, raw.shape[0]))
-        check(self.lib.tfk_accumulate_stacked_raw(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], y.ctypes.data_as(c_void_p),
-                                                  raw.shape[0], lens.ctypes.data_as(c_void_p), lens.size, int(context_width),
-                                                  cmvn_ptr, seg.ctypes.data_as(c_void_p), seg.size,
-                                                  _lib.LAST_MICROBATCH if last else 0))
+        return raw, y, lens, cmvn, cmvn_ptr
+
+    def _stacked_raw(self, fn, raw, y, lens, context_width, seg_utts, cmvn, flags):
+        seg = np.ascontiguousarray(seg_utts, dtype=np.int32)  # (in front of the cmvn and target checks, as it always was)
+        raw, y, lens, cmvn, cmvn_ptr = self._raw_targets(raw, y, lens, cmvn)
+        check(fn(self._h, _ptr(raw), raw.shape[1], _ptr(y), raw.shape[0], _ptr(lens), lens.size, int(context_width), cmvn_ptr,
+                 _ptr(seg), seg.size, flags))
+
+    def accumulate_stacked_raw(self, raw, y, lens, context_width, seg_utts, last=False, cmvn=None):
+        """unspliced frames of all utterances back to back, seg_utts utterances per micro-batch (CMVN + splice on the device)"""
+        self._stacked_raw(self.lib.tfk_accumulate_stacked_raw, raw, y, lens, context_width, seg_utts, cmvn,
+                          _lib.LAST_MICROBATCH if last else 0)
 
     def eval_accumulate_stacked(self, X, y, seg_rows):
         """Trainer.evaluate's micro-batches X[rows_0 + rows_1 + ..., F] back to back in ONE call: rows are independent in
@@ -310,25 +329,12 @@ class Engine(object):
 
     def eval_accumulate_stacked_raw(self, raw, y, lens, context_width, seg_utts, cmvn=None):
         """the same from unspliced frames (CMVN + splice on the device), seg_utts utterances per micro-batch"""
-        raw, lens = self._raw_batch(raw, lens)
-        y = np.ascontiguousarray(y, dtype=np.int32)
-        seg = np.ascontiguousarray(seg_utts, dtype=np.int32)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, lens)
-        if y.shape != (raw.shape[0],):
-            raise ValueError("targets %s do not match %d frames" % (y.shape, raw.shape[0]))
-        check(self.lib.tfk_eval_accumulate_stacked_raw(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1],
-                                                       y.ctypes.data_as(c_void_p), raw.shape[0], lens.ctypes.data_as(c_void_p),
-                                                       lens.size, int(context_width), cmvn_ptr, seg.ctypes.data_as(c_void_p),
-                                                       seg.size, 0))
+        self._stacked_raw(self.lib.tfk_eval_accumulate_stacked_raw, raw, y, lens, context_width, seg_utts, cmvn, 0)
 
     def eval_accumulate_raw(self, raw, y, lens, context_width, cmvn=None):
-        raw, lens = self._raw_batch(raw, lens)
-        y = np.ascontiguousarray(y, dtype=np.int32)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, lens)
-        check(self.lib.tfk_eval_accumulate_raw(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1],
-                                               y.ctypes.data_as(c_void_p), raw.shape[0],
-                                               lens.ctypes.data_as(c_void_p), lens.size, int(context_width),
-                                               cmvn_ptr, 0))
+        raw, y, lens, cmvn, cmvn_ptr = self._raw_targets(raw, y, lens, cmvn)
+        check(self.lib.tfk_eval_accumulate_raw(self._h, _ptr(raw), raw.shape[1], _ptr(y), raw.shape[0], _ptr(lens), lens.size,
+                                               int(context_width), cmvn_ptr, 0))
 
     def _out_buffer(self, rows):
         """[rows, O] result array; in pinned host memory (torch's caching pinned allocator) so that the engine can
@@ -705,28 +711,31 @@ class Engine(object):
             raise ValueError("CTC micro-batch: frames %s / utterance lengths / labels do not match" % (X.shape,))
         return X, utt_lens, labels, label_lens
 
+    def _accumulate_ctc(self, stem, X, utt_lens, labels, label_lens, own=(), last=False, train=True, raw=None):
+        """The C call of every CTC training entry, tfk_[eval_]accumulate_ctc<stem>[_raw]: stem "", "_wild", "_mwer" or
+        "_mmi"; X, utt_lens, labels, label_lens after _ctc_args; own: the criterion's own arguments behind the label counts,
+        validated, in the order of its signature -- arrays (None: a NULL pointer) and floats.  train=False is the
+        evaluation-mode entry, which never ends a step; raw = (context_width, cmvn): X holds UNSPLICED frames."""
+        name = "tfk_%saccumulate_ctc%s%s" % ("" if train else "eval_", stem, "" if raw is None else "_raw")
+        splice = ()
+        if raw is not None:
+            cmvn, cmvn_ptr = self._cmvn_table(raw[1], X, utt_lens)  # (cmvn: the array, alive for the length of the call)
+            splice = (int(raw[0]), cmvn_ptr)
+        check(getattr(self.lib, name)(self._h, _ptr(X), X.shape[1], X.shape[0], _ptr(utt_lens), utt_lens.size, *splice,
+                                      _ptr(labels), _ptr(label_lens),
+                                      *[_ptr(a) if a is None or isinstance(a, np.ndarray) else a for a in own],
+                                      _lib.LAST_MICROBATCH if (last and train) else 0))
+
     def accumulate_ctc_raw(self, raw, utt_lens, context_width, labels, label_lens, last=False, cmvn=None, train=True):
         """CTC micro-batch from UNSPLICED frames: CMVN + splice on the device (as accumulate_raw)"""
-        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
-        fn = self.lib.tfk_accumulate_ctc_raw if train else self.lib.tfk_eval_accumulate_ctc_raw
-        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
-                 label_lens.ctypes.data_as(c_void_p), _lib.LAST_MICROBATCH if (last and train) else 0))
+        self._accumulate_ctc("", *self._ctc_args(raw, utt_lens, labels, label_lens), last=last, train=train,
+                             raw=(context_width, cmvn))
 
     def accumulate_ctc(self, X, utt_lens, labels, label_lens, last=False):
-        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
-        check(self.lib.tfk_accumulate_ctc(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
-                                          utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
-                                          labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
-                                          _lib.LAST_MICROBATCH if last else 0))
+        self._accumulate_ctc("", *self._ctc_args(X, utt_lens, labels, label_lens), last=last)
 
     def eval_accumulate_ctc(self, X, utt_lens, labels, label_lens):
-        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
-        check(self.lib.tfk_eval_accumulate_ctc(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0],
-                                               utt_lens.ctypes.data_as(c_void_p), utt_lens.size,
-                                               labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
-                                               0))
+        self._accumulate_ctc("", *self._ctc_args(X, utt_lens, labels, label_lens), train=False)
 
     # ---- expected label errors over an N-best list (MWER) on top of ctc_weight x the CTC loss ----
     @staticmethod
@@ -741,10 +750,7 @@ class Engine(object):
         if hyp_lens.size != P or np.any(hyp_lens < 0) or int(hyp_lens.sum(dtype=np.int64)) != hyp_labels.size:
             raise ValueError("hypotheses: %d label counts (sum %d) for %d hypotheses and %d labels"
                              % (hyp_lens.size, int(hyp_lens.sum(dtype=np.int64)), P, hyp_labels.size))
-        ctc_weight = float(ctc_weight)
-        if not (np.isfinite(ctc_weight) and ctc_weight >= 0.0):
-            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
-        return hyp_counts, hyp_labels, hyp_lens, ctc_weight
+        return hyp_counts, hyp_labels, hyp_lens, _finite_nonneg("ctc_weight", ctc_weight)
 
     def accumulate_ctc_mwer(self, X, utt_lens, labels, label_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight=0.0,
                             last=False, train=True):
@@ -755,26 +761,15 @@ class Engine(object):
         per pair, as ctc_score takes them (neuralNetworks/ctc_mwer.pair_tables builds the three from lists).  The step's
         average (apply) is expected label errors per reference label + ctc_weight x CTC loss per label.
         train=False: evaluation-mode forward, loss only."""
-        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
-        hyp_counts, hyp_labels, hyp_lens, ctc_weight = self._mwer_args(utt_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight)
-        fn = self.lib.tfk_accumulate_ctc_mwer if train else self.lib.tfk_eval_accumulate_ctc_mwer
-        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p),
-                 hyp_counts.ctypes.data_as(c_void_p), hyp_labels.ctypes.data_as(c_void_p),
-                 hyp_lens.ctypes.data_as(c_void_p), ctc_weight, _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(X, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_mwer", *args, self._mwer_args(args[1], hyp_counts, hyp_labels, hyp_lens, ctc_weight), last, train)
 
     def accumulate_ctc_mwer_raw(self, raw, utt_lens, context_width, labels, label_lens, hyp_counts, hyp_labels, hyp_lens,
                                 ctc_weight=0.0, last=False, cmvn=None, train=True):
         """accumulate_ctc_mwer from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
-        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
-        hyp_counts, hyp_labels, hyp_lens, ctc_weight = self._mwer_args(utt_lens, hyp_counts, hyp_labels, hyp_lens, ctc_weight)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
-        fn = self.lib.tfk_accumulate_ctc_mwer_raw if train else self.lib.tfk_eval_accumulate_ctc_mwer_raw
-        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
-                 label_lens.ctypes.data_as(c_void_p), hyp_counts.ctypes.data_as(c_void_p),
-                 hyp_labels.ctypes.data_as(c_void_p), hyp_lens.ctypes.data_as(c_void_p), ctc_weight,
-                 _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(raw, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_mwer", *args, self._mwer_args(args[1], hyp_counts, hyp_labels, hyp_lens, ctc_weight), last, train,
+                             (context_width, cmvn))
 
     # ---- MMI against a denominator graph (CTC-CRF): the exact sum over every label sequence a grammar accepts ----
     def ctc_set_den(self, graph):
@@ -805,26 +800,14 @@ class Engine(object):
         return {"num_states": S.value, "num_arcs": A.value, "num_groups": K.value, "composed_states": S.value + A.value,
                 "residence": ("global", "lds", "lds+tables")[where.value]}
 
-    @staticmethod
-    def _mmi_args(lm_scale, ctc_weight):
-        lm_scale, ctc_weight = float(lm_scale), float(ctc_weight)
-        if not (np.isfinite(lm_scale) and lm_scale >= 0.0):
-            raise ValueError("lm_scale %r must be finite and >= 0" % (lm_scale,))
-        if not (np.isfinite(ctc_weight) and ctc_weight >= 0.0):
-            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
-        return lm_scale, ctc_weight
-
     def accumulate_ctc_mmi(self, X, utt_lens, labels, label_lens, lm_scale=1.0, ctc_weight=0.0, last=False, train=True):
         """One micro-batch of the MMI criterion (tfk_accumulate_ctc_mmi; the contract is stated in include/tfkaldi_hip.h):
         -(log p_ctc(reference) + lm_scale G(reference)) + log Z, Z the exact sum over every label sequence the denominator
         graph of ctc_set_den accepts, plus ctc_weight x the CTC loss.  Arguments as accumulate_ctc.  train=False:
         evaluation-mode forward, loss only."""
-        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
-        lm_scale, ctc_weight = self._mmi_args(lm_scale, ctc_weight)
-        fn = self.lib.tfk_accumulate_ctc_mmi if train else self.lib.tfk_eval_accumulate_ctc_mmi
-        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p), lm_scale, ctc_weight,
-                 _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(X, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_mmi", *args, (_finite_nonneg("lm_scale", lm_scale), _finite_nonneg("ctc_weight", ctc_weight)),
+                             last, train)
 
     def eval_accumulate_ctc_mmi(self, X, utt_lens, labels, label_lens, lm_scale=1.0, ctc_weight=0.0):
         self.accumulate_ctc_mmi(X, utt_lens, labels, label_lens, lm_scale, ctc_weight, train=False)
@@ -832,22 +815,11 @@ class Engine(object):
     def accumulate_ctc_mmi_raw(self, raw, utt_lens, context_width, labels, label_lens, lm_scale=1.0, ctc_weight=0.0,
                                last=False, cmvn=None, train=True):
         """accumulate_ctc_mmi from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
-        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
-        lm_scale, ctc_weight = self._mmi_args(lm_scale, ctc_weight)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
-        fn = self.lib.tfk_accumulate_ctc_mmi_raw if train else self.lib.tfk_eval_accumulate_ctc_mmi_raw
-        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
-                 label_lens.ctypes.data_as(c_void_p), lm_scale, ctc_weight, _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(raw, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_mmi", *args, (_finite_nonneg("lm_scale", lm_scale), _finite_nonneg("ctc_weight", ctc_weight)),
+                             last, train, (context_width, cmvn))
 
     # ---- CTC loss with wildcard gaps (W-CTC / STC): training on transcripts that cover only part of a recording ----
-    @staticmethod
-    def _penalty(penalty):
-        penalty = float(penalty)
-        if not (np.isfinite(penalty) and penalty >= 0.0):
-            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
-        return penalty
-
     def accumulate_ctc_wild(self, X, utt_lens, labels, label_lens, wild=None, penalty=0.0, last=False, train=True):
         """One micro-batch of the CTC loss with WILDCARD GAPS (tfk_accumulate_ctc_wild; the contract is stated in
         include/tfkaldi_hip.h): `wild` as ctc_align_wild takes it -- label_lens[u] + 1 flags per utterance, back to back
@@ -855,12 +827,9 @@ class Engine(object):
         loss is the value of the lattice: a labelling that several paths reach through a wildcard counts once per path, so
         it can be negative.  With no flag set this is accumulate_ctc bit for bit.  train=False: evaluation-mode forward,
         loss only."""
-        X, utt_lens, labels, label_lens = self._ctc_args(X, utt_lens, labels, label_lens)
-        wild, penalty = self._wild(wild, label_lens, "CTC micro-batch"), self._penalty(penalty)
-        fn = self.lib.tfk_accumulate_ctc_wild if train else self.lib.tfk_eval_accumulate_ctc_wild
-        check(fn(self._h, X.ctypes.data_as(c_void_p), X.shape[1], X.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, labels.ctypes.data_as(c_void_p), label_lens.ctypes.data_as(c_void_p), _ptr(wild), penalty,
-                 _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(X, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_wild", *args, (self._wild(wild, args[3], "CTC micro-batch"), _finite_nonneg("penalty", penalty)),
+                             last, train)
 
     def eval_accumulate_ctc_wild(self, X, utt_lens, labels, label_lens, wild=None, penalty=0.0):
         self.accumulate_ctc_wild(X, utt_lens, labels, label_lens, wild, penalty, train=False)
@@ -868,13 +837,9 @@ class Engine(object):
     def accumulate_ctc_wild_raw(self, raw, utt_lens, context_width, labels, label_lens, wild=None, penalty=0.0, last=False,
                                 cmvn=None, train=True):
         """accumulate_ctc_wild from UNSPLICED frames: CMVN + splice on the device (as accumulate_ctc_raw)"""
-        raw, utt_lens, labels, label_lens = self._ctc_args(raw, utt_lens, labels, label_lens)
-        wild, penalty = self._wild(wild, label_lens, "CTC micro-batch"), self._penalty(penalty)
-        cmvn, cmvn_ptr = self._cmvn_table(cmvn, raw, utt_lens)
-        fn = self.lib.tfk_accumulate_ctc_wild_raw if train else self.lib.tfk_eval_accumulate_ctc_wild_raw
-        check(fn(self._h, raw.ctypes.data_as(c_void_p), raw.shape[1], raw.shape[0], utt_lens.ctypes.data_as(c_void_p),
-                 utt_lens.size, int(context_width), cmvn_ptr, labels.ctypes.data_as(c_void_p),
-                 label_lens.ctypes.data_as(c_void_p), _ptr(wild), penalty, _lib.LAST_MICROBATCH if (last and train) else 0))
+        args = self._ctc_args(raw, utt_lens, labels, label_lens)
+        self._accumulate_ctc("_wild", *args, (self._wild(wild, args[3], "CTC micro-batch"), _finite_nonneg("penalty", penalty)),
+                             last, train, (context_width, cmvn))
 
     # ---- the optimiser step in parts (data parallel: Adam per reduced span, see dataparallel.BucketReducer) ----
     def apply_begin(self):

@@ -20,8 +20,9 @@ from abc import ABCMeta, abstractmethod
 import numpy as np
 
 from .. import _lib
-from ..dataparallel import (CtcMicroBatch, DataParallel, RawMicroBatch, StackedRawMicroBatches, local_device, partition,
-                            rank_seed)
+from ..dataparallel import (CtcMicroBatch, CtcMmiMicroBatch, CtcMwerMicroBatch, CtcWildMicroBatch, DataParallel,
+                            RawMicroBatch, StackedRawMicroBatches, _beam_settings, local_device, partition, rank_seed)
+from ..engine import _finite_nonneg
 from ..processing.feature_reader import Unspliced, cmvn_table
 from .classifiers.dnn import ModelSaver
 
@@ -171,8 +172,10 @@ class Trainer(object, metaclass=ABCMeta):
                   % (num_utt, per_minibatch, num_utt - used))
             Trainer._warned_truncation = True
 
-    def _microbatches(self, inputs, targets):
-        out = []
+    def _groups(self, inputs, targets):
+        """(utterance indices, micro-batch) of every micro-batch the batch yields: a group without frames yields none.  A
+        generator: the truncation warning and the per-group checks of frames against targets run as it is consumed, so
+        consume it to its end before the first micro-batch reaches the engine (as _microbatches does)"""
         plan = microbatch_indices(len(inputs), self.numutterances_per_minibatch)
         used = sum(len(idx) for idx in plan)
         if used < len(inputs):
@@ -186,12 +189,12 @@ class Trainer(object, metaclass=ABCMeta):
                 X = np.concatenate(frames, axis=0)
                 if X.shape[0] == 0:
                     continue
-                out.append(CtcMicroBatch(
+                yield idx, CtcMicroBatch(
                     X, np.array([f.shape[0] for f in frames], dtype=np.int32),
                     np.concatenate([np.asarray(targets[i]).astype(np.int32).reshape(-1) for i in idx]),
                     np.array([np.asarray(targets[i]).size for i in idx], dtype=np.int32),
                     context_width=inputs[idx[0]].context_width if deferred else None,
-                    cmvn=cmvn_table([inputs[i] for i in idx]) if deferred else None))
+                    cmvn=cmvn_table([inputs[i] for i in idx]) if deferred else None)
                 continue
             for i in idx:
                 if inputs[i].shape[0] != targets[i].shape[0]:
@@ -204,12 +207,30 @@ class Trainer(object, metaclass=ABCMeta):
                 # splice on the device: ship the unspliced frames + utterance lengths
                 raw = np.concatenate([np.asarray(inputs[i]) for i in idx], axis=0)
                 lens = np.array([inputs[i].shape[0] for i in idx], dtype=np.int32)
-                out.append(RawMicroBatch(raw, y, lens, inputs[idx[0]].context_width,
-                                         cmvn_table([inputs[i] for i in idx])))
+                yield idx, RawMicroBatch(raw, y, lens, inputs[idx[0]].context_width, cmvn_table([inputs[i] for i in idx]))
             else:
                 X = np.concatenate([_spliced(inputs[i]) for i in idx], axis=0)
-                out.append((X, y))
-        return out
+                yield idx, (X, y)
+
+    def _microbatches(self, inputs, targets):
+        return [mb for _, mb in self._groups(inputs, targets)]
+
+    def _step(self, microbatches, name, num_utts):
+        """one optimiser step over the micro-batches of the method `name`: the loss before the update"""
+        if not microbatches:
+            raise ValueError("%s: the batch holds no frames (no micro-batch could be built from %d utterance(s))"
+                             % (name, num_utts))
+        loss = self.dp.train_step(self.engine, microbatches)
+        self._summarise(loss)
+        return loss
+
+    def _evaluation(self, inputs, targets, build, *settings):
+        """the loss of the micro-batches build(inputs, targets, *settings) in evaluation mode; None when there is no data
+        (trainer.py:372-373)"""
+        if inputs is None or targets is None:
+            return None
+        microbatches = build(inputs, targets, *settings)  # (what it refuses, it refuses before the engine is touched)
+        return self.dp.eval_step(self.engine, microbatches)
 
     def update(self, inputs, targets):
         """
@@ -221,13 +242,7 @@ class Trainer(object, metaclass=ABCMeta):
         Returns:
             the loss at this step (batch_loss / num_frames, evaluated before the parameter update)
         """
-        microbatches = self._microbatches(inputs, targets)
-        if not microbatches:
-            raise ValueError("Trainer.update: the batch holds no frames (no micro-batch could be built from %d "
-                             "utterance(s))" % len(inputs))
-        loss = self.dp.train_step(self.engine, microbatches)
-        self._summarise(loss)
-        return loss
+        return self._step(self._microbatches(inputs, targets), "Trainer.update", len(inputs))
 
     def _summarise(self, loss):
         if self.summarywriter is not None:
@@ -237,9 +252,7 @@ class Trainer(object, metaclass=ABCMeta):
 
     def evaluate(self, inputs, targets):
         """the loss of the batch in evaluation mode; None when there is no data (trainer.py:372-373)"""
-        if inputs is None or targets is None:
-            return None
-        return self.dp.eval_step(self.engine, self._microbatches(inputs, targets))
+        return self._evaluation(inputs, targets, self._microbatches)
 
     # ---- the packed feed (BatchDispenser.next_packed): this rank's utterances only, CMVN + splice in HBM ----
     def selector(self):
@@ -375,12 +388,7 @@ class CTCTrainer(Trainer):
         more than 64 outputs be searched; it needs a beam_width too.  rescore_paths: an int N decodes the N best, scores
         them exactly on the device with their label errors (tfk_ctc_score) and counts the hypothesis that is best after
         re-ranking by exact score (+ lm.score with lm: decoder.ctc_rerank); it needs a beam_width as well."""
-        if rescore_paths is not None and beam_width is None:
-            raise ValueError("rescoring re-ranks the N best of a beam search: give beam_width with rescore_paths")
-        if lm is not None and beam_width is None:
-            raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm")
-        if label_topk is not None and beam_width is None:
-            raise ValueError("label_topk prunes a beam search: give beam_width with label_topk")
+        _beam_settings(beam_width, lm, label_topk, rescore_paths)
         if inputs is None or targets is None:
             return None
         kw = {} if lm is None else {"lm": lm}
@@ -392,28 +400,20 @@ class CTCTrainer(Trainer):
 
     # ---- training on the expected number of label errors over an N-best list (MWER) ----
     def _mwer_microbatches(self, inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk, add_reference, hyps):
-        from ..dataparallel import CtcMwerMicroBatch
         from .ctc_mwer import pair_tables
         if hyps is None:
             if beam_width is None:
                 raise ValueError("MWER needs an N-best list: give beam_width (and top_paths), or hyps")
-            top_paths = beam_width if top_paths is None else top_paths
-            if not 1 <= int(top_paths) <= int(beam_width):
-                raise ValueError("top_paths %r outside [1, beam_width = %r]" % (top_paths, beam_width))
+            top_paths = CtcMwerMicroBatch.search_paths(beam_width, top_paths)
         elif len(hyps) != len(inputs):
             raise ValueError("hyps: %d hypothesis lists for %d utterances" % (len(hyps), len(inputs)))
         if lm is not None and (beam_width is None or hyps is not None):
             raise ValueError("a language model ranks the prefixes of a beam search: give beam_width with lm (and no hyps)")
         if label_topk is not None and (beam_width is None or hyps is not None):
             raise ValueError("label_topk prunes a beam search: give beam_width with label_topk (and no hyps)")
-        if not (np.isfinite(ctc_weight) and ctc_weight >= 0):
-            raise ValueError("ctc_weight %r must be finite and >= 0" % (ctc_weight,))
+        ctc_weight = _finite_nonneg("ctc_weight", ctc_weight)
         out = []
-        plan = [idx for idx in microbatch_indices(len(inputs), self.numutterances_per_minibatch) if idx]
-        plain = self._microbatches(inputs, targets)  # (one per non-empty group that holds frames, in plan order)
-        plan = [idx for idx in plan if sum(np.asarray(inputs[i]).shape[0] for i in idx) > 0]
-        assert len(plan) == len(plain)
-        for idx, mb in zip(plan, plain):
+        for idx, mb in self._groups(inputs, targets):
             kw = dict(context_width=mb.context_width, cmvn=mb.cmvn, add_reference=add_reference, ctc_weight=ctc_weight)
             if hyps is None:
                 kw.update(beam_width=int(beam_width), top_paths=int(top_paths), lm=lm, label_topk=label_topk)
@@ -433,32 +433,20 @@ class CTCTrainer(Trainer):
         hyps, a list per utterance of label arrays, which skips the search.  add_reference: the reference joins every list
         that lacks it.  The hypotheses are scored on the train-mode logits of the step itself.  Returns the step's loss:
         expected label errors per reference label + ctc_weight x CTC loss per label, before the update."""
-        microbatches = self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
-                                               add_reference, hyps)
-        if not microbatches:
-            raise ValueError("CTCTrainer.update_mwer: the batch holds no frames (no micro-batch could be built from %d "
-                             "utterance(s))" % len(inputs))
-        loss = self.dp.train_step(self.engine, microbatches)
-        self._summarise(loss)
-        return loss
+        return self._step(self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
+                                                  add_reference, hyps), "CTCTrainer.update_mwer", len(inputs))
 
     def evaluate_mwer(self, inputs, targets, beam_width=None, top_paths=None, ctc_weight=0.01, lm=None, label_topk=None,
                       add_reference=False, hyps=None):
         """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
-        if inputs is None or targets is None:
-            return None
-        microbatches = self._mwer_microbatches(inputs, targets, beam_width, top_paths, ctc_weight, lm, label_topk,
-                                               add_reference, hyps)
-        return self.dp.eval_step(self.engine, microbatches)
+        return self._evaluation(inputs, targets, self._mwer_microbatches, beam_width, top_paths, ctc_weight, lm, label_topk,
+                                add_reference, hyps)
 
     # ---- MMI against a denominator graph (CTC-CRF): the exact sum over every label sequence a grammar accepts ----
     def _mmi_microbatches(self, inputs, targets, graph, lm_scale, ctc_weight):
-        from ..dataparallel import CtcMmiMicroBatch
         if graph is None or getattr(graph, "next", None) is None:
             raise ValueError("MMI needs a denominator graph: a ctc_lm.GraphLM")
-        for name, v in (("lm_scale", lm_scale), ("ctc_weight", ctc_weight)):
-            if not (np.isfinite(v) and v >= 0):
-                raise ValueError("%s %r must be finite and >= 0" % (name, v))
+        lm_scale, ctc_weight = _finite_nonneg("lm_scale", lm_scale), _finite_nonneg("ctc_weight", ctc_weight)
         for u, ref in enumerate(targets):
             ref = np.asarray(ref).reshape(-1)
             s, at = graph._walk(ref)
@@ -480,41 +468,25 @@ class CTCTrainer(Trainer):
         denominator from transcripts is GraphLM.from_ngram(NgramLM.from_label_sequences(...)); a lexicon is
         GraphLM.from_lexicon(...).  A reference the graph rejects raises a ValueError that names the utterance before the
         step starts.  Returns the step's loss per reference label, before the update."""
-        microbatches = self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight)
-        if not microbatches:
-            raise ValueError("CTCTrainer.update_mmi: the batch holds no frames (no micro-batch could be built from %d "
-                             "utterance(s))" % len(inputs))
-        loss = self.dp.train_step(self.engine, microbatches)
-        self._summarise(loss)
-        return loss
+        return self._step(self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight), "CTCTrainer.update_mmi",
+                          len(inputs))
 
     def evaluate_mmi(self, inputs, targets, graph, lm_scale=1.0, ctc_weight=0.0):
         """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
-        if inputs is None or targets is None:
-            return None
-        return self.dp.eval_step(self.engine, self._mmi_microbatches(inputs, targets, graph, lm_scale, ctc_weight))
+        return self._evaluation(inputs, targets, self._mmi_microbatches, graph, lm_scale, ctc_weight)
 
     # ---- training on partial transcripts: the CTC loss with wildcard gaps (W-CTC / STC) ----
     def _wild_microbatches(self, inputs, targets, wild, penalty):
-        from ..dataparallel import CtcWildMicroBatch
         from .decoder import Decoder
         if len(inputs) != len(targets):
             raise ValueError("%d utterances, %d label sequences" % (len(inputs), len(targets)))
-        try:
-            penalty = float(penalty)
-        except (TypeError, ValueError):
-            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
-        if not (np.isfinite(penalty) and penalty >= 0):
-            raise ValueError("penalty %r must be finite and >= 0" % (penalty,))
+        penalty = _finite_nonneg("penalty", penalty)
         seqs = [np.asarray(t).astype(np.int32).reshape(-1) for t in targets]
         flat = Decoder._gap_flags(wild, seqs)  # (validates `wild`; len(s) + 1 flags per utterance, back to back)
         first = np.concatenate([[0], np.cumsum([s.size + 1 for s in seqs], dtype=np.int64)])
-        plan = [idx for idx in microbatch_indices(len(inputs), self.numutterances_per_minibatch) if idx]
-        plain = self._microbatches(inputs, targets)  # (one per non-empty group that holds frames, in plan order)
-        plan = [idx for idx in plan if sum(np.asarray(inputs[i]).shape[0] for i in idx) > 0]
-        assert len(plan) == len(plain)
         out = []
-        for idx, mb in zip(plan, plain):  # the flags are cut per micro-batch: utterance u's start at lab_off[u] + u THERE
+        # the flags are cut per micro-batch: utterance u's start at lab_off[u] + u THERE
+        for idx, mb in self._groups(inputs, targets):
             cut = None if flat is None else np.concatenate([flat[first[i]:first[i + 1]] for i in idx])
             out.append(CtcWildMicroBatch(mb.X, mb.utt_lens, mb.labels, mb.label_lens, wild=cut, penalty=penalty,
                                          context_width=mb.context_width, cmvn=mb.cmvn))
@@ -529,16 +501,8 @@ class CTCTrainer(Trainer):
         utterance.  The loss is the value of the lattice -- a frame labelling that several lattice paths reach through a
         wildcard counts once per path -- so it can be negative.  A bad wild or penalty raises a ValueError before the step
         starts.  Returns the step's loss per reference label, before the update."""
-        microbatches = self._wild_microbatches(inputs, targets, wild, penalty)
-        if not microbatches:
-            raise ValueError("CTCTrainer.update_wild: the batch holds no frames (no micro-batch could be built from %d "
-                             "utterance(s))" % len(inputs))
-        loss = self.dp.train_step(self.engine, microbatches)
-        self._summarise(loss)
-        return loss
+        return self._step(self._wild_microbatches(inputs, targets, wild, penalty), "CTCTrainer.update_wild", len(inputs))
 
     def evaluate_wild(self, inputs, targets, wild="ends", penalty=0.0):
         """the same figure in evaluation mode, without an update; None when there is no data (as evaluate)"""
-        if inputs is None or targets is None:
-            return None
-        return self.dp.eval_step(self.engine, self._wild_microbatches(inputs, targets, wild, penalty))
+        return self._evaluation(inputs, targets, self._wild_microbatches, wild, penalty)
